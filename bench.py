@@ -11,11 +11,19 @@ enqueued back to back and the host synchronises once at the end of the timed reg
 reference reads the objective only every 100 iterations, test/synthetic_data_hard_test.py:143-155); every step's value is
 checked after timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--prec mixed] [--graph auto|on|off] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--prec mixed] [--graph auto|on|off]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary] [--no-grad] [--no-side]]
         (N > 1 without a rendezvous in the environment: starts the N ranks itself as a child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  `value` is whole-job evaluations/s (D=512 is a fixed total: strong scaling).
+A plain run sets up, warms up, times the K steps and prints the line (with the psi2 roofline of the timed steps' own events).
+--full adds the side measurements, each on runs of its own: the gram / Cholesky kernel figures (`secondary`), the exact-fp32
+and fp64 runs of the same metric, objective + gradients and the over-T model (`objective_and_gradients`, `objective_over_t`)
+and the CPU baseline (`cpu_baseline`); the --no-* flags drop single ones of them.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (fp64): objective_terms [5] = (objective,
+f_hat, KL, DP objective, hyper-prior) and per_dimension_terms [D, 5] (rank 0's output dims when D is sharded).  The inputs
+are seeded (utils/synthetic.py), so two builds compare output for output.
 """
 import argparse
 import json
@@ -46,7 +54,14 @@ def parse():
     ap.add_argument('--graph', default='auto', choices=['auto', 'on', 'off'],
                     help='replay the evaluation from a HIP graph (auto = off: measured no faster)')
     ap.add_argument('--cpu-dims', type=int, default=0, help='output dims in the bounded CPU sample (0 = auto)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also the side measurements (gram / Cholesky figures, exact-fp32 and fp64 runs, objective + gradients, '
+                         'CPU baseline); off: only the timed steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 def host_cpu():
@@ -313,6 +328,10 @@ def main():
     assert np.isfinite(objs).all() and np.all(objs == objs[0]), 'objective is not finite / not reproducible'
     assert os.environ.get('DPGP_BENCH_NOCHECK') or np.array_equal(objs, outs[:, 0].cpu().numpy())
     assert os.environ.get('DPGP_BENCH_NOCHECK') or int(info.abs().max().item()) == 0, 'a factorisation failed or a precision guard fired'
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, 'objective_terms.npy'), outs[-1].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(a.dump_outputs, 'per_dimension_terms.npy'), terms.cpu().numpy().astype(np.float64))
 
     def rate(mdl, steps, warm=3):
         """evals/s of another model object on the same problem (side figures; same launch mode, short run)."""
@@ -371,9 +390,9 @@ def main():
         res['roofline'].update({'traffic': traffic, 'traffic_source': traffic_rec, 'kernel_ms': psi2_ms,
                                 'kernel': 'psi2_pairs_kernel (+ K_uu task slice)' if f16_path else 'psi2_mfma_kernel (+ K_uu task slice)',
                                 'algorithmic_exps': exps, 'algorithmic_flops': flops})
-        if world == 1 and not a.no_secondary:
+        if world == 1 and a.full and not a.no_secondary:
             res['secondary'] = secondary(dev, shape, p)
-        if world == 1 and not a.no_side and a.prec == 'mixed':
+        if world == 1 and a.full and not a.no_side and a.prec == 'mixed':
             # the same metric in the other arithmetic: exact-fp32 products (v_mfma_f32_16x16x4_f32, no f16 split / range limit)
             # and the reference's own fp64 (src/utils/types.py:13-14) — short runs, same problem, same step definition
             ks = max(3, min(10, a.steps))
@@ -390,7 +409,7 @@ def main():
             res['precision_check'] = {'objective_mixed': float(objs[0]), 'objective_fp32_exact': o32, 'objective_f64': o64,
                                       'rel_err_mixed_vs_f64': abs(float(objs[0]) - o64) / abs(o64),
                                       'rel_err_fp32_exact_vs_f64': abs(o32 - o64) / abs(o64)}
-        if world == 1 and not a.no_grad and (a.prec == 'mixed' or (a.prec == 'f64' and m <= 128)):
+        if world == 1 and a.full and not a.no_grad and (a.prec == 'mixed' or (a.prec == 'f64' and m <= 128)):
             # side measurements, not the headline metric: (1) one objective evaluation + the gradients of all raw variables
             # (backward pass; what one Adam iteration of the reference needs); (2) one objective evaluation
             # of the over-T formulation dp_gp_lvm_t on the same data (8f row 3: T Psi2's instead of D)
@@ -469,7 +488,7 @@ def main():
                         return 1e3 * (time.perf_counter() - t1) / reps
                     res['objective_over_t']['optimise_iteration_ms'] = opt_ms(model_t)
                     res['objective_and_gradients']['optimise_iteration_ms'] = opt_ms(model)
-        if not a.no_cpu_baseline and world == 1:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(a.config, p, shape, a.cpu_dims)
         print(json.dumps(res))
     if world > 1:

@@ -18,10 +18,10 @@ if [ "$part" = trace ] || [ "$part" = all ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_c3_f64 -- python3 bench.py --steps 10 --warmup 3 --prec f64 $S > $O/bench_trace_c3_f64.log 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_linalg -- python3 scratch/prof_linalg.py 8 > $O/trace_linalg.log 2>&1
   echo "traces done" > $O/progress.txt
-  python3 bench.py > $O/bench_default_output.json 2> $O/bench_default.err
-  python3 bench.py --config 2 --no-cpu-baseline > $O/bench_config2_output.json 2>> $O/bench_default.err
-  python3 bench.py --config 4 --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_config4_output.json 2>> $O/bench_default.err
-  python3 bench.py --config 5 --no-cpu-baseline > $O/bench_config5_output.json 2>> $O/bench_default.err
+  python3 bench.py --full > $O/bench_default_output.json 2> $O/bench_default.err
+  python3 bench.py --full --config 2 --no-cpu-baseline > $O/bench_config2_output.json 2>> $O/bench_default.err
+  python3 bench.py --full --config 4 --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_config4_output.json 2>> $O/bench_default.err
+  python3 bench.py --full --config 5 --no-cpu-baseline > $O/bench_config5_output.json 2>> $O/bench_default.err
   echo "bench lines done" >> $O/progress.txt
 fi
 if [ "$part" = pmc ] || [ "$part" = all ]; then

@@ -32,10 +32,10 @@ PY
   for c in 3 2 5; do rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_grad_c$c -- python3 $O/grad_run.py $c 8 > $O/trace_grad_c$c.log 2>&1; done
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_grad_c4 -- python3 $O/grad_run.py 4 3 > $O/trace_grad_c4.log 2>&1
   echo "traces done" > $O/progress.txt
-  python3 bench.py > $O/bench_default_output.json 2> $O/bench_default.err
-  python3 bench.py --config 2 --no-cpu-baseline > $O/bench_config2_output.json 2>> $O/bench_default.err
-  python3 bench.py --config 4 --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_config4_output.json 2>> $O/bench_default.err
-  python3 bench.py --config 5 --no-cpu-baseline > $O/bench_config5_output.json 2>> $O/bench_default.err
+  python3 bench.py --full > $O/bench_default_output.json 2> $O/bench_default.err
+  python3 bench.py --full --config 2 --no-cpu-baseline > $O/bench_config2_output.json 2>> $O/bench_default.err
+  python3 bench.py --full --config 4 --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_config4_output.json 2>> $O/bench_default.err
+  python3 bench.py --full --config 5 --no-cpu-baseline > $O/bench_config5_output.json 2>> $O/bench_default.err
   echo "bench lines done" >> $O/progress.txt
 fi
 if [ "$part" = pmc ] || [ "$part" = all ]; then
