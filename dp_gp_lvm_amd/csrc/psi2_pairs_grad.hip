@@ -83,6 +83,16 @@ __device__ __forceinline__ void pg_put(_Float16 *xt, int f, int rr, float v) {
     }
 }
 
+// kg(gamma_dq): the power of two that lifts a small gamma into [1/2, 1) (1 for gamma >= 1/2).  The observation features a'_q, b_q
+// are proportional to w = gamma / (gamma s + 1): for the gamma of a latent dim that ARD has switched off (1e-2 ... 1e-6) their f16
+// (hi, lo) pairs go subnormal.  The features carry kg; the finishing kernels that read them (pg_finish_pairs_kernel,
+// pg_finish_m1_kernel) divide it out exactly, from the same fp32 gamma.
+__host__ __device__ __forceinline__ float pg_kg(float g) {
+    int ex = 0;
+    (void)frexpf(g, &ex);
+    return ex < 0 ? ldexpf(1.0f, min(-ex, 100)) : 1.0f;
+}
+
 // ---- the row of the exponent GEMM's A operand for observation n of output dim d (as phase A of psi2_pairs_kernel) --------
 // dst: 8 KS words (16 KS f16 slots) in REGISTERS (the loop over the latent dims is unrolled to the most a K-step count holds, so every
 // index is a constant); the features a'_q, b_q (the values the slots were split from) of this row (rr within its tile) go into the
@@ -122,12 +132,16 @@ __device__ __forceinline__ bool pg_obs_row(bool valid, int n, int Q, const doubl
                 dst[3 * q] = __builtin_bit_cast(unsigned, w0);
                 dst[3 * q + 1] = __builtin_bit_cast(unsigned, w1);
                 dst[3 * q + 2] = __builtin_bit_cast(unsigned, w2);
-                // (xw: a per-row weight of the features — y_nd for the Psi1 term)
-                pg_put(xt, 2 * q, rr, xw * ((float)ah + (float)alo));
-                pg_put(xt, 2 * q + 1, rr, xw * ((float)bh + (float)blo));
+                // (xw: a per-row weight of the features — ky_d y_nd for the Psi1 term; kg: see pg_kg.  The features are the coefficients
+                // themselves, not their (hi, lo) pairs in the exponent operand: for a small gamma those pairs are subnormal and off by
+                // up to a few per cent, which moved d/dz of that latent dim by as much; in the exponent the same error is ~1e-8 absolute)
+                const float xk = xw * pg_kg(g), fa = xk * a, fb = xk * bb;
+                oor |= !(fabsf(fa) <= 60000.0f) | !(fabsf(fb) <= 60000.0f);    // (f16 range of the features: w up to ~150, include/dpgp.h)
+                pg_put(xt, 2 * q, rr, fa);
+                pg_put(xt, 2 * q + 1, rr, fb);
             }
         }
-        oor = !(cc >= -8192.0f);                                  // range guard of the f16-split exponent (psi2_pairs.hip)
+        oor |= !(cc >= -8192.0f);                                 // range guard of the f16-split exponent (psi2_pairs.hip)
         cc = fmaxf(cc, -60000.0f) + PG_WSHIFT;
     } else {
 #pragma unroll
@@ -287,8 +301,8 @@ __global__ __launch_bounds__(256) void pg_obs_images_kernel(int N, int Q, const 
                                                             const double *__restrict__ mu, const double *__restrict__ s,
                                                             const double *__restrict__ gamma, _Float16 *__restrict__ cimg,
                                                             _Float16 *__restrict__ ximg, int NT, int *__restrict__ flag,
-                                                            const double *__restrict__ y, int ldy) {
-    // y != nullptr: the images of the Psi1 term (den = g s + 1, half coefficients, features weighted by y_nd)
+                                                            const double *__restrict__ y, int ldy, const float *__restrict__ ky) {
+    // y != nullptr: the images of the Psi1 term (den = g s + 1, half coefficients, features weighted by ky_d y_nd: pg_ky_kernel)
     constexpr int NFB = PgCfg<KS>::NFB, XP = pg_xp(NFB), NFZ = NFB == 2 ? 48 : 32;   // (NFZ: feature slots that exist in the image)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     float *gq = reinterpret_cast<float *>(smem_raw), *zc = gq + 32;
@@ -303,9 +317,10 @@ __global__ __launch_bounds__(256) void pg_obs_images_kernel(int N, int Q, const 
     {
         _Float16 *xr = xt + (size_t)(t >> 5) * 512 * XP;
         const bool valid = n0 + t < N;
-        const float xw = (y && valid) ? (float)y[(size_t)(n0 + t) * ldy + d] : 1.0f;
+        const float xw = (y && valid) ? (float)(y[(size_t)(n0 + t) * ldy + d] * (double)ky[d]) : 1.0f;
         unsigned row[8 * KS];
-        const bool oor = pg_obs_row<KS>(valid, n0 + t, Q, mu, s, gq, zc, row, xr, t & 31, y ? 1.0f : 2.0f, y ? 0.5f : 1.0f, xw);
+        bool oor = pg_obs_row<KS>(valid, n0 + t, Q, mu, s, gq, zc, row, xr, t & 31, y ? 1.0f : 2.0f, y ? 0.5f : 1.0f, xw);
+        oor |= !(fabsf(xw) <= 32.0f);                             // (non-finite y, or a column beyond the range ky covers: include/dpgp.h)
         pg_put(xr, 2 * Q, t & 31, valid ? xw : 0.0f);
         for (int f = 2 * Q + 1; f < NFZ; ++f) pg_put(xr, f, t & 31, 0.0f);
         if (oor) atomicOr(flag, 1);
@@ -367,6 +382,32 @@ __global__ __launch_bounds__(256) void pg_pair_images_kernel(int Ppad, int Q, co
     for (int e = t; e < ntl * 64 * XP; e += 256) xd[e] = reinterpret_cast<const pg_u4 *>(xt)[e];
 }
 
+// ky[d]: the power of two that brings max_n |y_nd| into [2^4, 2^5) (1 for a zero or non-finite column).  The Psi1 pass's features are
+// ky_d y_nd (a', b, 1): with |a'| <= ~12 w (w = gamma / (gamma s + 1)) they stay inside the f16 range, and the lo half of a column's
+// largest entries is a normal number whatever the scale of y (raw y: below ~1e-3 the lo halves went subnormal, past 65504 the features
+// overflowed).  A power of two, so the consumers (the Psi1^T y epilogue of the pass, pg_finish_m1_kernel) undo it exactly.
+__global__ __launch_bounds__(256) void pg_ky_kernel(int N, const double *__restrict__ y, int ldy, float *__restrict__ ky) {
+    __shared__ double red[4];
+    const int d = blockIdx.x, t = threadIdx.x;
+    double mx = 0.0;
+    for (int n = t; n < N; n += 256) mx = fmax(mx, fabs(y[(size_t)n * ldy + d]));    // (fmax drops NaN: the image kernel flags it)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    if ((t & 63) == 0) red[t >> 6] = mx;
+    __syncthreads();
+    if (t == 0) {
+        const double m0 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+        float k = 1.0f;
+        if (m0 > 0.0 && m0 <= 1.0e300) {
+            int ex;
+            (void)frexp(m0, &ex);
+            ex = max(-120, min(120, ex));
+            k = ldexpf(1.0f, 5 - ex);
+        }
+        ky[d] = k;
+    }
+}
+
 // ---- Psi1 term through the same passes --------------------------------------------------------------------------------------
 // psi1[n, m] = alpha exp2(c_n + sum_q a_nq z'_mq^2 + b_nq z'_mq) is the exponent product of the pair form on the DIAGONAL pairs
 // p = (m, m): s = 2 z'_m, s^2 / 64 = z'^2 / 16, with half the observation-side coefficients and den = g s + 1 (pg_obs_row).
@@ -409,11 +450,12 @@ __global__ __launch_bounds__(64) void pg_u1_kernel(int M, int Mp, int Mpad, cons
     }
 }
 // d/dz of the Psi1 term: block = inducing point m, threads over the output dims:
-//   dz[m][q] += 2 ln2 2^-12 sum_d u1_dm (2 S2 s_mq R[d][m][2q] + R[d][m][2q + 1]),  s = 2 z'
-// (R: pass "rows = observations, columns = inducing points" with the y-weighted features; the 2: d s / d z')
+//   dz[m][q] += 2 ln2 2^-12 sum_d u1_dm / (ky_d kg_dq) (2 S2 s_mq R[d][m][2q] + R[d][m][2q + 1]),  s = 2 z'
+// (R: pass "rows = observations, columns = inducing points" with the ky_d y-weighted features; the 2: d s / d z')
 template <int NF, int QP>
 __global__ __launch_bounds__(256) void pg_finish_m1_kernel(int M, int Mpad, int Q, int D, const double *__restrict__ z,
                                                            const unsigned char *__restrict__ consts, const float *__restrict__ u1,
+                                                           const float *__restrict__ ky, const double *__restrict__ gamma,
                                                            const float *__restrict__ r, double *__restrict__ dz) {
     __shared__ double red[4][2 * QP];
     const int m = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -421,7 +463,7 @@ __global__ __launch_bounds__(256) void pg_finish_m1_kernel(int M, int Mpad, int 
 #pragma unroll
     for (int q = 0; q < QP; ++q) { ta[q] = 0.0; tb[q] = 0.0; }
     for (int d = t; d < D; d += 256) {
-        const double ud = (double)u1[(size_t)d * Mpad + m];
+        const double ud = (double)u1[(size_t)d * Mpad + m] / (double)ky[d];       // (the features were ky_d y_nd: exact)
         const pg_f4 *row = reinterpret_cast<const pg_f4 *>(r + ((size_t)d * Mpad + m) * NF);   // (this pass writes [column][feature])
         float rv[NF];
 #pragma unroll
@@ -431,7 +473,11 @@ __global__ __launch_bounds__(256) void pg_finish_m1_kernel(int M, int Mpad, int 
         }
 #pragma unroll
         for (int q = 0; q < QP; ++q)
-            if (q < Q && 2 * q + 1 < NF) { ta[q] += ud * (double)rv[2 * q]; tb[q] += ud * (double)rv[2 * q + 1]; }
+            if (q < Q && 2 * q + 1 < NF) {
+                const double uk = ud / (double)pg_kg((float)gamma[(size_t)d * Q + q]);
+                ta[q] += uk * (double)rv[2 * q];
+                tb[q] += uk * (double)rv[2 * q + 1];
+            }
     }
 #pragma unroll
     for (int q = 0; q < QP; ++q) {
@@ -473,6 +519,7 @@ struct PgPsi2Out {                    // Psi2 as a by-product of pass 1 (see the
     double *vout;                     // [D][vM] or nullptr: alpha_d 2^-12 x the column sums of feature fsel (the Psi1 pass with rows =
     const double *valpha;             //   observations, y-weighted features: Psi1^T y of the forward pass, elbo_run's v)
     int vM;
+    const float *vky;                 // [D] the features' y weights ky_d (pg_ky_kernel), divided out of vout
 };
 struct PgSlot { int kind, i; };      // kind 0: exponent chain K-step i; 1: product i of the previous step's K-step-1 half; 2: of this step's K-step-0 half
 struct PgUnit { int kind, i; };      // kind 0: v_exp_f32 of element i; 1: v_cvt_pk_f16_f32 (hi) of element pair i; 2: the two v_fma_mix_f32 (e - hi) of pair i; 3: v_cvt_pk_f16_f32 (lo)
@@ -851,7 +898,7 @@ __global__ __launch_bounds__(64 * PgCfg<KS>::NW, PgCfg<KS>::WPS) void pg_pass_ke
                     po.part[(size_t)d * po.Mp * po.Mp + (size_t)(pm >> 16) * po.Mp + (pm & 0xffffu)] =
                         po.scale[(size_t)d * po.Ppad + p] * (cs * (1.0f / 4096.0f)) + poison;      // (x 2^-PG_WSHIFT)
             } else if (half == hs && p < po.vM) {
-                po.vout[(size_t)d * po.vM + p] = po.valpha[d] * (double)(cs * (1.0f / 4096.0f) + poison);
+                po.vout[(size_t)d * po.vM + p] = po.valpha[d] * ((double)(cs * (1.0f / 4096.0f) + poison) / (double)po.vky[d]);
             }
         }
         // feature-major inside a column tile (pg_oix): one store instruction = two 128-byte runs, and the finishing kernels (thread =
@@ -876,7 +923,7 @@ __global__ __launch_bounds__(64 * PgCfg<KS>::NW, PgCfg<KS>::WPS) void pg_pass_ke
 
 // ---- finishing, pair side -----------------------------------------------------------------------------------------------
 // thread = pair p, blockIdx.y = chunk of output dims, blockIdx.z = block of four latent dims: partial sums over the chunk's d of
-//   tp[c][0][q][p] = sum_d u_dp R2[2q],  tp[c][1][q][p] = sum_d u_dp R2[2q+1],  tp[c][2][q][p] = sum_d u_dp C_dp gamma_dq  (C = R2[2Q])
+//   tp[c][0][q][p] = sum_d u_dp R2[2q] / kg_dq,  tp[c][1][q][p] = sum_d u_dp R2[2q+1] / kg_dq,  tp[c][2][q][p] = sum_d u_dp C_dp gamma_dq  (C = R2[2Q])
 // (tp: [chunk][3][Q][P]).  Every load is a coalesced run (pg_oix); two output dims per trip so that their loads are in flight
 // together; four latent dims per thread keep it at a few dozen registers (a thread with all Q of them needed 200).
 template <int NF>
@@ -884,7 +931,7 @@ __global__ __launch_bounds__(256) void pg_finish_pairs_kernel(int M, int Q, int 
                                                               const double *__restrict__ gamma, const float *__restrict__ u,
                                                               const float *__restrict__ r2, double *__restrict__ tp) {
     constexpr int QB = 4, KD = 2;                             // (KD output dims per trip: their 10 KD loads in flight together; 4: slower, 122 registers)
-    __shared__ double gsh[32][QB];
+    __shared__ double gsh[32][QB], iksh[32][QB];
     const int t = threadIdx.x, p = blockIdx.x * 256 + t, c = blockIdx.y, q0 = QB * blockIdx.z;
     const int P = (int)((long long)M * (M + 1) / 2);
     const bool ok = p < P;
@@ -899,6 +946,7 @@ __global__ __launch_bounds__(256) void pg_finish_pairs_kernel(int M, int Q, int 
         if (t < nd * QB) {
             const int dd = t / QB, q = t - dd * QB;
             gsh[dd][q] = q0 + q < Q ? gamma[(size_t)(d0 + dd) * Q + q0 + q] : 0.0;
+            iksh[dd][q] = 1.0 / (double)pg_kg((float)gsh[dd][q]);          // (the features' weight kg, pg_kg: exact)
         }
         __syncthreads();
         for (int dd = 0; dd < nd; dd += KD) {
@@ -923,8 +971,8 @@ __global__ __launch_bounds__(256) void pg_finish_pairs_kernel(int M, int Q, int 
                 const int dl = dd + k < nd ? dd + k : dd;
 #pragma unroll
                 for (int q = 0; q < QB; ++q) {
-                    a1[q] += udd * (double)ra[k][q];
-                    a2[q] += udd * (double)rb[k][q];
+                    a1[q] += udd * iksh[dl][q] * (double)ra[k][q];
+                    a2[q] += udd * iksh[dl][q] * (double)rb[k][q];
                     a3[q] += uc * gsh[dl][q];
                 }
             }
@@ -1182,7 +1230,7 @@ template <int KS> static int pg_ring_tiles() {                   // row tiles pe
 struct PgLayout {
     int KS, NF, P, Ppad, NT, PT, nblk_obs, MT;
     size_t off_u, off_kap, off_flag, off_cobs, off_xobs, off_xpair, off_r2, off_r1, off_tp, off_tt, off_dmup, off_dsp, off_dgp,
-        off_cobs1, off_xobs1, off_dimg, off_xm1, off_r1p, off_r2p, off_u1, off_kap1, total;   // (..1 / ..p: the Psi1 term)
+        off_cobs1, off_xobs1, off_dimg, off_xm1, off_r1p, off_r2p, off_u1, off_kap1, off_ky, total;   // (..1 / ..p: the Psi1 term)
 };
 static PgLayout pg_layout(int D, int N, int M, int Q) {
     PgLayout L;
@@ -1214,6 +1262,7 @@ static PgLayout pg_layout(int D, int N, int M, int Q) {
     L.off_r2p = o;   o += dpgp_align256(sizeof(float) * (size_t)D * L.MT * 32 * L.NF);
     L.off_u1 = o;    o += dpgp_align256(sizeof(float) * (size_t)D * L.MT * 32);
     L.off_kap1 = o;  o += dpgp_align256(sizeof(float) * (size_t)D);
+    L.off_ky = o;    o += dpgp_align256(sizeof(float) * (size_t)D);
     L.total = o;
     return L;
 }
@@ -1294,22 +1343,24 @@ static int launch_psi1_front(int D, int N, int M, int Q, const unsigned char *co
     const _Float16 *pimg = reinterpret_cast<const _Float16 *>(consts + C.off_pairs);
     _Float16 *cobs1 = reinterpret_cast<_Float16 *>(ws + L.off_cobs1), *xobs1 = reinterpret_cast<_Float16 *>(ws + L.off_xobs1),
              *dimg = reinterpret_cast<_Float16 *>(ws + L.off_dimg);
-    float *r2p = reinterpret_cast<float *>(ws + L.off_r2p);
+    float *r2p = reinterpret_cast<float *>(ws + L.off_r2p), *ky = reinterpret_cast<float *>(ws + L.off_ky);
     const int Mpad = 32 * L.MT;
+    DPGP_PRELAUNCH(); hipLaunchKernelGGL(pg_ky_kernel, dim3(D), dim3(256), 0, st, N, y, ldy, ky);
+    DPGP_LAUNCH_CHECK();
     {
         const size_t lds = 256 + sizeof(_Float16) * 8 * 512 * pg_xp(NFB);
         auto kern = pg_obs_images_kernel<KS>;
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return DPGP_ERR_LAUNCH;
         DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, dim3(dpgp_ceil_div(N, 256), D), dim3(256), lds, st, N, Q, consts, mu, s, gamma, cobs1, xobs1,
-                           L.NT, flag, y, ldy);
+                           L.NT, flag, y, ldy, (const float *)ky);
         DPGP_LAUNCH_CHECK();
     }
     DPGP_PRELAUNCH(); hipLaunchKernelGGL((pg_diag_image_kernel<KS>), dim3(dpgp_ceil_div(Mpad * KS * 2, 256)), dim3(256), 0, st, M, Mpad, pimg, dimg);
     DPGP_LAUNCH_CHECK();
     // rows: the observations of output dim d (cobs1, y-weighted features xobs1); columns: the inducing points -> R2' [d][m][.]
     // (the pass that also yields Psi1^T y keeps the lo half of the exponentials whatever the mode, as the one that yields Psi2)
-    PgPsi2Out po = {nullptr, nullptr, nullptr, flag, 0, 0, 2 * Q, 1, psi1v, alpha, M};
+    PgPsi2Out po = {nullptr, nullptr, nullptr, flag, 0, 0, 2 * Q, 1, psi1v, alpha, M, ky};
     if (wlo || psi1v) return pg_launch_pass<KS, true>(D, cobs1, 1, xobs1, dimg, 0, r2p, L.NT, L.MT, po, st);
     return pg_launch_pass<KS, false>(D, cobs1, 1, xobs1, dimg, 0, r2p, L.NT, L.MT, po, st);
 }
@@ -1332,10 +1383,10 @@ static int launch_pgrad_part1(int D, int N, int M, int Q, const unsigned char *c
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return DPGP_ERR_LAUNCH;
         DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, dim3(dpgp_ceil_div(N, 256), D), dim3(256), lds, st, N, Q, consts, mu, s, gamma, cobs, xobs, L.NT,
-                           flag, (const double *)nullptr, 0);
+                           flag, (const double *)nullptr, 0, (const float *)nullptr);
         DPGP_LAUNCH_CHECK();
     }
-    PgPsi2Out po = {psi2_part, scale, reinterpret_cast<const unsigned *>(consts + C.off_pmap), flag, dpgp_round_up(M, 16), L.Ppad, 2 * Q, 0, nullptr, nullptr, 0};
+    PgPsi2Out po = {psi2_part, scale, reinterpret_cast<const unsigned *>(consts + C.off_pmap), flag, dpgp_round_up(M, 16), L.Ppad, 2 * Q, 0, nullptr, nullptr, 0, nullptr};
     // rows: the observations of output dim d (cobs, xobs); columns: the pairs (the forward's pair image)
     // (the pass that also yields Psi2 keeps the lo half of the exponentials whatever the mode: the objective is not a "fast" quantity)
     if (wlo || psi2_part) return pg_launch_pass<KS, true>(D, cobs, 1, xobs, pimg, 0, r2, L.NT, L.PT, po, st);
@@ -1376,7 +1427,7 @@ static int launch_pgrad_part2(int D, int N, int M, int Q, const unsigned char *c
     DPGP_LAUNCH_CHECK();
     int rc;
     {
-        PgPsi2Out po = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, 0};
+        PgPsi2Out po = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, 0, nullptr};
         // rows: the pairs (pair image, xpair of output dim d); columns: the observations of output dim d
         rc = wlo ? pg_launch_pass<KS, true>(D, pimg, 0, xpair, cobs, 1, r1, L.PT, L.NT, po, st)
                  : pg_launch_pass<KS, false>(D, pimg, 0, xpair, cobs, 1, r1, L.PT, L.NT, po, st);
@@ -1415,14 +1466,14 @@ static int launch_pgrad_part2(int D, int N, int M, int Q, const unsigned char *c
         DPGP_PRELAUNCH(); hipLaunchKernelGGL((pg_pair_images_kernel<KS>), dim3(dpgp_ceil_div(Mpad, 256), D), dim3(256), 0, st, Mpad, Q,
                            (const _Float16 *)dimg, (const float *)u1, (const float *)kap1, xm1);
         DPGP_LAUNCH_CHECK();
-        PgPsi2Out po = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, 0};
+        PgPsi2Out po = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, 0, nullptr};
         // rows: the inducing points (dimg, features xm1 of output dim d); columns: the observations of output dim d -> R1' [d][n][.]
         rc = wlo ? pg_launch_pass<KS, true>(D, dimg, 0, xm1, cobs1, 1, r1p, L.MT, L.NT, po, st)
                  : pg_launch_pass<KS, false>(D, dimg, 0, xm1, cobs1, 1, r1p, L.MT, L.NT, po, st);
         if (rc != DPGP_OK) return rc;
         DPGP_PRELAUNCH();
         PG_QP_SWITCH(Q, hipLaunchKernelGGL((pg_finish_m1_kernel<NF, QP_>), dim3(M), dim3(256), 0, st, M, Mpad, Q, D, z, consts, (const float *)u1,
-                                           (const float *)r2p, dz));
+                                           (const float *)(ws + L.off_ky), gamma, (const float *)r2p, dz));
         DPGP_LAUNCH_CHECK();
     }
     const int dco = dpgp_ceil_div(D, PG_DC_OBS), nco = dpgp_ceil_div(D, dco);

@@ -69,7 +69,18 @@ extern "C" {
  *   says "this atom's K_uu / B is ill-conditioned for an fp32 Psi2", not a bound on a particular output dim's terms.
  * Operands outside the f16 range of the default fp32 psi kernels (|z - mean z| or |mu - mean z| beyond ~90 length scales)
  * are detected in the kernels: the affected Psi2 patch / Psi1^T y slab comes out as NaN, which the fused ELBO reports as a
- * failed factorisation (info > 0, NaN terms).  DPGP_ALGO_MFMA_F32 and fp64 have no such limit.                              */
+ * failed factorisation (info > 0, NaN terms).  DPGP_ALGO_MFMA_F32 and fp64 have no such limit.
+ * y in the pair-tile stage B and the training step (dpgp_elbo_step, dpgp_elbo_grad_psi[_ex] in mixed precision): the f16 features
+ * of the Psi1 pass are y_nd times a power of two per output dim that brings max_n |y_nd| into [16, 32), undone exactly where the
+ * pass's results are read — so any finite y whose every nonzero column has max_n |y_nd| in [2^-120, 2^120] is accepted with the
+ * accuracy of unit-scale data (tests/test_gpu_scales.py sweeps 2^-20 ... 2^20 and columns of their own scale from 1e-4 to 1e5).
+ * A non-finite y, or a column beyond 2^120, is refused as a range-guard hit: NaN gradients (and, in dpgp_elbo_step, NaN terms).
+ * The observation features a'_q, b_q of the same passes are proportional to w = gamma_dq / (gamma_dq s_nq + 1); they carry a power
+ * of two per (d, q) that lifts a gamma below 1/2 into [1/2, 1), so ARD-switched-off latent dims (gamma down to 1e-6 and below) keep
+ * their d/dz to the mixed tolerance.  w above ~150 (gamma and 1/s both that large) overflows the features' f16 range: refused
+ * in the same way (NaN plus the range flag), never a finite wrong number.
+ * A large |y| still makes a mixed forward pass flag the output dim as DPGP_INFO_ILL_CONDITIONED: the conditioning-guard bound grows
+ * with y^2 against an absolute threshold.                                                              */
 #define DPGP_INFO_ILL_CONDITIONED (-2)
 #define DPGP_GUARD_REL 2.0e-3
 

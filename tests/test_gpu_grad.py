@@ -465,7 +465,9 @@ def test_training_step_equals_the_three_calls(dev, shape):
     mixed-precision gradient tolerance (5e-4 of the largest entry) of the all-fp64 gradients."""
     n, d, m, q = shape
     args = _stage_b_problem(dev, shape)
-    args[1] = args[1] * 0.6                                      # (inducing inputs inside the cloud of latent means: well-conditioned K_uu)
+    # inducing inputs inside the cloud of latent means (well-conditioned K_uu); where more than 16 of them per latent dim crowd few latent
+    # dims (M = 70 in Q = 4) they are spread further, so that the conditioning guard flags no output dim and every gradient is compared
+    args[1] = args[1] * (1.5 if m > 16 * q else 0.6)
     w3 = ops.ElboWorkspace(d, n, m, q, 'mixed', dev)
     terms3, sums3, info3 = [a.clone() for a in ops.elbo_fhat(*args, prec='mixed', workspace=w3)]
     gp, wk, gv, dab3, infog3 = ops.elbo_grad_chain(args[5], args[6], w3)
@@ -475,26 +477,23 @@ def test_training_step_equals_the_three_calls(dev, shape):
     assert ops.elbo_step_supported(m, q)
     for rep in range(2):                                         # (twice: the buffers are reused by every step)
         (terms1, sums1, info1), (dmu, ds, dz, dg, dab1, infog1) = ops.elbo_step(*args, workspace=w1, buffers=b1)
-    # output dims that the conditioning guard flags (info = -2: the fp32 rounding of Psi2 is amplified beyond the mixed tolerance by a
-    # nearly singular K_uu — random inducing inputs in few latent dims) are exempt in both paths, as in the forward tests
+    # no output dim may be flagged (info = -2: the fp32 rounding of Psi2 amplified beyond the mixed tolerance by a nearly singular K_uu):
+    # the inputs above are chosen so that every comparison below runs for every shape
     ok = ((info1 == 0) & (info3 == 0)).cpu().numpy()
-    assert int(info1.clamp(min=0).max()) == 0 and int(info3.clamp(min=0).max()) == 0
-    assert torch.equal(info1, info3), 'the two paths flag different output dims'
+    assert ok.all(), 'flagged or failed output dims: step %s, three calls %s' % (info1.tolist(), info3.tolist())
     t3 = terms3.cpu().numpy()
     assert np.isfinite(terms1.cpu().numpy()).all()
-    if ok.any():
-        np.testing.assert_allclose(terms1.cpu().numpy()[ok], t3[ok], rtol=0, atol=2e-5 * np.abs(t3[ok]).max())
-    if ok.all():
-        np.testing.assert_allclose(sums1.cpu().numpy(), sums3.cpu().numpy(), rtol=2e-6)
-        assert int(infog1.abs().max()) == 0 and int(infog3.abs().max()) == 0
-        w64 = ops.ElboWorkspace(d, n, m, q, 'f64', dev)
-        ops.elbo_fhat(*args, prec='f64', workspace=w64)
-        gp, wk, gv, dab64, _ = ops.elbo_grad_chain(args[5], args[6], w64)
-        g64 = [a.cpu().numpy() for a in ops.elbo_grad_psi(args[0], args[1], args[2], args[3], args[4], args[5], gp, wk, gv, prec='f64')]
-        for path, dab, grads in (('step', dab1, [a.cpu().numpy() for a in (dmu, ds, dz, dg)]), ('three calls', dab3, g3)):
-            np.testing.assert_allclose(dab.cpu().numpy(), dab64.cpu().numpy(), rtol=0, atol=5e-4 * float(dab64.abs().max()), err_msg=path)
-            for name, got, want in zip(('d mu', 'd S', 'd z', 'd gamma'), grads, g64):
-                np.testing.assert_allclose(got, want, rtol=0, atol=5e-4 * np.abs(want).max(), err_msg='%s, %s' % (name, path))
+    np.testing.assert_allclose(terms1.cpu().numpy(), t3, rtol=0, atol=2e-5 * np.abs(t3).max())
+    np.testing.assert_allclose(sums1.cpu().numpy(), sums3.cpu().numpy(), rtol=2e-6)
+    assert int(infog1.abs().max()) == 0 and int(infog3.abs().max()) == 0
+    w64 = ops.ElboWorkspace(d, n, m, q, 'f64', dev)
+    ops.elbo_fhat(*args, prec='f64', workspace=w64)
+    gp, wk, gv, dab64, _ = ops.elbo_grad_chain(args[5], args[6], w64)
+    g64 = [a.cpu().numpy() for a in ops.elbo_grad_psi(args[0], args[1], args[2], args[3], args[4], args[5], gp, wk, gv, prec='f64')]
+    for path, dab, grads in (('step', dab1, [a.cpu().numpy() for a in (dmu, ds, dz, dg)]), ('three calls', dab3, g3)):
+        np.testing.assert_allclose(dab.cpu().numpy(), dab64.cpu().numpy(), rtol=0, atol=5e-4 * float(dab64.abs().max()), err_msg=path)
+        for name, got, want in zip(('d mu', 'd S', 'd z', 'd gamma'), grads, g64):
+            np.testing.assert_allclose(got, want, rtol=0, atol=5e-4 * np.abs(want).max(), err_msg='%s, %s' % (name, path))
 
 
 def test_model_gradients_fused_step_equals_separate_calls(dev, monkeypatch):
