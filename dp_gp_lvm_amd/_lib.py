@@ -65,6 +65,8 @@ SIGNATURES = {
     'dpgp_elbo_grad_chain_big': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _i, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dpgp_trouble_flag': (_i, [_sz, _vp, _i, _vp, _vp, _vp]),
     'dpgp_trtri_lower_batched_f64': (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'dpgp_ard_rbf_gram_grad_workspace_bytes': (_sz, [_i, _i]),
+    'dpgp_ard_rbf_gram_grad_f64': (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dpgp_gemm_strided_f64': (_i, [_i, _i, _i, _i, _d, _vp, _ll, _ll, _ll, _vp, _ll, _ll, _ll, _d, _vp, _ll, _ll, _ll, _vp]),
 }
 for _t in ('f32', 'f64'):

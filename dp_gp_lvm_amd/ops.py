@@ -69,6 +69,37 @@ def ard_rbf_gram(x0, x1, gamma, alpha, beta, include_noise=False, include_jitter
     return out
 
 
+def ard_rbf_gram_grad(x, gamma, alpha, w):
+    """The gram-gradient contraction of dpgp_ard_rbf_gram_grad_f64 (fp64): with G = w * (noise-free ARD-RBF gram of x),
+    returns r = G.sum(1) [N], sx[i,q] = sum_j G_ij (x_iq - x_jq) [N,Q] and sq[i,q] = sum_j G_ij (x_iq - x_jq)^2 [N,Q].
+    x [N,Q], gamma [1,Q] or [Q], alpha one element, w [N,N] (any; a row-sliced view with unit column stride is used in place)."""
+    f64 = torch.float64
+    x = _prep(x, f64, 'x')
+    assert x.dim() == 2, 'x must be [N x Q]'
+    n, q = x.shape
+    gamma = _prep(gamma, f64, 'gamma').reshape(-1)
+    alpha = _prep(alpha, f64, 'alpha').reshape(-1)
+    assert gamma.numel() == q and alpha.numel() == 1, 'gamma must be [1 x Q], alpha [1 x 1]'
+    if not isinstance(w, torch.Tensor) or not w.is_cuda:
+        raise RuntimeError('w must live on the GPU: dp_gp_lvm_amd runs its operators in HIP only')
+    assert w.dim() == 2 and tuple(w.shape) == (n, n), 'w must be [N x N]'
+    w = w.to(f64)
+    if w.stride(1) != 1 or w.stride(0) < max(1, n):
+        w = w.contiguous()
+    r = torch.empty(n, dtype=f64, device=x.device)
+    sx = torch.empty((n, q), dtype=f64, device=x.device)
+    sq = torch.empty((n, q), dtype=f64, device=x.device)
+    if n == 0:
+        return r, sx, sq
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_gram_grad_workspace_bytes(n, q)
+    ws = _ws(wsb, x.device)
+    _lib.check(l.dpgp_ard_rbf_gram_grad_f64(n, q, x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(), w.data_ptr(), w.stride(0),
+                                            r.data_ptr(), sx.data_ptr(), sq.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_ard_rbf_gram_grad_f64')
+    return r, sx, sq
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

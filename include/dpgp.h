@@ -95,6 +95,18 @@ int dpgp_ard_rbf_gram_f32(int B, int N0, int N1, int Q, const float *x0, const f
 int dpgp_ard_rbf_gram_f64(int B, int N0, int N1, int Q, const double *x0, const double *x1, const double *gamma,
                           const double *alpha, const double *beta, int flags, double jitter, double *out, void *stream);
 
+/* ---- gradient contraction of the ARD-RBF gram (gp_regression / gp_lvm backward pass, gaussian_process.py:22-129):
+ *      G_ij = w_ij alpha exp(-1/2 sum_q gamma_q (x_iq - x_jq)^2)  (the noise-free gram; the diagonal counts, with exp = 1)
+ *      r[i] = sum_j G_ij,  sx[i][q] = sum_j G_ij (x_iq - x_jq),  sq[i][q] = sum_j G_ij (x_iq - x_jq)^2
+ *      x[N][Q], gamma[Q], alpha[1], w[N][ldw] (ldw >= N; any w, symmetry is not assumed), r[N], sx[N][Q], sq[N][Q].
+ *      1 <= Q <= DPGP_GRAM_GRAD_MAX_Q (the LDS bound of the row / column strips).  N == 0 does nothing.  Partial sums go to
+ *      ws and are added in a fixed order: no atomics, the same bits on every run.  dL/dK = w then gives
+ *      dL/dalpha = sum r / alpha, dL/dgamma_q = -1/2 sum_i sq[i][q], dL/dx_iq = -2 gamma_q sx[i][q] (w symmetric). */
+#define DPGP_GRAM_GRAD_MAX_Q 64
+size_t dpgp_ard_rbf_gram_grad_workspace_bytes(int N, int Q);
+int dpgp_ard_rbf_gram_grad_f64(int N, int Q, const double *x, const double *gamma, const double *alpha, const double *w, int ldw,
+                               double *r, double *sx, double *sq, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);
