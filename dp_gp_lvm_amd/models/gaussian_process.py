@@ -187,6 +187,140 @@ def _gaussian_process(x_raw, y, raw, x_name, device):
     return GaussianProcess()
 
 
+class _TestBound:
+    """The q(X*) part of the prediction bounds of bayesian_gp_lvm / manifold_relevance_determination (gaussian_process.py:365-394,
+    :776-831, :880-919): B frozen ARD-RBF kernels (inducing inputs z [B,M,Q], gamma [B,Q], alpha [B], beta [B]) sharing q(X*), each
+    with its own test outputs y_b [N*, D_b].  Everything runs in fp64 on the device, whatever precision the model trains in.
+
+    Once per object (the trained model is frozen): K_uu_b, its Cholesky factor L_b, L_b^-1, K_uu_b^-1 (ard_rbf_gram / potrf_batched /
+    tril_inverse_batched / matmul) and the q(X*)-independent pair factor of Psi2 (ops.qx_pair_factor).
+    Per evaluation: Psi1*, Psi2* of the B kernels (one qx_psi_stats_batched), then on [B, M, M] arrays
+        T = L^-1 Psi2* L^-T,  A = beta T + I = L_A L_A^T,  R0 = L_A^-1 L^-1,  U = R0 Psi1*^T Y,
+        f_hat*_b = 1/2 N* D_b (log beta - log 2 pi) - D_b log|L_A| + 1/2 D_b beta (tr T - alpha N*) + 1/2 beta^2 |U|^2 - 1/2 beta |Y|^2
+    and, for the gradient, the adjoints  (P = R0^T R0 = (K_uu + beta Psi2*)^-1,  R = R0^T U)
+        G2 = 1/2 D_b beta (K_uu^-1 - P) - 1/2 beta^3 R R^T,    G1 = beta^2 Y R^T
+    contracted with dPsi/d(mu, s) by one qx_psi_adjoint.  No host synchronisation."""
+
+    def __init__(self, z, gamma, alpha, beta, ys, device):
+        f64 = TORCH_DTYPE
+        self.z = torch.stack([_as_device(v, device) for v in z]).contiguous()                       # [B, M, Q]
+        self.gamma = torch.stack([_as_device(v, device).reshape(-1) for v in gamma]).contiguous()   # [B, Q]
+        self.alpha = torch.cat([_as_device(v, device).reshape(-1) for v in alpha]).contiguous()     # [B]
+        self.beta = torch.cat([_as_device(v, device).reshape(-1) for v in beta]).contiguous()       # [B]
+        b, m = self.z.shape[0], self.z.shape[1]
+        self.m, self.device = m, device
+        self.dims = torch.tensor([y.shape[1] for y in ys], dtype=f64, device=device)
+        n_t, dmax = ys[0].shape[0], max(y.shape[1] for y in ys)
+        self.n_t = n_t
+        self.y = torch.zeros((b, n_t, dmax), dtype=f64, device=device)                          # zero-padded columns
+        for i, y in enumerate(ys):
+            self.y[i, :, :y.shape[1]] = y
+        self.yy = torch.sum(self.y * self.y, dim=(1, 2))
+        one = torch.ones(1, 1, dtype=f64, device=device)
+        k_uu = torch.stack([ops.ard_rbf_gram(self.z[i], None, self.gamma[i:i + 1], self.alpha[i].reshape(1, 1), one,
+                                             include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)[0]
+                            for i in range(b)])
+        self.l_uu, self.info_uu = ops.potrf_batched(k_uu)
+        self.li = ops.tril_inverse_batched(self.l_uu)
+        self.kinv = ops.matmul(self.li.transpose(1, 2), self.li)
+        self.zfac = ops.qx_pair_factor(self.z, self.gamma, self.alpha)
+        self.eye = torch.eye(m, dtype=f64, device=device)
+        self.terms = None
+
+    def psi(self, mu, s):
+        return ops.qx_psi_stats_batched(self.z, mu, s, self.gamma, self.alpha, self.zfac)
+
+    def evaluate(self, mu, s, grad=False):
+        """f_hat* summed over the B kernels (0-d tensor); with grad, also d f_hat* / d(mu, s).  self.terms: [B x 5] per-kernel
+        terms (the five summands above), self.info: failed factorisations of A (0 = fine)."""
+        be, n_t, dd = self.beta, self.n_t, self.dims
+        psi_1, psi_2 = self.psi(mu, s)
+        tm = ops.matmul(ops.matmul(self.li, psi_2), self.li.transpose(1, 2))
+        l_a, self.info = ops.potrf_batched(be[:, None, None] * tm + self.eye)
+        r0 = ops.matmul(ops.tril_inverse_batched(l_a), self.li)
+        u = ops.matmul(r0, ops.matmul(psi_1.transpose(1, 2), self.y))                       # [B, M, Dmax]
+        logdet = torch.sum(torch.log(torch.diagonal(l_a, dim1=-2, dim2=-1)), dim=-1)
+        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
+        self.terms = torch.stack([0.5 * n_t * dd * (torch.log(be) - math.log(2.0 * math.pi)), -dd * logdet,
+                                  0.5 * dd * be * (tr - self.alpha * n_t), 0.5 * be * be * torch.sum(u * u, dim=(1, 2)),
+                                  -0.5 * be * self.yy], dim=1)
+        f = torch.sum(self.terms)
+        if not grad:
+            return f, psi_1, psi_2
+        r = ops.matmul(r0.transpose(1, 2), u)                                                  # [B, M, Dmax]
+        p = ops.matmul(r0.transpose(1, 2), r0)
+        g2 = (0.5 * dd * be)[:, None, None] * (self.kinv - p) - (0.5 * be ** 3)[:, None, None] * ops.matmul(r, r.transpose(1, 2))
+        g1 = (be * be)[:, None, None] * ops.matmul(self.y, r.transpose(1, 2))                # [B, N*, M]
+        d_mu, d_s = ops.qx_psi_adjoint(self.z, mu, s, self.gamma, self.alpha, g1, g2, self.zfac)
+        return f, d_mu, d_s
+
+
+def _kl_test(mu, s):
+    """KL(q(X*) || N(0, I)) (gp_expressions.py:10-24) and its gradient with respect to (mu, s)."""
+    return ops.kl_qx(mu, s), mu, 0.5 * (1.0 - 1.0 / s)
+
+
+def _init_test_latents(y_ref, y_test, x_train_mean, num_latent_dims, use_pca, x_test_mean, x_test_var, device):
+    """q(X*) as gaussian_process.py:346-360: mean from the PCA of y_test, or from the nearest training neighbour (L2 over the given
+    columns, utils/expressions.py:28-44) plus N(0, 0.01^2) noise; variances 1 — unless values are handed in."""
+    n_t = y_test.shape[0]
+    if x_test_mean is not None:
+        init = np.asarray(x_test_mean.detach().cpu() if torch.is_tensor(x_test_mean) else x_test_mean, dtype=np.float64)
+    elif use_pca:
+        init = pca(y_test, num_latent_dimensions=num_latent_dims)
+    else:
+        d2 = ((y_ref[:, None, :] - y_test[None, :, :]) ** 2).sum(-1)
+        init = x_train_mean.detach().cpu().numpy()[np.argmin(d2, axis=0)] + \
+            np.random.normal(scale=0.01, size=(n_t, num_latent_dims))
+    if x_test_var is not None:
+        var = np.asarray(x_test_var.detach().cpu() if torch.is_tensor(x_test_var) else x_test_var, dtype=np.float64)
+    else:
+        var = np.ones((n_t, num_latent_dims))
+    return _as_device(init, device, (n_t, num_latent_dims)), _as_device(var, device, (n_t, num_latent_dims))
+
+
+def _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate):
+    """Adam on q(X*) (mean, softplus-parametrised variances) ascending the bound whose gradient grad_fn(mu, s) returns; no host
+    reads inside the loop."""
+    xt = xt.clone()
+    raw = torch.log(torch.expm1(st_))
+    opt = torch.optim.Adam([xt, raw], lr=learning_rate)
+    for _ in range(num_iterations):
+        g_mu, g_s = grad_fn(xt, F.softplus(raw))
+        xt.grad, raw.grad = -g_mu, -g_s * torch.sigmoid(raw)
+        opt.step()
+    return xt.detach(), F.softplus(raw).detach()
+
+
+def _predictive_moments(bound_u, c_index, x_mean, s_train, y_train_u, xt, st_):
+    """Predictive means [N* x D_b] and covariances [D_b x N* x N*] of the kernels of bound_u (the unobserved views / dims) at
+    q(X*) (gaussian_process.py:495-536, :920-988), from the training q(X) = (x_mean, s_train) and training outputs y_train_u
+    [N x D_b] of each kernel.  Training Psi statistics and factors are formed once per call, in fp64.  c_index[b]: the kernel
+    whose training C = L_A^-1 L^-1 Psi1^T enters kernel b's mean (b itself; the reference's MRD uses the last training view's C
+    for every view, gaussian_process.py:938)."""
+    psi_1, psi_2 = bound_u.psi(x_mean, s_train)
+    tm = ops.matmul(ops.matmul(bound_u.li, psi_2), bound_u.li.transpose(1, 2))
+    l_a, _ = ops.potrf_batched(bound_u.beta[:, None, None] * tm + bound_u.eye)
+    psi_1t, psi_2t = bound_u.psi(xt, st_)
+    n_t = xt.shape[0]
+    r0 = ops.matmul(ops.tril_inverse_batched(l_a), bound_u.li)                                 # L_A^-1 L^-1 (training)
+    c_tr = ops.matmul(r0, psi_1.transpose(1, 2))                                             # [B, M, N]
+    c_pred = ops.matmul(r0, psi_1t.transpose(1, 2))                                          # [B, M, N*]
+    means, covars = [], []
+    p = ops.matmul(r0.transpose(1, 2), r0)                                                   # (K_uu + beta Psi2)^-1
+    gmat = psi_2t - ops.matmul(psi_1t.transpose(1, 2), psi_1t)
+    tr = torch.diagonal(ops.matmul(bound_u.kinv - p, psi_2t), dim1=-2, dim2=-1).sum(-1)
+    for b, y_u in enumerate(y_train_u):
+        be, al = bound_u.beta[b], bound_u.alpha[b]
+        cy = ops.matmul(c_tr[c_index[b]], y_u)                                               # [M, D_b]
+        means.append(be * ops.matmul(c_pred[b].transpose(0, 1), cy))
+        scale = ops.matmul(p[b], ops.matmul(psi_1[b].transpose(0, 1), y_u))                 # [M, D_b]
+        var = be * be * torch.sum(scale * ops.matmul(gmat[b], scale), dim=0)                 # diag(scale^T g scale)
+        eye = torch.eye(n_t, dtype=TORCH_DTYPE, device=xt.device)
+        covars.append(var[:, None, None] + (al * n_t + 1.0 / be - tr[b]) * eye)
+    return means, covars
+
+
 def _hyper_raw(q, kernel, iv, device):
     if kernel is not None:
         hp = kernel.hyperparameters
@@ -290,9 +424,129 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             if callback is not None:
                 callback(it)
 
+    y_np = np.asarray(y_train, dtype=np.float64)
+    dev_ = inner.raw['x_mean'].device
+    pred_state = {}
+
+    def _frozen():
+        """The trained kernel as a B = 1 test bound's parameters (fp64 values of the raw variables)."""
+        with torch.no_grad():
+            return ([raw['x_u'].detach()], [F.softplus(raw['gamma_atoms']).detach()], [F.softplus(raw['alpha_atoms']).detach()],
+                    [F.softplus(raw['beta_atoms']).detach()])
+
+    def _test_bound(y_test):
+        z, g, a, b = _frozen()
+        bound = _TestBound(z, g, a, b, [_as_device(y_test, dev_)], dev_)
+        pred_state['bound'] = bound
+        return bound
+
+    def _check_observed(y_test, full):
+        y_test = np.asarray(y_test, dtype=np.float64)
+        assert y_test.ndim == 2 and y_test.shape[0] >= 1, 'y_test must be [N* x D]'
+        if full:
+            assert y_test.shape[1] == num_dimensions, \
+                'Observed dimensionality for prediction must be equal to the dimensionality of the training data.'
+        else:
+            assert y_test.shape[1] < num_dimensions, \
+                'Observed dimensionality for missing data scenario must be less than the total ' \
+                'dimensionality of the training data.'
+        return y_test
+
+    def _train_terms():
+        t_ = inner.objective_terms                          # (objective_t, f_hat, KL, DP objective, hyper-prior)
+        return t_[1], t_[2]
+
+    def _bound_at(y_test, xt, st_):
+        bound = _test_bound(y_test)
+        with torch.no_grad():
+            f_test, _, _ = bound.evaluate(xt, st_)
+            f_hat, kl = _train_terms()
+            kl_t = ops.kl_qx(xt, st_)
+        return f_hat, kl, f_test, kl_t
+
+    def _test_latent_gradients(y_test, x_test_mean, x_test_var):
+        y_test = np.asarray(y_test, dtype=np.float64)
+        assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
+        bound = _test_bound(y_test)
+        xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
+        with torch.no_grad():
+            _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
+            _, k_mu, k_s = _kl_test(xt, st_)
+        return d_mu - k_mu, d_s - k_s
+
+    def _optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None, x_test_var=None):
+        y_test = np.asarray(y_test, dtype=np.float64)
+        assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
+        xt, st_ = _init_test_latents(y_np[:, :y_test.shape[1]], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean,
+                                     x_test_var, dev_)
+        bound = _test_bound(y_test)
+
+        def grad_fn(mu, s):
+            _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
+            return d_mu - mu, d_s - 0.5 * (1.0 - 1.0 / s)
+        with torch.no_grad():
+            return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
+
     class BayesianGPLVM(Trainable):
-        """Accessors as in the reference (gaussian_process.py:276-340)."""
+        """Accessors as in the reference (gaussian_process.py:276-340), and its two prediction methods (:329-538) with the same
+        keywords and return tuples as dp_gp_lvm's, plus test_latent_gradients / optimise_test_latents / prediction_terms.
+        Prediction runs in fp64 (the reference's dtype) whatever `precision` the model trains in; the training-side f_hat and
+        KL(q(X)) of the bounds are those of the model's own evaluation (mixed Psi statistics when precision='mixed')."""
         raw_variables = raw
+
+        @staticmethod
+        def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+            """q(X*) for fully observed test data y_test [N* x D] (gaussian_process.py:329-402).  Returns
+                (prediction_lower_bound = f_hat + f_hat* - KL(q(X)) - KL(q(X*)), x_test_mean [N* x Q], x_test_covar [N* x Q x Q],
+                 test_log_likelihood = f_hat* - f_hat)
+            — the test log-likelihood exactly as the reference defines it (:400, "equation 36"): the training f_hat is
+            subtracted and KL(q(X*)) is not.  q(X*) starts at the nearest training neighbour + N(0, 0.01^2) noise, or the PCA of
+            y_test (use_pca), or the given x_test_mean / x_test_var (values; variances 1 by default).  reference_compat: accepted
+            for symmetry with dp_gp_lvm; the reference's B = 1 bound has no defect to reproduce, so both settings agree."""
+            y_test = _check_observed(y_test, True)
+            xt, st_ = _init_test_latents(y_np, y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
+            f_hat, kl, f_test, kl_t = _bound_at(y_test, xt, st_)
+            return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), f_test - f_hat
+
+        @staticmethod
+        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+            """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
+                (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
+            for the remaining Du = D - Do dims, at the initial q(X*) of predict_new_latent_variables (nearest neighbour over
+            the observed dims).  The predictive moments are the reference's (:495-536), composed of the library's operators;
+            reference_compat: as predict_new_latent_variables (no effect)."""
+            y_test = _check_observed(y_test, False)
+            do = y_test.shape[1]
+            xt, st_ = _init_test_latents(y_np[:, :do], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var,
+                                         dev_)
+            f_hat, kl, f_test, kl_t = _bound_at(y_test, xt, st_)
+            bound = pred_state['bound']
+            with torch.no_grad():
+                means, covars = _predictive_moments(bound, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
+                                                    [_as_device(y_np[:, do:], dev_)], xt, st_)
+            return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covars[0]
+
+        @staticmethod
+        def test_latent_gradients(y_test, x_test_mean, x_test_var):
+            """d(f_hat* - KL(q(X*))) / d(x_test_mean, x_test_var) [N* x Q] each — the gradient of either prediction bound with
+            respect to q(X*) (mean and diagonal variances), the trained model fixed; y_test [N* x Do], Do <= D (the first Do
+            output dims).  One qx_psi_stats_batched + dense chain + qx_psi_adjoint, fp64."""
+            return _test_latent_gradients(y_test, x_test_mean, x_test_var)
+
+        @staticmethod
+        def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
+                                  x_test_var=None):
+            """Adam on q(X*) (the mean and softplus-parametrised variances) maximising f_hat* - KL(q(X*)) for test points
+            observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*.  K_uu and its factor
+            are formed once; no host synchronisation inside the loop."""
+            return _optimise_test_latents(y_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var)
+
+        @property
+        def prediction_terms(self):
+            """[1 x 5] terms of f_hat* in the last prediction evaluation: 1/2 N* D (log beta - log 2 pi), -D log|L_A|,
+            1/2 D beta (tr(K_uu^-1 Psi2*) - alpha N*), 1/2 beta^2 |C* Y*|^2, -1/2 beta |Y*|^2."""
+            b = pred_state.get('bound')
+            return None if b is None else b.terms
 
         @property
         def kernel(self):
@@ -413,9 +667,134 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             if callback is not None:
                 callback(it)
 
+    views_np = [np.asarray(v, dtype=np.float64) for v in views_train]
+    dev_ = x_mean_t.device
+    pred_state = {}
+
+    def _test_bound(views_test):
+        """Test bound of the first len(views_test) kernels (the observed views)."""
+        with torch.no_grad():
+            ks = inner[:len(views_test)]
+            bound = _TestBound([mv.raw['x_u'].detach() for mv in ks], [F.softplus(mv.raw['gamma_atoms']).detach() for mv in ks],
+                               [F.softplus(mv.raw['alpha_atoms']).detach() for mv in ks],
+                               [F.softplus(mv.raw['beta_atoms']).detach() for mv in ks],
+                               [_as_device(v, dev_) for v in views_test], dev_)
+        pred_state['bound'] = bound
+        return bound
+
+    def _check_views(views_test, missing):
+        vo = len(views_test)
+        if missing:
+            assert 0 < vo < num_views, \
+                'The number of test views for the missing data scenario must be less than the number of training views.'
+        else:
+            assert vo == num_views, 'The number of test views must be the same as the number of training views.'
+        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+        assert all(v.ndim == 2 for v in views_test), 'Each test view must be [N* x D_v].'
+        assert np.size(np.unique([v.shape[0] for v in views_test])) == 1 and views_test[0].shape[0] >= 1, \
+            'Each view must have the same number of test points.'
+        assert [v.shape[1] for v in views_test] == num_dimensions[:vo], \
+            'Observed dimensionality for prediction must be equal to the dimensionality of the training data for each ' \
+            'observed view.'
+        return views_test
+
+    def _bound_at(views_test, xt, st_):
+        bound = _test_bound(views_test)
+        with torch.no_grad():
+            f_test, _, _ = bound.evaluate(xt, st_)
+            terms = [mv.objective_terms for mv in inner]    # (objective_t, f_hat, KL, DP objective, hyper-prior) per view
+            f_hat = sum(t_[1] for t_ in terms)
+            kl, kl_t = terms[0][2], ops.kl_qx(xt, st_)
+        return f_hat + f_test - kl - kl_t
+
+    def _init(views_test, use_pca, x_test_mean, x_test_var):
+        vo = len(views_test)
+        return _init_test_latents(np.hstack(views_np[:vo]), np.hstack(views_test), x_mean_t, q, use_pca, x_test_mean,
+                                  x_test_var, dev_)
+
+    def _test_latent_gradients(views_test, x_test_mean, x_test_var):
+        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+        assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
+            'views_test must be the first Vo <= V views, each [N* x D_v]'
+        bound = _test_bound(views_test)
+        xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
+        with torch.no_grad():
+            _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
+            _, k_mu, k_s = _kl_test(xt, st_)
+        return d_mu - k_mu, d_s - k_s
+
+    def _optimise_test_latents(views_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
+                               x_test_var=None):
+        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+        assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
+            'views_test must be the first Vo <= V views, each [N* x D_v]'
+        xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
+        bound = _test_bound(views_test)
+
+        def grad_fn(mu, s):
+            _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
+            return d_mu - mu, d_s - 0.5 * (1.0 - 1.0 / s)
+        with torch.no_grad():
+            return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
+
     class ManifoldRelevanceDetermination(Trainable):
-        """Accessors as in the reference (gaussian_process.py:667-727)."""
+        """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
+        test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
+        y_test: the first Vo views are observed.  Prediction runs in fp64 (the reference's dtype) whatever `precision` the
+        model trains in; the training-side f_hat and KL(q(X)) are those of the model's own evaluation."""
         raw_variables = raw
+
+        @staticmethod
+        def predict_new_latent_variables(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+            """q(X*) for test points observed in every view, views_test: V arrays [N* x D_v] (gaussian_process.py:729-832).
+            Returns (prediction_lower_bound = sum_v f_hat_v + sum_v f_hat*_v - KL(q(X)) - KL(q(X*)), x_test_mean [N* x Q],
+            x_test_covar [N* x Q x Q]) — the reference's 3-tuple.  q(X*) starts as in bayesian_gp_lvm (nearest neighbour over
+            all views' columns).  reference_compat: no defect in this bound (both settings agree)."""
+            views_test = _check_views(views_test, False)
+            xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
+            return _bound_at(views_test, xt, st_), xt, torch.diag_embed(st_)
+
+        @staticmethod
+        def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+            """views_test: the FIRST Vo < V views of the test points (gaussian_process.py:834-990).  Returns
+                (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_means, predicted_covars)
+            with one entry per unobserved view v = Vo .. V-1: mean [N* x D_v], covariance [D_v x N* x N*].
+            reference_compat=True reproduces the reference's predicted means, which use the LAST training view's
+            C = L_A^-1 L_uu^-1 Psi1^T for every unobserved view (a variable leaked from the training loop, :938); the default
+            uses view v's own C.  The bound and the covariances are the same either way."""
+            views_test = _check_views(views_test, True)
+            vo = len(views_test)
+            xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
+            lb = _bound_at(views_test, xt, st_)
+            ku = inner[vo:]
+            with torch.no_grad():
+                bound_u = _TestBound([mv.raw['x_u'].detach() for mv in ku], [F.softplus(mv.raw['gamma_atoms']).detach() for mv in ku],
+                                     [F.softplus(mv.raw['alpha_atoms']).detach() for mv in ku],
+                                     [F.softplus(mv.raw['beta_atoms']).detach() for mv in ku],
+                                     [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(ku), dev_)
+                c_index = [len(ku) - 1] * len(ku) if reference_compat else list(range(len(ku)))
+                means, covars = _predictive_moments(bound_u, c_index, x_mean_t.detach(), F.softplus(x_var_raw).detach(),
+                                                    [_as_device(v, dev_) for v in views_np[vo:]], xt, st_)
+            return lb, xt, torch.diag_embed(st_), means, covars
+
+        @staticmethod
+        def test_latent_gradients(views_test, x_test_mean, x_test_var):
+            """d(sum_v f_hat*_v - KL(q(X*))) / d(x_test_mean, x_test_var) over the given first Vo <= V views (one batched
+            qx_psi_stats_batched / qx_psi_adjoint over the Vo kernels)."""
+            return _test_latent_gradients(views_test, x_test_mean, x_test_var)
+
+        @staticmethod
+        def optimise_test_latents(views_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
+                                  x_test_var=None):
+            """Adam on q(X*) maximising sum_v f_hat*_v - KL(q(X*)) over the given first Vo views; returns (x_test_mean,
+            x_test_var).  No host synchronisation inside the loop."""
+            return _optimise_test_latents(views_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var)
+
+        @property
+        def prediction_terms(self):
+            """[Vo x 5] terms of f_hat*_v of the last prediction evaluation (as bayesian_gp_lvm.prediction_terms, per view)."""
+            b = pred_state.get('bound')
+            return None if b is None else b.terms
 
         @property
         def number_of_views(self):

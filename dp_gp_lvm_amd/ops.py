@@ -100,6 +100,69 @@ def ard_rbf_gram_grad(x, gamma, alpha, w):
     return r, sx, sq
 
 
+def _qx_args(z, mu, s, gamma, alpha, zfac):
+    f64 = torch.float64
+    z, mu, s = _prep(z, f64, 'z'), _prep(mu, f64, 'mu'), _prep(s, f64, 's')
+    assert z.dim() == 3, 'z must be [B x M x Q]'
+    b, m, q = z.shape
+    assert mu.dim() == 2 and mu.shape[1] == q and s.shape == mu.shape, 'mu and s must be [N* x Q]'
+    gamma = _prep(gamma, f64, 'gamma').reshape(b, -1)
+    alpha = _prep(alpha, f64, 'alpha').reshape(-1)
+    assert gamma.shape[1] == q and alpha.numel() == b, 'gamma must be [B x Q], alpha [B]'
+    if zfac is not None:
+        zfac = _prep(zfac, f64, 'zfac')
+        assert tuple(zfac.shape) == (b, m, m), 'zfac must be [B x M x M]'
+    return z, mu, s, gamma, alpha, zfac, b, mu.shape[0], m, q
+
+
+def qx_pair_factor(z, gamma, alpha):
+    """The q(X*)-independent factor of Psi2 per kernel, alpha_b^2 exp(-1/4 sum_q gamma_bq (z_bm - z_bm')^2) [B,M,M], as the gram
+    of z_b with gamma_b / 2 and alpha_b^2 (one dpgp_ard_rbf_gram_f64 per kernel; formed once while Z is frozen)."""
+    f64 = torch.float64
+    z = _prep(z, f64, 'z')
+    gamma = _prep(gamma, f64, 'gamma').reshape(z.shape[0], -1)
+    alpha = _prep(alpha, f64, 'alpha').reshape(-1)
+    one = torch.ones(1, 1, dtype=f64, device=z.device)
+    return torch.cat([ard_rbf_gram(z[b], None, 0.5 * gamma[b:b + 1], (alpha[b] * alpha[b]).reshape(1, 1), one)
+                      for b in range(z.shape[0])]).contiguous()
+
+
+def qx_psi_stats_batched(z, mu, s, gamma, alpha, zfac=None):
+    """Psi1 [B,N*,M] and Psi2 [B,M,M] of q(X*) = (mu, s) [N*,Q] for B kernels with their own inducing inputs z [B,M,Q],
+    gamma [B,Q], alpha [B] (rbf_kernel.py:135-199), fp64 (dpgp_qx_psi_stats_batched_f64).  zfac: qx_pair_factor(z, gamma, alpha)
+    or None (computed in the kernels)."""
+    z, mu, s, gamma, alpha, zfac, b, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    psi_1 = torch.empty((b, n, m), dtype=torch.float64, device=mu.device)
+    psi_2 = torch.empty((b, m, m), dtype=torch.float64, device=mu.device)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_stats_workspace_bytes(b, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_stats_batched_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                               alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), psi_1.data_ptr(),
+                                               psi_2.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_stats_batched_f64')
+    return psi_1, psi_2
+
+
+def qx_psi_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None):
+    """(d_mu, d_s) [N*,Q]: the adjoints g1 = dF/dPsi1 [B,N*,M] and g2 = dF/dPsi2 [B,M,M] of the B kernels of
+    qx_psi_stats_batched contracted with dPsi/d(mu, s), summed over the kernels (dpgp_qx_psi_adjoint_f64; fixed summation
+    order, the same bits on every run)."""
+    z, mu, s, gamma, alpha, zfac, b, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    g1, g2 = _prep(g1, torch.float64, 'g1'), _prep(g2, torch.float64, 'g2')
+    assert tuple(g1.shape) == (b, n, m) and tuple(g2.shape) == (b, m, m), 'g1 must be [B x N* x M], g2 [B x M x M]'
+    d_mu = torch.empty((n, q), dtype=torch.float64, device=mu.device)
+    d_s = torch.empty_like(d_mu)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_adjoint_workspace_bytes(b, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_adjoint_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                         alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), g1.data_ptr(),
+                                         g2.data_ptr(), d_mu.data_ptr(), d_s.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_adjoint_f64')
+    return d_mu, d_s
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

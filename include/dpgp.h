@@ -107,6 +107,31 @@ size_t dpgp_ard_rbf_gram_grad_workspace_bytes(int N, int Q);
 int dpgp_ard_rbf_gram_grad_f64(int N, int Q, const double *x, const double *gamma, const double *alpha, const double *w, int ldw,
                                double *r, double *sx, double *sq, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Psi statistics of a test-point q(X*) for B kernels with their own inducing inputs, and their adjoint (the prediction
+ *      paths of bayesian_gp_lvm / manifold_relevance_determination: gaussian_process.py:329-538 and :729-990 evaluate
+ *      kernel.psi_1 / psi_2 of rbf_kernel.py:135-199 at q(X*) per view and differentiate the bound through them).
+ *      z[B][M][Q] (kernel b's inducing inputs), mu[N][Q], s[N][Q] (q(X*) shared by the B kernels), gamma[B][Q], alpha[B].
+ *      zfac: NULL, or [B][M][M] = alpha_b^2 exp(-1/4 sum_q gamma_bq (z_bmq - z_bm'q)^2), the pair factor of Psi2 that does not
+ *      depend on q(X*) (precompute it once while Z is frozen, e.g. as the gram of z with gamma / 2 and alpha^2; NULL computes
+ *      it in the kernels).  1 <= B, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.  Sums over pairs / test points are added in a fixed
+ *      order through the workspace: no atomics, the same bits on every run.
+ *   dpgp_qx_psi_stats_batched_f64:  psi1[B][N][M] (rbf_kernel.py:135-161), psi2[B][M][M] (:164-199, summed over the N test
+ *      points, exactly symmetric).  ws: dpgp_qx_psi_stats_workspace_bytes(B,N,M,Q).
+ *   dpgp_qx_psi_adjoint_f64:  with g1[B][N][M] = dF/dPsi1_b and g2[B][M][M] = dF/dPsi2_b (any matrix; symmetry not assumed)
+ *      d_mu[N][Q] = sum_b sum_m g1_b[n,m] dPsi1_b[n,m]/dmu[n,q] + sum_b sum_{m,m'} g2_b[m,m'] dPsi2_b[m,m']/dmu[n,q],  d_s
+ *      likewise (the derivatives with respect to the variances s, not their softplus parameters).  No z / gamma / alpha
+ *      outputs.  ws: dpgp_qx_psi_adjoint_workspace_bytes(B,N,M,Q).
+ *   The workspace queries are host functions (0 for a shape out of range). */
+#define DPGP_QX_PSI_MAX_Q 64
+size_t dpgp_qx_psi_stats_workspace_bytes(int B, int N, int M, int Q);
+int dpgp_qx_psi_stats_batched_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                  const double *gamma, const double *alpha, const double *zfac, double *psi1, double *psi2,
+                                  void *ws, size_t ws_bytes, void *stream);
+size_t dpgp_qx_psi_adjoint_workspace_bytes(int B, int N, int M, int Q);
+int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s, const double *gamma,
+                            const double *alpha, const double *zfac, const double *g1, const double *g2, double *d_mu, double *d_s,
+                            void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);
