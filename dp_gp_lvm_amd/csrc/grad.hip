@@ -736,8 +736,11 @@ __global__ __launch_bounds__(256) void psi1_grad_z_kernel(int D, int N, int M, i
 
 // ---------------------------------------------------------------------------------------------------------------
 // K_uu term of stage B for any M (the plain kernel above holds one row per thread, M <= 128): wk = (df/dK_uu) .* (K_uu - jitter I)
-// symmetric,  R[a] = sum_m' wk[a,m'],  T[a,q] = sum_m' wk[a,m'] z_m'q:   d/dz_aq = -2 gamma_q (z_aq R - T),
-// d/dgamma_q = -sum_a (R z_aq^2 - z_aq T).   Workgroup = (64 rows a, output dim), 4 lane groups share the columns m'.
+// symmetric,  T[a,q] = sum_m' wk[a,m'] (z_aq - z_m'q),  S[a,q] = sum_m' wk[a,m'] (z_aq - z_m'q)^2:   d/dz_aq = -2 gamma_q T,
+// d/dgamma_q = -1/2 sum_a S.   The differences are formed before the products: the diagonal wk[a,a], often the largest entry of
+// a row, adds exactly nothing (as z_aq R - T with R = sum_m' wk[a,m'], it left its fp32 rounding in a sum that it does not belong
+// to: 1e-3 of the largest entry of d/dz where the off-diagonal terms are small).  Workgroup = (64 rows a, output dim), 4 lane
+// groups share the columns m'.
 // ---------------------------------------------------------------------------------------------------------------
 template <int QP>
 __global__ __launch_bounds__(256) void kuu_grad_kernel(int D, int M, int Mp, int Q, const unsigned char *__restrict__ consts,
@@ -745,7 +748,7 @@ __global__ __launch_bounds__(256) void kuu_grad_kernel(int D, int M, int Mp, int
                                                        double *__restrict__ dz_part, double *__restrict__ dg_part) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     float *zs = reinterpret_cast<float *>(smem_raw);            // [M][QP] centred
-    float *comb = zs + (size_t)M * QP;                          // [3][64][QP + 1]
+    float *comb = zs + (size_t)M * QP;                          // [3][64][QP + 1]: T, then S
     float *red = comb + 3 * 64 * (QP + 1);                      // [QP]
     const Psi2Consts C = psi2_consts_layout(M, Q);
     const float *zs_g = reinterpret_cast<const float *>(consts + C.off_zs);
@@ -757,36 +760,50 @@ __global__ __launch_bounds__(256) void kuu_grad_kernel(int D, int M, int Mp, int
     if (t < QP) red[t] = 0.0f;
     __syncthreads();
     const double *W = WK + (size_t)d * Mp * Mp;
-    float R = 0.0f, T[QP];
+    float za[QP], T[QP], S[QP];
 #pragma unroll
-    for (int q = 0; q < QP; ++q) T[q] = 0.0f;
+    for (int q = 0; q < QP; ++q) {
+        za[q] = (a < M) ? zs[a * QP + q] : 0.0f;
+        T[q] = 0.0f;
+        S[q] = 0.0f;
+    }
     if (a < M)
         for (int mp = part; mp < M; mp += 4) {
             const float w = (float)((a >= mp) ? W[(size_t)a * Mp + mp] : W[(size_t)mp * Mp + a]);
-            R += w;
 #pragma unroll
-            for (int q = 0; q < QP; ++q) T[q] += w * zs[mp * QP + q];
+            for (int q = 0; q < QP; ++q) {
+                const float c = za[q] - zs[mp * QP + q], wc = w * c;
+                T[q] += wc;
+                S[q] += wc * c;
+            }
         }
-    if (part > 0) {
-        float *c = comb + ((part - 1) * 64 + al) * (QP + 1);
-        c[QP] = R;
+    float *c = comb + ((part > 0 ? part - 1 : 0) * 64 + al) * (QP + 1);
+    if (part > 0)
 #pragma unroll
         for (int q = 0; q < QP; ++q) c[q] = T[q];
-    }
+    __syncthreads();
+    if (part == 0)
+        for (int k = 0; k < 3; ++k) {
+            const float *ck = comb + (k * 64 + al) * (QP + 1);
+#pragma unroll
+            for (int q = 0; q < QP; ++q) T[q] += ck[q];
+        }
+    __syncthreads();
+    if (part > 0)
+#pragma unroll
+        for (int q = 0; q < QP; ++q) c[q] = S[q];
     __syncthreads();
     if (part == 0) {
         for (int k = 0; k < 3; ++k) {
-            const float *c = comb + (k * 64 + al) * (QP + 1);
-            R += c[QP];
+            const float *ck = comb + (k * 64 + al) * (QP + 1);
 #pragma unroll
-            for (int q = 0; q < QP; ++q) T[q] += c[q];
+            for (int q = 0; q < QP; ++q) S[q] += ck[q];
         }
 #pragma unroll
         for (int q = 0; q < QP; ++q) {
-            const float za = (a < M) ? zs[a * QP + q] : 0.0f;
             const float g = (q < Q) ? (float)gamma[(size_t)d * Q + q] : 0.0f;
-            if (a < M && q < Q) dz_part[((size_t)d * M + a) * Q + q] = (double)(-2.0f * g * (za * R - T[q]));
-            float x = (a < M) ? -(R * za * za - za * T[q]) : 0.0f;
+            if (a < M && q < Q) dz_part[((size_t)d * M + a) * Q + q] = (double)(-2.0f * g * T[q]);
+            float x = (a < M) ? -0.5f * S[q] : 0.0f;
             x = wave_sum(x);
             if (al == 0) red[q] = x;
         }

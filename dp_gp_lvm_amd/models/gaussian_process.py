@@ -418,6 +418,12 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         opt = torch.optim.Adam(list(raw.values()), lr=learning_rate)
         for it in range(num_iterations):
             g = _gradients()
+            # a failed factorisation or a non-finite gradient raises before Adam steps on it (as dp_gp_lvm_t and MRD do)
+            bad = ~torch.stack([torch.isfinite(v).all() for v in g.values()]).all() | (inner.cholesky_info != 0)
+            if bool(bad):
+                eff = precision or 'f64'
+                raise FloatingPointError('iteration %d: failed Cholesky factorisation or non-finite gradient (precision=%r)%s'
+                                         % (it, eff, '' if eff == 'f64' else '; use precision="f64"'))
             for k, p_ in raw.items():
                 p_.grad = g[k].reshape(p_.shape)
             opt.step()
