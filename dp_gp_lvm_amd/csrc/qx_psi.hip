@@ -24,6 +24,12 @@
 //            The Psi1 term is evaluated by the workgroup whose slab holds the diagonal tile of the column block.  Partial
 //            (d_mu, d_s) go to slab [slab][b]; a second launch adds them in b order, then slab order.
 // No atomics anywhere: the same inputs give the same bits.
+//
+// Weighted forms (per-entry observation masks): wt [B][N] multiplies test point n's Psi2 term of kernel b (c2_n in both
+// kernels); Psi1 and its adjoint are not weighted.  The kernels are templated on WEIGHTED: the unweighted instantiations
+// are the code of the unweighted entry points, and wt == NULL runs them.  A point of weight 0 costs no exponential: the
+// stats kernel skips it in its staged-point loop (a workgroup-uniform branch on the staged weight), the adjoint skips a
+// tile's pair loop when all 64 points of the wave have weight 0 for kernel b.  Either way its contribution is exactly 0.
 #include "internal.h"
 
 #define QP_TILE 32
@@ -74,11 +80,13 @@ __global__ __launch_bounds__(256) void qp_psi1_kernel(int N, int M, int Q, const
     psi1[(size_t)b * N * M + e] = alpha[b] * exp(-0.5 * acc);
 }
 
-// ---- Psi2 partial tiles: (pair tile, n slab, b)
+// ---- Psi2 partial tiles: (pair tile, n slab, b); WEIGHTED: sc2 carries wt[b][n] c2_n and a zero skips the point
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void qp_psi2_kernel(int N, int M, int Q, int T, int n_per_slab, const double *__restrict__ z,
                                                       const double *__restrict__ mu, const double *__restrict__ s,
                                                       const double *__restrict__ gamma, const double *__restrict__ alpha,
-                                                      const double *__restrict__ zfac, double *__restrict__ part) {
+                                                      const double *__restrict__ zfac, const double *__restrict__ wt,
+                                                      double *__restrict__ part) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     double *smu = reinterpret_cast<double *>(smem_raw);    // [QP_SN][Q]
     double *siw = smu + (size_t)QP_SN * Q;                  // [QP_SN][Q]
@@ -111,12 +119,18 @@ __global__ __launch_bounds__(256) void qp_psi2_kernel(int N, int M, int Q, int T
             siw[k] = g / w2;
         }
         if (t < nn) {
-            double l = 0.0;
-            for (int q = 0; q < Q; ++q) l += log(fma(2.0 * gamma[(size_t)b * Q + q], s[(size_t)(nb + t) * Q + q], 1.0));
-            sc2[t] = exp(-0.5 * l);
+            const double wn = WEIGHTED ? wt[(size_t)b * N + nb + t] : 1.0;
+            if (WEIGHTED && wn == 0.0) {
+                sc2[t] = 0.0;
+            } else {
+                double l = 0.0;
+                for (int q = 0; q < Q; ++q) l += log(fma(2.0 * gamma[(size_t)b * Q + q], s[(size_t)(nb + t) * Q + q], 1.0));
+                sc2[t] = WEIGHTED ? wn * exp(-0.5 * l) : exp(-0.5 * l);
+            }
         }
         __syncthreads();
         for (int i = 0; i < nn; ++i) {
+            if (WEIGHTED && sc2[i] == 0.0) continue;           // (the same LDS word for every thread: uniform)
             const double *mi = smu + (size_t)i * Q, *wi = siw + (size_t)i * Q;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -155,13 +169,13 @@ __global__ __launch_bounds__(256) void qp_psi2_reduce_kernel(int B, int M, int s
 }
 
 // ---- adjoint partials: (64 test points, pair slab, b * qchunks + chunk); KQ: the chunk's register width
-template <int KQ>
+template <int KQ, bool WEIGHTED>
 __global__ __launch_bounds__(64) void qp_adjoint_kernel(int B, int N, int M, int Q, int T, int tiles_per_slab,
                                                         const double *__restrict__ z, const double *__restrict__ mu,
                                                         const double *__restrict__ s, const double *__restrict__ gamma,
                                                         const double *__restrict__ alpha, const double *__restrict__ zfac,
-                                                        const double *__restrict__ g1, const double *__restrict__ g2,
-                                                        double *__restrict__ part) {
+                                                        const double *__restrict__ wt, const double *__restrict__ g1,
+                                                        const double *__restrict__ g2, double *__restrict__ part) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     double *smu = reinterpret_cast<double *>(smem_raw);    // [Q][64]
     double *siw1 = smu + (size_t)Q * QP_NT;                 // [Q][64]
@@ -190,7 +204,9 @@ __global__ __launch_bounds__(64) void qp_adjoint_kernel(int B, int N, int M, int
         l1 += log(w1);
         l2 += log(w2);
     }
-    const double c1 = al * exp(-0.5 * l1), c2 = exp(-0.5 * l2);
+    const double wn = WEIGHTED ? (live ? wt[(size_t)b * N + n] : 0.0) : 1.0;
+    const double c1 = al * exp(-0.5 * l1), c2 = WEIGHTED ? wn * exp(-0.5 * l2) : exp(-0.5 * l2);
+    const bool pairs = !WEIGHTED || __any(wn != 0.0);          // the workgroup is one wave: uniform
     double mk[KQ], i1[KQ], i2[KQ], s1[KQ], s2[KQ], t1[KQ], t2[KQ], dk[KQ];
     double s0 = 0.0, t0 = 0.0;
 #pragma unroll
@@ -206,6 +222,7 @@ __global__ __launch_bounds__(64) void qp_adjoint_kernel(int B, int N, int M, int
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
         int I, J;
         qp_tile_ij(tile, T, I, J);
+        if (WEIGHTED && !pairs && I != J) continue;            // every weight of the wave is 0 and no Psi1 term here
         const int m0 = I * QP_TILE, c0 = J * QP_TILE;
         const int nr = min(QP_TILE, M - m0), nc = min(QP_TILE, M - c0);
         __syncthreads();                                       // (previous tile done with zr / zc / hs)
@@ -227,7 +244,7 @@ __global__ __launch_bounds__(64) void qp_adjoint_kernel(int B, int N, int M, int
         }
         __syncthreads();
         // Psi2 term over the tile's pairs (uniform over the wave: every lane visits the same pair)
-        for (int r = 0; r < nr; ++r) {
+        for (int r = 0; r < (pairs ? nr : 0); ++r) {
             const double *zrr = zr + (size_t)r * Q;
             for (int cc = (I == J ? r : 0); cc < nc; ++cc) {
                 const double h = hs[r * QP_HSTRIDE + cc];
@@ -357,17 +374,41 @@ int qp_set_lds(const void *fn, size_t lds) {
     return DPGP_OK;
 }
 
-template <int KQ>
+template <int KQ, bool WEIGHTED>
 int qp_launch_adjoint(const QpAdjPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
-                      const double *gamma, const double *alpha, const double *zfac, const double *g1, const double *g2,
-                      double *part, hipStream_t st) {
+                      const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g1,
+                      const double *g2, double *part, hipStream_t st) {
     const size_t lds = qp_adj_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_adjoint_kernel<KQ>), lds)) return DPGP_ERR_LAUNCH;
+    if (qp_set_lds(reinterpret_cast<const void *>(qp_adjoint_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
-    hipLaunchKernelGGL((qp_adjoint_kernel<KQ>), dim3(p.nt, p.slabs, B * p.qchunks), dim3(QP_NT), lds, st, B, N, M, Q, p.T,
-                       p.tiles_per_slab, z, mu, s, gamma, alpha, zfac, g1, g2, part);
+    hipLaunchKernelGGL((qp_adjoint_kernel<KQ, WEIGHTED>), dim3(p.nt, p.slabs, B * p.qchunks), dim3(QP_NT), lds, st, B, N, M, Q,
+                       p.T, p.tiles_per_slab, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;
+}
+
+template <bool WEIGHTED>
+int qp_launch_psi2(const QpStatsPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                   const double *gamma, const double *alpha, const double *zfac, const double *wt, double *part,
+                   hipStream_t st) {
+    const size_t lds = qp_stats_lds(Q);
+    if (qp_set_lds(reinterpret_cast<const void *>(qp_psi2_kernel<WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL((qp_psi2_kernel<WEIGHTED>), dim3(p.tiles, p.slabs, B), dim3(256), lds, st, N, M, Q, p.T, p.n_per_slab,
+                       z, mu, s, gamma, alpha, zfac, wt, part);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
+
+template <bool WEIGHTED>
+int qp_dispatch_adjoint(const QpAdjPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                        const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g1,
+                        const double *g2, double *part, hipStream_t st) {
+    const int w = Q < QP_QCHUNK ? Q : QP_QCHUNK;
+    return w <= 1   ? qp_launch_adjoint<1, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
+           : w <= 2 ? qp_launch_adjoint<2, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
+           : w <= 4 ? qp_launch_adjoint<4, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
+                    : qp_launch_adjoint<8, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st);
 }
 
 bool qp_shape_ok(int B, int N, int M, int Q) {
@@ -382,9 +423,10 @@ extern "C" size_t dpgp_qx_psi_stats_workspace_bytes(int B, int N, int M, int Q) 
     return sizeof(double) * (size_t)p.slabs * B * M * M;
 }
 
-extern "C" int dpgp_qx_psi_stats_batched_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
-                                             const double *gamma, const double *alpha, const double *zfac, double *psi1,
-                                             double *psi2, void *ws, size_t ws_bytes, void *stream) {
+// wt == NULL: the unweighted instantiations (dpgp_qx_psi_stats_batched_f64 is this with wt == NULL)
+extern "C" int dpgp_qx_psi_stats_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                              const double *gamma, const double *alpha, const double *zfac, const double *wt,
+                                              double *psi1, double *psi2, void *ws, size_t ws_bytes, void *stream) {
     if (B < 1) return -1;
     if (N < 1) return -2;
     if (M < 1) return -3;
@@ -404,18 +446,21 @@ extern "C" int dpgp_qx_psi_stats_batched_f64(int B, int N, int M, int Q, const d
     hipLaunchKernelGGL(qp_psi1_kernel, dim3((unsigned)(((size_t)N * M + 255) / 256), B), dim3(256), 0, st, N, M, Q, z, mu, s,
                        gamma, alpha, psi1);
     DPGP_LAUNCH_CHECK();
-    const size_t lds = qp_stats_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_psi2_kernel), lds)) return DPGP_ERR_LAUNCH;
     double *part = static_cast<double *>(ws);
-    DPGP_PRELAUNCH();
-    hipLaunchKernelGGL(qp_psi2_kernel, dim3(p.tiles, p.slabs, B), dim3(256), lds, st, N, M, Q, p.T, p.n_per_slab, z, mu, s,
-                       gamma, alpha, zfac, part);
-    DPGP_LAUNCH_CHECK();
+    const int rc = wt ? qp_launch_psi2<true>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, part, st)
+                      : qp_launch_psi2<false>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, part, st);
+    if (rc) return rc;
     const size_t tot = (size_t)B * M * M;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL(qp_psi2_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, B, M, p.slabs, part, psi2);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;
+}
+
+extern "C" int dpgp_qx_psi_stats_batched_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                             const double *gamma, const double *alpha, const double *zfac, double *psi1,
+                                             double *psi2, void *ws, size_t ws_bytes, void *stream) {
+    return dpgp_qx_psi_stats_weighted_f64(B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, psi1, psi2, ws, ws_bytes, stream);
 }
 
 extern "C" size_t dpgp_qx_psi_adjoint_workspace_bytes(int B, int N, int M, int Q) {
@@ -424,9 +469,11 @@ extern "C" size_t dpgp_qx_psi_adjoint_workspace_bytes(int B, int N, int M, int Q
     return sizeof(double) * (size_t)p.slabs * B * 2 * Q * N;
 }
 
-extern "C" int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
-                                       const double *gamma, const double *alpha, const double *zfac, const double *g1,
-                                       const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes, void *stream) {
+// wt == NULL: the unweighted instantiations (dpgp_qx_psi_adjoint_f64 is this with wt == NULL)
+extern "C" int dpgp_qx_psi_adjoint_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                                const double *gamma, const double *alpha, const double *zfac, const double *wt,
+                                                const double *g1, const double *g2, double *d_mu, double *d_s, void *ws,
+                                                size_t ws_bytes, void *stream) {
     if (B < 1) return -1;
     if (N < 1) return -2;
     if (M < 1) return -3;
@@ -445,11 +492,8 @@ extern "C" int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double 
     hipStream_t st = (hipStream_t)stream;
     const QpAdjPlan p = qp_adj_plan(B, N, M, Q);
     double *part = static_cast<double *>(ws);
-    const int w = Q < QP_QCHUNK ? Q : QP_QCHUNK;
-    int rc = w <= 1   ? qp_launch_adjoint<1>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, g1, g2, part, st)
-             : w <= 2 ? qp_launch_adjoint<2>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, g1, g2, part, st)
-             : w <= 4 ? qp_launch_adjoint<4>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, g1, g2, part, st)
-                      : qp_launch_adjoint<8>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, g1, g2, part, st);
+    const int rc = wt ? qp_dispatch_adjoint<true>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
+                      : qp_dispatch_adjoint<false>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, g1, g2, part, st);
     if (rc) return rc;
     const size_t tot = (size_t)2 * Q * N;
     DPGP_PRELAUNCH();
@@ -457,4 +501,11 @@ extern "C" int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double 
                        d_mu, d_s);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;
+}
+
+extern "C" int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                       const double *gamma, const double *alpha, const double *zfac, const double *g1,
+                                       const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes, void *stream) {
+    return dpgp_qx_psi_adjoint_weighted_f64(B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, g1, g2, d_mu, d_s, ws, ws_bytes,
+                                            stream);
 }

@@ -24,9 +24,11 @@ from ..utils.constants import GP_LVM_DEFAULT_LATENT_DIMENSIONS, GP_LVM_DEFAULT_N
     DP_DEFAULT_TRUNCATION_LEVEL, DP_DEFAULT_ALPHA_PRIOR_PARAMS, GP_INIT_GAMMA, GP_INIT_ALPHA, GP_INIT_BETA, \
     GP_DEFAULT_JITTER
 from ..utils.expressions import principal_component_analysis as pca
+from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
+from .test_bound import _TestBound
 
 
 def shard_bounds(num_dimensions, rank, world_size):
@@ -396,6 +398,61 @@ def dp_gp_lvm(y_train,
         pred_state['terms'] = terms_t.clone()
         return sums[0].clone(), sums[1].clone()
 
+    def _masked(y_test, observed, predict=False, reference_compat=False):
+        assert not sharded and world == 1, 'prediction paths run on one GPU'
+        return _missing.masked_arguments(y_test, observed, num_dimensions, predict, reference_compat)
+
+    def _masked_bound(y0, obs):
+        """The fp64 test bound with one slot per output dim that has an observed entry: that dim's mixed (gamma, alpha, beta) of
+        this evaluate() and the shared inducing inputs.  Returns (bound, the training-side evaluation out[5])."""
+        out = evaluate().clone()
+        cols = np.flatnonzero(obs.any(axis=0))
+        idx = torch.as_tensor(cols, device=device)
+        bound = _TestBound.slots(x_u.detach(), buf['gamma'][idx], buf['alpha'][idx, 0], buf['beta'][idx, 0],
+                                 _t(y0[:, cols].T[:, :, None]), np.ones(cols.size), _t(obs[:, cols].T), device)
+        pred_state['missing_columns'] = _missing.missing_columns(obs)
+        return bound, out
+
+    def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
+        if x_test_mean is None and not use_pca:
+            x_test_mean = _missing.masked_nearest_neighbour_init(np.asarray(y_train), y0, obs, x_mean.detach().cpu().numpy())
+        return _init_test_latents(y0, None, use_pca, x_test_mean, x_test_var)
+
+    def _predictive_moments(cols, xt, st_):
+        """Predictive mean [N* x Du] and covariance [Du x N* x N*] of the output dims `cols` at q(X*) (dp_gp_lvm.py:426-498)."""
+        num_test_points, m_ = xt.shape[0], num_inducing_points
+        idx = torch.as_tensor(np.asarray(cols), device=device)
+        gu, au, bu = buf['gamma'][idx].contiguous(), buf['alpha'][:, 0][idx].contiguous(), buf['beta'][:, 0][idx].contiguous()
+        s_train = F.softplus(x_var_raw)
+        psi_1 = ops.psi1(x_u, x_mean, s_train, gu, au)                          # [Du x N x M]
+        psi_2 = ops.psi2(x_u, x_mean, s_train, gu, au)
+        psi_1t = ops.psi1(x_u, xt, st_, gu, au)                                  # [Du x N* x M]
+        psi_2t = ops.psi2(x_u, xt, st_, gu, au)
+        k_uu = ops.ard_rbf_gram(x_u, None, gu, au, bu, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)
+        l_uu, _ = ops.potrf_batched(k_uu)
+        h = ops.trsm_batched(l_uu, psi_2)
+        a_mat = bu[:, None, None] * ops.trsm_batched(l_uu, h.transpose(1, 2).contiguous()).transpose(1, 2) + \
+            torch.eye(m_, dtype=TORCH_DTYPE, device=device)
+        l_a, _ = ops.potrf_batched(a_mat.contiguous())
+        c = ops.trsm_batched(l_a, ops.trsm_batched(l_uu, psi_1.transpose(1, 2).contiguous()))          # [Du x M x N]
+        c_pred = ops.trsm_batched(l_a, ops.trsm_batched(l_uu, psi_1t.transpose(1, 2).contiguous()))   # [Du x M x N*]
+        y_u = _t(np.asarray(y_train)[:, np.asarray(cols)]).transpose(0, 1).contiguous()[:, :, None]    # [Du x N x 1]
+        cy = ops.matmul(c, y_u)                                                # [Du x M x 1]
+        predicted_mean = (bu[:, None] * ops.matmul(c_pred.transpose(1, 2), cy)[:, :, 0]).transpose(0, 1)   # [N* x Du]
+        eye = torch.eye(m_, dtype=TORCH_DTYPE, device=device).expand(len(cols), m_, m_).contiguous()
+        l_uu_inv, l_a_inv = ops.trsm_batched(l_uu, eye), ops.trsm_batched(l_a, eye)
+        ainv = ops.matmul(l_a_inv.transpose(1, 2), l_a_inv)                    # A^-1
+        g = psi_2t - ops.matmul(psi_1t.transpose(1, 2), psi_1t)               # [Du x M x M]
+        scale_yu = ops.matmul(ops.matmul(ops.matmul(l_uu_inv.transpose(1, 2), ops.matmul(ainv, l_uu_inv)),
+                                         psi_1.transpose(1, 2)), y_u)       # [Du x M x 1]
+        yu_var = bu * bu * ops.matmul(scale_yu.transpose(1, 2), ops.matmul(g, scale_yu))[:, 0, 0]
+        tr_term = torch.diagonal(ops.matmul(ops.matmul(l_uu_inv.transpose(1, 2), ops.matmul(eye - ainv, l_uu_inv)),
+                                            psi_2t), dim1=-2, dim2=-1).sum(-1)
+        psi_0t = ops.psi0(num_test_points, au)[:, 0]
+        predicted_covar = yu_var[:, None, None] + (psi_0t + 1.0 / bu + tr_term)[:, None, None] * \
+            torch.eye(num_test_points, dtype=TORCH_DTYPE, device=device)
+        return predicted_mean, predicted_covar
+
     class DP_GP_LVM(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508)."""
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
@@ -482,8 +539,14 @@ def dp_gp_lvm(y_train,
 
         @property
         def prediction_terms(self):
-            """[D* x 5] f_hat terms of the test points in the last predict_* call (the observed dims for missing data)."""
+            """[D* x 5] f_hat terms of the test points in the last predict_* call (the observed dims for missing data; with
+            `observed`: [slots x 5], one slot per output dim that has an observed entry, ascending)."""
             return pred_state.get('terms')
+
+        @property
+        def missing_columns(self):
+            """The output dims whose moments the last predict_missing_data returned (ascending), or None."""
+            return pred_state.get('missing_columns')
 
         @staticmethod
         def _reference_defect(num_test_points):
@@ -523,10 +586,20 @@ def dp_gp_lvm(y_train,
             return lower_bound, xt, torch.diag_embed(st_), test_ll
 
         @staticmethod
-        def test_latent_gradients(y_test, x_test_mean, x_test_var):
+        def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
             """d (f_hat_test - KL(q(X*))) / d (x_test_mean, x_test_var) with the trained model fixed — what TensorFlow's autograd
             gives a caller of the reference who optimises q(X*) on the bounds returned by predict_*; y_test [N* x Do], Do <= D
-            (the first Do output dims).  Uses the backward pass of the fused ELBO (stages A and B) on the test points."""
+            (the first Do output dims).  Uses the backward pass of the fused ELBO (stages A and B) on the test points.
+            observed: as predict_missing_data (y_test [N* x D]; True everywhere is allowed here): the gradient of the masked
+            bound, fp64, by the weighted test-point operators."""
+            if observed is not None:
+                bound, _ = _masked_bound(*_masked(y_test, observed))
+                xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
+                    _t(x_test_var.detach().cpu().numpy() if torch.is_tensor(x_test_var) else x_test_var)
+                with torch.no_grad():
+                    _, dmu, ds = bound.evaluate(xt, st_, grad=True)
+                    pred_state['terms'] = bound.terms
+                return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)
             assert not sharded and world == 1, 'prediction paths run on one GPU'
             y_t = _t(np.asarray(y_test, dtype=np.float64))
             dd = y_t.shape[1]
@@ -542,9 +615,24 @@ def dp_gp_lvm(y_train,
 
         @staticmethod
         def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
-                                  x_test_var=None):
+                                  x_test_var=None, observed=None):
             """Adam on q(X*) (mean and softplus-parametrised variances) maximising f_hat_test - KL(q(X*)) for test points
-            observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*."""
+            observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*.  observed: as
+            predict_missing_data; the slots' factors are formed once, no host synchronisation inside the loop."""
+            if observed is not None:
+                y0, obs = _masked(y_test, observed)
+                xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+                bound, _ = _masked_bound(y0, obs)
+                raw = torch.log(torch.expm1(st_))
+                opt = torch.optim.Adam([xt, raw], lr=learning_rate)
+                with torch.no_grad():
+                    for _ in range(num_iterations):
+                        sv = F.softplus(raw)
+                        _, g_mu, g_s = bound.evaluate(xt, sv, grad=True)
+                        xt.grad, raw.grad = -(g_mu - xt), -(g_s - 0.5 * (1.0 - 1.0 / sv)) * torch.sigmoid(raw)
+                        opt.step()
+                    pred_state['terms'] = bound.terms
+                    return xt, F.softplus(raw)
             y_test = np.asarray(y_test, dtype=np.float64)
             xt, st_ = _init_test_latents(y_test, np.asarray(y_train)[:, :y_test.shape[1]], use_pca, x_test_mean, x_test_var)
             raw = torch.log(torch.expm1(st_))
@@ -557,55 +645,47 @@ def dp_gp_lvm(y_train,
             return xt, F.softplus(raw)
 
         @staticmethod
-        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
+                                 observed=None):
             """Mirror of dp_gp_lvm.py:311-500: y_test [N* x Do] holds the FIRST Do output dims of the test points; returns
             (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
             for the remaining Du = D - Do dims at the initial q(X*) (see predict_new_latent_variables).  Composed of the
-            library's operators (Psi statistics at q(X*), batched Cholesky / triangular solves) and plain fp64 GEMMs."""
+            library's operators (Psi statistics at q(X*), batched Cholesky / triangular solves) and plain fp64 GEMMs.
+
+            observed (extension): a boolean [N* x D] mask of the entries of y_test [N* x D] that were measured, any pattern
+            (entries where it is False are ignored and may be NaN).  The bound is f_hat + f_hat*(masked) - KL(q(X)) - KL(q(X*)):
+            output dim d enters f_hat* with the test points at which it was measured, as one slot of the weighted test-point
+            operators (fp64 whatever `precision` is; the training-side f_hat and KL are the model's own evaluation);
+            KL(q(X*)) runs over all N* rows.  The Du predicted dims are the columns with at least one unobserved entry,
+            ascending (property missing_columns); q(X*) starts at the masked nearest neighbour (a row with nothing observed
+            at 0).  AssertionError for a non-boolean mask, a shape mismatch, a mask that is True everywhere, or
+            reference_compat=True."""
+            if observed is not None:
+                y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
+                xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+                bound, out = _masked_bound(y0, obs)
+                with torch.no_grad():
+                    f_hat_test, _, _ = bound.evaluate(xt, st_)
+                    pred_state['terms'] = bound.terms
+                    lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                    predicted_mean, predicted_covar = _predictive_moments(pred_state['missing_columns'], xt, st_)
+                return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
             assert not sharded and world == 1, 'prediction paths run on one GPU'
             y_test = np.asarray(y_test, dtype=np.float64)
             num_test_points, num_observed_dims = np.shape(y_test)
             assert num_observed_dims < num_dimensions, \
                 'Observed dimensionality for missing data scenario must be less than total ' \
                 'dimensionality of training data.'
-            do, m_ = num_observed_dims, num_inducing_points
+            do = num_observed_dims
             xt, st_ = _init_test_latents(y_test, np.asarray(y_train)[:, :do], use_pca, x_test_mean, x_test_var)
             out = evaluate().clone()
-            gam, al, be = buf['gamma'], buf['alpha'][:, 0], buf['beta'][:, 0]
             f_hat_test, kl_test = _fhat_on(_t(y_test), xt, st_, dims=do)
             lower_bound = out[1] + f_hat_test - out[2] - kl_test
             if reference_compat:
                 lower_bound = lower_bound + DP_GP_LVM._reference_defect(num_test_points)
             # predictive mean / covariance of the unobserved dims (:426-498), output dims do .. D-1 only
-            gu, au, bu = gam[do:].contiguous(), al[do:].contiguous(), be[do:].contiguous()
-            s_train = F.softplus(x_var_raw)
-            psi_1 = ops.psi1(x_u, x_mean, s_train, gu, au)                          # [Du x N x M]
-            psi_2 = ops.psi2(x_u, x_mean, s_train, gu, au)
-            psi_1t = ops.psi1(x_u, xt, st_, gu, au)                                  # [Du x N* x M]
-            psi_2t = ops.psi2(x_u, xt, st_, gu, au)
-            k_uu = ops.ard_rbf_gram(x_u, None, gu, au, bu, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)
-            l_uu, _ = ops.potrf_batched(k_uu)
-            h = ops.trsm_batched(l_uu, psi_2)
-            a_mat = bu[:, None, None] * ops.trsm_batched(l_uu, h.transpose(1, 2).contiguous()).transpose(1, 2) + \
-                torch.eye(m_, dtype=TORCH_DTYPE, device=device)
-            l_a, _ = ops.potrf_batched(a_mat.contiguous())
-            c = ops.trsm_batched(l_a, ops.trsm_batched(l_uu, psi_1.transpose(1, 2).contiguous()))          # [Du x M x N]
-            c_pred = ops.trsm_batched(l_a, ops.trsm_batched(l_uu, psi_1t.transpose(1, 2).contiguous()))   # [Du x M x N*]
-            y_u = _t(np.asarray(y_train)[:, do:]).transpose(0, 1).contiguous()[:, :, None]                 # [Du x N x 1]
-            cy = ops.matmul(c, y_u)                                                # [Du x M x 1]
-            predicted_mean = (bu[:, None] * ops.matmul(c_pred.transpose(1, 2), cy)[:, :, 0]).transpose(0, 1)   # [N* x Du]
-            eye = torch.eye(m_, dtype=TORCH_DTYPE, device=device).expand(num_dimensions - do, m_, m_).contiguous()
-            l_uu_inv, l_a_inv = ops.trsm_batched(l_uu, eye), ops.trsm_batched(l_a, eye)
-            ainv = ops.matmul(l_a_inv.transpose(1, 2), l_a_inv)                    # A^-1
-            g = psi_2t - ops.matmul(psi_1t.transpose(1, 2), psi_1t)               # [Du x M x M]
-            scale_yu = ops.matmul(ops.matmul(ops.matmul(l_uu_inv.transpose(1, 2), ops.matmul(ainv, l_uu_inv)),
-                                                 psi_1.transpose(1, 2)), y_u)       # [Du x M x 1]
-            yu_var = bu * bu * ops.matmul(scale_yu.transpose(1, 2), ops.matmul(g, scale_yu))[:, 0, 0]
-            tr_term = torch.diagonal(ops.matmul(ops.matmul(l_uu_inv.transpose(1, 2), ops.matmul(eye - ainv, l_uu_inv)),
-                                                  psi_2t), dim1=-2, dim2=-1).sum(-1)
-            psi_0t = ops.psi0(num_test_points, au)[:, 0]
-            predicted_covar = yu_var[:, None, None] + (psi_0t + 1.0 / bu + tr_term)[:, None, None] * \
-                torch.eye(num_test_points, dtype=TORCH_DTYPE, device=device)
+            pred_state['missing_columns'] = np.arange(do, num_dimensions)
+            predicted_mean, predicted_covar = _predictive_moments(pred_state['missing_columns'], xt, st_)
             return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
 
     return DP_GP_LVM()

@@ -26,9 +26,11 @@ from ..kernels.rbf_kernel import k_ard_rbf
 from ..utils.constants import GP_LVM_DEFAULT_LATENT_DIMENSIONS, GP_LVM_DEFAULT_NUM_INDUCING_POINTS, GP_INIT_GAMMA, \
     GP_INIT_ALPHA, GP_INIT_BETA, GP_DEFAULT_JITTER
 from ..utils.expressions import principal_component_analysis as pca
+from ..utils import missing as _missing
 from .dp_gp_lvm import dp_gp_lvm_t
 from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
+from .test_bound import _TestBound, _as_device
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -77,11 +79,6 @@ class _GPLogLikelihood(torch.autograd.Function):
         x, gamma, alpha, beta, kinv, a = ctx.saved_tensors
         d_x, d_gamma, d_alpha, d_beta = _gp_backward(x, gamma, alpha, beta, kinv.clone(), a, weights=g)
         return d_x, d_gamma, d_alpha, d_beta, None
-
-
-def _as_device(v, device, shape=None):
-    t = torch.as_tensor(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64), dtype=TORCH_DTYPE)
-    return (t if shape is None else t.reshape(shape)).to(device).contiguous()
 
 
 def _gaussian_process(x_raw, y, raw, x_name, device):
@@ -185,74 +182,6 @@ def _gaussian_process(x_raw, y, raw, x_name, device):
                 return raw[x_name]
         return GPLVM()
     return GaussianProcess()
-
-
-class _TestBound:
-    """The q(X*) part of the prediction bounds of bayesian_gp_lvm / manifold_relevance_determination (gaussian_process.py:365-394,
-    :776-831, :880-919): B frozen ARD-RBF kernels (inducing inputs z [B,M,Q], gamma [B,Q], alpha [B], beta [B]) sharing q(X*), each
-    with its own test outputs y_b [N*, D_b].  Everything runs in fp64 on the device, whatever precision the model trains in.
-
-    Once per object (the trained model is frozen): K_uu_b, its Cholesky factor L_b, L_b^-1, K_uu_b^-1 (ard_rbf_gram / potrf_batched /
-    tril_inverse_batched / matmul) and the q(X*)-independent pair factor of Psi2 (ops.qx_pair_factor).
-    Per evaluation: Psi1*, Psi2* of the B kernels (one qx_psi_stats_batched), then on [B, M, M] arrays
-        T = L^-1 Psi2* L^-T,  A = beta T + I = L_A L_A^T,  R0 = L_A^-1 L^-1,  U = R0 Psi1*^T Y,
-        f_hat*_b = 1/2 N* D_b (log beta - log 2 pi) - D_b log|L_A| + 1/2 D_b beta (tr T - alpha N*) + 1/2 beta^2 |U|^2 - 1/2 beta |Y|^2
-    and, for the gradient, the adjoints  (P = R0^T R0 = (K_uu + beta Psi2*)^-1,  R = R0^T U)
-        G2 = 1/2 D_b beta (K_uu^-1 - P) - 1/2 beta^3 R R^T,    G1 = beta^2 Y R^T
-    contracted with dPsi/d(mu, s) by one qx_psi_adjoint.  No host synchronisation."""
-
-    def __init__(self, z, gamma, alpha, beta, ys, device):
-        f64 = TORCH_DTYPE
-        self.z = torch.stack([_as_device(v, device) for v in z]).contiguous()                       # [B, M, Q]
-        self.gamma = torch.stack([_as_device(v, device).reshape(-1) for v in gamma]).contiguous()   # [B, Q]
-        self.alpha = torch.cat([_as_device(v, device).reshape(-1) for v in alpha]).contiguous()     # [B]
-        self.beta = torch.cat([_as_device(v, device).reshape(-1) for v in beta]).contiguous()       # [B]
-        b, m = self.z.shape[0], self.z.shape[1]
-        self.m, self.device = m, device
-        self.dims = torch.tensor([y.shape[1] for y in ys], dtype=f64, device=device)
-        n_t, dmax = ys[0].shape[0], max(y.shape[1] for y in ys)
-        self.n_t = n_t
-        self.y = torch.zeros((b, n_t, dmax), dtype=f64, device=device)                          # zero-padded columns
-        for i, y in enumerate(ys):
-            self.y[i, :, :y.shape[1]] = y
-        self.yy = torch.sum(self.y * self.y, dim=(1, 2))
-        one = torch.ones(1, 1, dtype=f64, device=device)
-        k_uu = torch.stack([ops.ard_rbf_gram(self.z[i], None, self.gamma[i:i + 1], self.alpha[i].reshape(1, 1), one,
-                                             include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)[0]
-                            for i in range(b)])
-        self.l_uu, self.info_uu = ops.potrf_batched(k_uu)
-        self.li = ops.tril_inverse_batched(self.l_uu)
-        self.kinv = ops.matmul(self.li.transpose(1, 2), self.li)
-        self.zfac = ops.qx_pair_factor(self.z, self.gamma, self.alpha)
-        self.eye = torch.eye(m, dtype=f64, device=device)
-        self.terms = None
-
-    def psi(self, mu, s):
-        return ops.qx_psi_stats_batched(self.z, mu, s, self.gamma, self.alpha, self.zfac)
-
-    def evaluate(self, mu, s, grad=False):
-        """f_hat* summed over the B kernels (0-d tensor); with grad, also d f_hat* / d(mu, s).  self.terms: [B x 5] per-kernel
-        terms (the five summands above), self.info: failed factorisations of A (0 = fine)."""
-        be, n_t, dd = self.beta, self.n_t, self.dims
-        psi_1, psi_2 = self.psi(mu, s)
-        tm = ops.matmul(ops.matmul(self.li, psi_2), self.li.transpose(1, 2))
-        l_a, self.info = ops.potrf_batched(be[:, None, None] * tm + self.eye)
-        r0 = ops.matmul(ops.tril_inverse_batched(l_a), self.li)
-        u = ops.matmul(r0, ops.matmul(psi_1.transpose(1, 2), self.y))                       # [B, M, Dmax]
-        logdet = torch.sum(torch.log(torch.diagonal(l_a, dim1=-2, dim2=-1)), dim=-1)
-        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
-        self.terms = torch.stack([0.5 * n_t * dd * (torch.log(be) - math.log(2.0 * math.pi)), -dd * logdet,
-                                  0.5 * dd * be * (tr - self.alpha * n_t), 0.5 * be * be * torch.sum(u * u, dim=(1, 2)),
-                                  -0.5 * be * self.yy], dim=1)
-        f = torch.sum(self.terms)
-        if not grad:
-            return f, psi_1, psi_2
-        r = ops.matmul(r0.transpose(1, 2), u)                                                  # [B, M, Dmax]
-        p = ops.matmul(r0.transpose(1, 2), r0)
-        g2 = (0.5 * dd * be)[:, None, None] * (self.kinv - p) - (0.5 * be ** 3)[:, None, None] * ops.matmul(r, r.transpose(1, 2))
-        g1 = (be * be)[:, None, None] * ops.matmul(self.y, r.transpose(1, 2))                # [B, N*, M]
-        d_mu, d_s = ops.qx_psi_adjoint(self.z, mu, s, self.gamma, self.alpha, g1, g2, self.zfac)
-        return f, d_mu, d_s
 
 
 def _kl_test(mu, s):
@@ -446,6 +375,28 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         pred_state['bound'] = bound
         return bound
 
+    def _masked(y_test, observed, predict=False, reference_compat=False):
+        return _missing.masked_arguments(y_test, observed, num_dimensions, predict, reference_compat)
+
+    def _masked_bound(y0, obs):
+        """The test bound whose slots are the column groups of the mask that share one row pattern; all share the one kernel."""
+        groups = _missing.group_columns_by_pattern(obs)
+        dmax = max(len(c) for c, _ in groups)
+        y = np.zeros((len(groups), y0.shape[0], dmax))
+        for i, (cols, _) in enumerate(groups):
+            y[i, :, :len(cols)] = y0[:, cols]
+        z, g, a, b = _frozen()
+        bound = _TestBound.slots(z[0], g[0], a[0], b[0], _as_device(y, dev_), [len(c) for c, _ in groups],
+                                 _as_device(np.stack([w for _, w in groups]), dev_), dev_)
+        pred_state['bound'] = bound
+        pred_state['missing_columns'] = _missing.missing_columns(obs)
+        return bound
+
+    def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
+        if x_test_mean is None and not use_pca:
+            x_test_mean = _missing.masked_nearest_neighbour_init(y_np, y0, obs, raw['x_mean'].detach().cpu().numpy())
+        return _init_test_latents(None, y0, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
+
     def _check_observed(y_test, full):
         y_test = np.asarray(y_test, dtype=np.float64)
         assert y_test.ndim == 2 and y_test.shape[0] >= 1, 'y_test must be [N* x D]'
@@ -470,22 +421,31 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             kl_t = ops.kl_qx(xt, st_)
         return f_hat, kl, f_test, kl_t
 
-    def _test_latent_gradients(y_test, x_test_mean, x_test_var):
-        y_test = np.asarray(y_test, dtype=np.float64)
-        assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
-        bound = _test_bound(y_test)
+    def _test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
+        if observed is not None:
+            bound = _masked_bound(*_masked(y_test, observed))
+        else:
+            y_test = np.asarray(y_test, dtype=np.float64)
+            assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
+            bound = _test_bound(y_test)
         xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
         with torch.no_grad():
             _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
             _, k_mu, k_s = _kl_test(xt, st_)
         return d_mu - k_mu, d_s - k_s
 
-    def _optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None, x_test_var=None):
-        y_test = np.asarray(y_test, dtype=np.float64)
-        assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
-        xt, st_ = _init_test_latents(y_np[:, :y_test.shape[1]], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean,
-                                     x_test_var, dev_)
-        bound = _test_bound(y_test)
+    def _optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None, x_test_var=None,
+                               observed=None):
+        if observed is not None:
+            y0, obs = _masked(y_test, observed)
+            xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+            bound = _masked_bound(y0, obs)
+        else:
+            y_test = np.asarray(y_test, dtype=np.float64)
+            assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
+            xt, st_ = _init_test_latents(y_np[:, :y_test.shape[1]], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean,
+                                         x_test_var, dev_)
+            bound = _test_bound(y_test)
 
         def grad_fn(mu, s):
             _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
@@ -515,14 +475,39 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), f_test - f_hat
 
         @staticmethod
-        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
+                                 observed=None):
             """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
                 (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
             for the remaining Du = D - Do dims, at the initial q(X*) of predict_new_latent_variables (nearest neighbour over
             the observed dims).  The predictive moments are the reference's (:495-536), composed of the library's operators;
-            reference_compat: as predict_new_latent_variables (no effect)."""
+            reference_compat: as predict_new_latent_variables (no effect).
+
+            observed (extension): a boolean [N* x D] mask of the entries of y_test [N* x D] that were measured, any pattern
+            (entries where it is False are ignored and may be NaN).  The bound is f_hat + f_hat*(masked) - KL(q(X)) - KL(q(X*)):
+            output dim d enters f_hat* with the test points at which it was measured (columns of one row pattern share a slot
+            of the weighted test-point operators); KL(q(X*)) runs over all N* rows.  The Du predicted dims are then the columns
+            with at least one unobserved entry, ascending (property missing_columns); their moments are the same formulas and
+            depend on the mask only through q(X*), which starts at the masked nearest neighbour (smallest mean squared
+            difference over each row's observed columns; a row with nothing observed starts at 0).  AssertionError for a
+            non-boolean mask, a shape mismatch, a mask that is True everywhere, or reference_compat=True."""
+            if observed is not None:
+                y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
+                xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+                bound = _masked_bound(y0, obs)
+                mc = pred_state['missing_columns']
+                with torch.no_grad():
+                    f_test, _, _ = bound.evaluate(xt, st_)
+                    f_hat, kl = _train_terms()
+                    kl_t = ops.kl_qx(xt, st_)
+                    z, g, a, b = _frozen()
+                    plain = _TestBound(z, g, a, b, [torch.zeros((y0.shape[0], 1), dtype=TORCH_DTYPE, device=dev_)], dev_)
+                    means, covars = _predictive_moments(plain, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
+                                                        [_as_device(y_np[:, mc], dev_)], xt, st_)
+                return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covars[0]
             y_test = _check_observed(y_test, False)
             do = y_test.shape[1]
+            pred_state['missing_columns'] = np.arange(do, num_dimensions)
             xt, st_ = _init_test_latents(y_np[:, :do], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var,
                                          dev_)
             f_hat, kl, f_test, kl_t = _bound_at(y_test, xt, st_)
@@ -533,23 +518,29 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covars[0]
 
         @staticmethod
-        def test_latent_gradients(y_test, x_test_mean, x_test_var):
+        def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
             """d(f_hat* - KL(q(X*))) / d(x_test_mean, x_test_var) [N* x Q] each — the gradient of either prediction bound with
             respect to q(X*) (mean and diagonal variances), the trained model fixed; y_test [N* x Do], Do <= D (the first Do
-            output dims).  One qx_psi_stats_batched + dense chain + qx_psi_adjoint, fp64."""
-            return _test_latent_gradients(y_test, x_test_mean, x_test_var)
+            output dims).  One qx_psi_stats_batched + dense chain + qx_psi_adjoint, fp64.  observed: as predict_missing_data
+            (y_test [N* x D]; True everywhere is allowed here)."""
+            return _test_latent_gradients(y_test, x_test_mean, x_test_var, observed)
 
         @staticmethod
         def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
-                                  x_test_var=None):
+                                  x_test_var=None, observed=None):
             """Adam on q(X*) (the mean and softplus-parametrised variances) maximising f_hat* - KL(q(X*)) for test points
             observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*.  K_uu and its factor
-            are formed once; no host synchronisation inside the loop."""
-            return _optimise_test_latents(y_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var)
+            are formed once; no host synchronisation inside the loop.  observed: as predict_missing_data."""
+            return _optimise_test_latents(y_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var, observed)
+
+        @property
+        def missing_columns(self):
+            """The output dims whose moments the last predict_missing_data returned (ascending), or None."""
+            return pred_state.get('missing_columns')
 
         @property
         def prediction_terms(self):
-            """[1 x 5] terms of f_hat* in the last prediction evaluation: 1/2 N* D (log beta - log 2 pi), -D log|L_A|,
+            """[slots x 5] terms of f_hat* in the last prediction evaluation: 1/2 N* D (log beta - log 2 pi), -D log|L_A|,
             1/2 D beta (tr(K_uu^-1 Psi2*) - alpha N*), 1/2 beta^2 |C* Y*|^2, -1/2 beta |Y*|^2."""
             b = pred_state.get('bound')
             return None if b is None else b.terms

@@ -115,6 +115,15 @@ def _qx_args(z, mu, s, gamma, alpha, zfac):
     return z, mu, s, gamma, alpha, zfac, b, mu.shape[0], m, q
 
 
+def _qx_weights(weights, b, n, ref):
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or not weights.is_contiguous():
+        raise TypeError('weights must be a contiguous float64 torch.Tensor')
+    if weights.device != ref.device:
+        raise RuntimeError('weights must live on the device of the inputs')
+    assert tuple(weights.shape) == (b, n), 'weights must be [B x N*]'
+    return weights
+
+
 def qx_pair_factor(z, gamma, alpha):
     """The q(X*)-independent factor of Psi2 per kernel, alpha_b^2 exp(-1/4 sum_q gamma_bq (z_bm - z_bm')^2) [B,M,M], as the gram
     of z_b with gamma_b / 2 and alpha_b^2 (one dpgp_ard_rbf_gram_f64 per kernel; formed once while Z is frozen)."""
@@ -127,16 +136,24 @@ def qx_pair_factor(z, gamma, alpha):
                       for b in range(z.shape[0])]).contiguous()
 
 
-def qx_psi_stats_batched(z, mu, s, gamma, alpha, zfac=None):
+def qx_psi_stats_batched(z, mu, s, gamma, alpha, zfac=None, weights=None):
     """Psi1 [B,N*,M] and Psi2 [B,M,M] of q(X*) = (mu, s) [N*,Q] for B kernels with their own inducing inputs z [B,M,Q],
     gamma [B,Q], alpha [B] (rbf_kernel.py:135-199), fp64 (dpgp_qx_psi_stats_batched_f64).  zfac: qx_pair_factor(z, gamma, alpha)
-    or None (computed in the kernels)."""
+    or None (computed in the kernels).  weights: None, or [B,N*] fp64 contiguous on the inputs' device: Psi2_b becomes
+    sum_n weights[b,n] (test point n's term) (dpgp_qx_psi_stats_weighted_f64; Psi1 is not weighted)."""
     z, mu, s, gamma, alpha, zfac, b, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
     psi_1 = torch.empty((b, n, m), dtype=torch.float64, device=mu.device)
     psi_2 = torch.empty((b, m, m), dtype=torch.float64, device=mu.device)
     l = _lib.lib()
     wsb = l.dpgp_qx_psi_stats_workspace_bytes(b, n, m, q)
     ws = _ws(wsb, mu.device)
+    if weights is not None:
+        weights = _qx_weights(weights, b, n, mu)
+        _lib.check(l.dpgp_qx_psi_stats_weighted_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                    alpha.data_ptr(), None if zfac is None else zfac.data_ptr(),
+                                                    weights.data_ptr(), psi_1.data_ptr(), psi_2.data_ptr(), ws.data_ptr(), wsb,
+                                                    _stream()), 'dpgp_qx_psi_stats_weighted_f64')
+        return psi_1, psi_2
     _lib.check(l.dpgp_qx_psi_stats_batched_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
                                                alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), psi_1.data_ptr(),
                                                psi_2.data_ptr(), ws.data_ptr(), wsb, _stream()),
@@ -144,10 +161,11 @@ def qx_psi_stats_batched(z, mu, s, gamma, alpha, zfac=None):
     return psi_1, psi_2
 
 
-def qx_psi_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None):
+def qx_psi_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None, weights=None):
     """(d_mu, d_s) [N*,Q]: the adjoints g1 = dF/dPsi1 [B,N*,M] and g2 = dF/dPsi2 [B,M,M] of the B kernels of
     qx_psi_stats_batched contracted with dPsi/d(mu, s), summed over the kernels (dpgp_qx_psi_adjoint_f64; fixed summation
-    order, the same bits on every run)."""
+    order, the same bits on every run).  weights: as qx_psi_stats_batched; the Psi2 part of test point n from kernel b is
+    multiplied by weights[b,n], the Psi1 part is governed by g1 alone (dpgp_qx_psi_adjoint_weighted_f64)."""
     z, mu, s, gamma, alpha, zfac, b, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
     g1, g2 = _prep(g1, torch.float64, 'g1'), _prep(g2, torch.float64, 'g2')
     assert tuple(g1.shape) == (b, n, m) and tuple(g2.shape) == (b, m, m), 'g1 must be [B x N* x M], g2 [B x M x M]'
@@ -156,6 +174,14 @@ def qx_psi_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None):
     l = _lib.lib()
     wsb = l.dpgp_qx_psi_adjoint_workspace_bytes(b, n, m, q)
     ws = _ws(wsb, mu.device)
+    if weights is not None:
+        weights = _qx_weights(weights, b, n, mu)
+        _lib.check(l.dpgp_qx_psi_adjoint_weighted_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                      alpha.data_ptr(), None if zfac is None else zfac.data_ptr(),
+                                                      weights.data_ptr(), g1.data_ptr(), g2.data_ptr(), d_mu.data_ptr(),
+                                                      d_s.data_ptr(), ws.data_ptr(), wsb, _stream()),
+                   'dpgp_qx_psi_adjoint_weighted_f64')
+        return d_mu, d_s
     _lib.check(l.dpgp_qx_psi_adjoint_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
                                          alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), g1.data_ptr(),
                                          g2.data_ptr(), d_mu.data_ptr(), d_s.data_ptr(), ws.data_ptr(), wsb, _stream()),

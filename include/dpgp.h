@@ -121,6 +121,15 @@ int dpgp_ard_rbf_gram_grad_f64(int N, int Q, const double *x, const double *gamm
  *      d_mu[N][Q] = sum_b sum_m g1_b[n,m] dPsi1_b[n,m]/dmu[n,q] + sum_b sum_{m,m'} g2_b[m,m'] dPsi2_b[m,m']/dmu[n,q],  d_s
  *      likewise (the derivatives with respect to the variances s, not their softplus parameters).  No z / gamma / alpha
  *      outputs.  ws: dpgp_qx_psi_adjoint_workspace_bytes(B,N,M,Q).
+ *   dpgp_qx_psi_stats_weighted_f64 / dpgp_qx_psi_adjoint_weighted_f64:  the same with a weight per (kernel, test point),
+ *      w[B][N] (any finite values; NULL = all ones, which runs the unweighted kernels and gives the unweighted bits):
+ *      psi2[b] = sum_n w[b][n] (test point n's Psi2 term of kernel b), still exactly symmetric; psi1 is not weighted.  The
+ *      adjoint multiplies the Psi2 part of test point n's (d_mu, d_s) from kernel b by w[b][n]; the Psi1 part is governed by
+ *      g1 alone (zero the rows of g1 that must not count).  A weight of 0 contributes exactly 0.0 and costs no exponential
+ *      in the stats kernel; in the adjoint a wave of 64 consecutive test points whose weights for kernel b are all 0 skips
+ *      its pair loops.  w is nullable like zfac and follows it, so the negative bad-argument codes, the order of the checks
+ *      and the workspace sizes are those of the unweighted functions.  (An output dim observed at a subset of the test
+ *      points is a kernel b with w[b][n] = 1 where it was measured: per-entry missing-data masks.)
  *   The workspace queries are host functions (0 for a shape out of range). */
 #define DPGP_QX_PSI_MAX_Q 64
 size_t dpgp_qx_psi_stats_workspace_bytes(int B, int N, int M, int Q);
@@ -131,6 +140,13 @@ size_t dpgp_qx_psi_adjoint_workspace_bytes(int B, int N, int M, int Q);
 int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s, const double *gamma,
                             const double *alpha, const double *zfac, const double *g1, const double *g2, double *d_mu, double *d_s,
                             void *ws, size_t ws_bytes, void *stream);
+int dpgp_qx_psi_stats_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                   const double *gamma, const double *alpha, const double *zfac, const double *w, double *psi1,
+                                   double *psi2, void *ws, size_t ws_bytes, void *stream);
+int dpgp_qx_psi_adjoint_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                     const double *gamma, const double *alpha, const double *zfac, const double *w,
+                                     const double *g1, const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes,
+                                     void *stream);
 
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
