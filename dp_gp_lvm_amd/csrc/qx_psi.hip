@@ -23,6 +23,16 @@
 //            A lane keeps the accumulators of one chunk of up to 8 latent dims in registers; the exponent runs over all Q.
 //            The Psi1 term is evaluated by the workgroup whose slab holds the diagonal tile of the column block.  Partial
 //            (d_mu, d_s) go to slab [slab][b]; a second launch adds them in b order, then slab order.
+//   parameter adjoint (d/dz_b, d/dgamma_b, d/dalpha_b per kernel b; the closed forms are in include/dpgp.h): the outputs reduce
+//            over n, so the Psi2 term has the stats kernel's layout: workgroup (pair tile, n slab, (b, chunk of 4 latent dims)),
+//            256 threads = 32 columns x 8 row groups, 4 pairs each, the slab's points staged 32 at a time as [32][Q][4] =
+//            (mu, gamma / w2, 1 / w2, s / w2).  Per (point, pair): one exponential over all Q, then for the chunk's dims
+//            sum a d2 / w2 and sum a (s / w2 + d2^2 / w2^2) in registers (a = weighted pair factor x c2_n x exp).  At the end the
+//            tile's pairs give, per dim, a row-side and a column-side d_z sum (through two [32][33] LDS tiles, added in index
+//            order) and a block-wide d_gamma / d_alpha sum (a fixed binary tree), written to the cell (slab, b, tile) of the
+//            workspace.  The Psi1 term is its own launch: workgroup (32 inducing points, n slab, b); per step a1 = g1 Psi1
+//            [32][33] with one exponential per (n, m), then the items (m, q) add over the step's points into LDS accumulators.
+//            A last launch adds the cells in a fixed order.  The z tiles have the odd row stride Q | 1 (lane = column reads).
 // No atomics anywhere: the same inputs give the same bits.
 //
 // Weighted forms (per-entry observation masks): wt [B][N] multiplies test point n's Psi2 term of kernel b (c2_n in both
@@ -30,6 +40,7 @@
 // are the code of the unweighted entry points, and wt == NULL runs them.  A point of weight 0 costs no exponential: the
 // stats kernel skips it in its staged-point loop (a workgroup-uniform branch on the staged weight), the adjoint skips a
 // tile's pair loop when all 64 points of the wave have weight 0 for kernel b.  Either way its contribution is exactly 0.
+// The parameter adjoint skips a point of weight 0 as the stats kernel does, on its staged weight; its Psi1 term is not weighted.
 #include "internal.h"
 
 #define QP_TILE 32
@@ -37,6 +48,7 @@
 #define QP_NT 64           // test points per adjoint workgroup (one wave)
 #define QP_SN 32           // test points staged per step of the stats kernel
 #define QP_QCHUNK 8        // latent dims per adjoint accumulator chunk
+#define QP_PCHUNK 4        // latent dims per parameter-adjoint accumulator chunk
 #define QP_TARGET_WGS 1024
 
 namespace {
@@ -335,6 +347,300 @@ __global__ __launch_bounds__(256) void qp_adjoint_reduce_kernel(int B, int N, in
     else d_s[(size_t)n * Q + (kq - Q)] = acc;
 }
 
+// ---- parameter adjoint, Psi2 term: (pair tile, n slab, b * qchunks + chunk); layout in the header comment
+// sum of v over the 256 threads of the workgroup, added as a fixed binary tree in LDS (red [256])
+__device__ __forceinline__ double qp_block_sum(double v, double *red, int t) {
+    red[t] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+template <int KQ, bool WEIGHTED>
+__global__ __launch_bounds__(256) void qp_param_kernel(int B, int N, int M, int Q, int T, int n_per_slab,
+                                                       const double *__restrict__ z, const double *__restrict__ mu,
+                                                       const double *__restrict__ s, const double *__restrict__ gamma,
+                                                       const double *__restrict__ alpha, const double *__restrict__ zfac,
+                                                       const double *__restrict__ wt, const double *__restrict__ g2,
+                                                       double *__restrict__ part) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int ZS = Q | 1;                                   // odd row stride of the z tiles: lane = column reads hit 32 banks
+    double *sp = reinterpret_cast<double *>(smem_raw);    // staged points [QP_SN][Q][4]: mu, gamma / w2, 1 / w2, s / w2
+    double *sc = sp + (size_t)QP_SN * Q * 4;                // [QP_SN] wt c2_n
+    double *zt = sc + QP_SN;                                // [64][ZS]: rows of block I, then columns of block J
+    double *gm = zt + (size_t)2 * QP_TILE * ZS;             // [Q]
+    double *buf = gm + Q;                                   // [2][32][33] row- and column-side d_z terms, then [256]
+    const int t = threadIdx.x, slab = blockIdx.y;
+    const int qchunks = (Q + QP_PCHUNK - 1) / QP_PCHUNK;
+    const int b = blockIdx.z / qchunks, q0 = (blockIdx.z % qchunks) * QP_PCHUNK;
+    const int nq = min(QP_PCHUNK, Q - q0);
+    int I, J;
+    qp_tile_ij(blockIdx.x, T, I, J);
+    const bool diag = I == J;
+    const int m0 = I * QP_TILE, c0 = J * QP_TILE;
+    {
+        const double *zb = z + (size_t)b * M * Q;
+        for (int k = t; k < QP_TILE * Q; k += 256) {
+            const int r = k / Q, q = k % Q;
+            zt[r * ZS + q] = m0 + r < M ? zb[(size_t)(m0 + r) * Q + q] : 0.0;
+            zt[(QP_TILE + r) * ZS + q] = c0 + r < M ? zb[(size_t)(c0 + r) * Q + q] : 0.0;
+        }
+        for (int q = t; q < Q; q += 256) gm[q] = gamma[(size_t)b * Q + q];
+    }
+    const int c = t & 31, rg = t >> 5;
+    const double *zcc = zt + (size_t)(QP_TILE + c) * ZS;     // the thread's column
+    const double *zr0 = zt + (size_t)rg * ZS;                // its rows: zr0 + 8 k ZS
+    __syncthreads();
+    // weighted pair factor of the thread's four pairs: (G2[m,m'] + G2[m',m]) F off the diagonal, G2[m,m] F on it, 0 for a
+    // pair that is out of range or below the diagonal of a diagonal tile (such a pair then adds exact zeros everywhere)
+    double h[4];
+    {
+        const double *g2b = g2 + (size_t)b * M * M;
+        const double al = alpha[b];
+        const int mp = c0 + c;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = rg + 8 * k, m = m0 + r;
+            h[k] = 0.0;
+            if (m < M && mp < M && (!diag || c >= r)) {
+                const double w = m == mp ? g2b[(size_t)m * M + m] : g2b[(size_t)m * M + mp] + g2b[(size_t)mp * M + m];
+                h[k] = w * qp_pair_factor(zfac, b, M, Q, m, mp, zr0 + (size_t)8 * k * ZS, zcc, gm, al);
+            }
+        }
+    }
+    double p0[4], p1[4][KQ], p2[4][KQ];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        p0[k] = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < KQ; ++kk) p1[k][kk] = p2[k][kk] = 0.0;
+    }
+    const int n_hi = min(N, (slab + 1) * n_per_slab);
+    for (int nb = slab * n_per_slab; nb < n_hi; nb += QP_SN) {
+        const int nn = min(QP_SN, n_hi - nb);
+        __syncthreads();                                       // (previous step done with the staged points)
+        for (int k = t; k < nn * Q; k += 256) {
+            const int q = k % Q;
+            const double g = gm[q], sv = s[(size_t)nb * Q + k];
+            const double i2 = 1.0 / fma(2.0 * g, sv, 1.0);
+            sp[4 * k] = mu[(size_t)nb * Q + k];
+            sp[4 * k + 1] = g * i2;
+            sp[4 * k + 2] = i2;
+            sp[4 * k + 3] = sv * i2;
+        }
+        if (t < nn) {
+            const double wn = WEIGHTED ? wt[(size_t)b * N + nb + t] : 1.0;
+            const double *sn = s + (size_t)(nb + t) * Q;
+            if (WEIGHTED && wn == 0.0) {
+                sc[t] = 0.0;
+            } else {
+                double l = 0.0;
+                for (int q = 0; q < Q; ++q) l += log(fma(2.0 * gm[q], sn[q], 1.0));
+                sc[t] = WEIGHTED ? wn * exp(-0.5 * l) : exp(-0.5 * l);
+            }
+        }
+        __syncthreads();
+        // Psi2 term: one exponential per (point, pair), then the chunk's accumulators
+        for (int i = 0; i < nn; ++i) {
+            const double c2 = sc[i];
+            if (WEIGHTED && c2 == 0.0) continue;               // (the same LDS word for every thread: uniform)
+            const double *pi = sp + (size_t)i * Q * 4;
+            double a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double *zrr = zr0 + (size_t)8 * k * ZS;
+                double e = 0.0;
+                for (int q = 0; q < Q; ++q) {
+                    const double d = pi[4 * q] - 0.5 * (zrr[q] + zcc[q]);
+                    e = fma(pi[4 * q + 1] * d, d, e);
+                }
+                a[k] = h[k] * c2 * exp(-e);
+                p0[k] += a[k];
+            }
+#pragma unroll
+            for (int kk = 0; kk < KQ; ++kk)
+                if (kk < nq) {
+                    const int q = q0 + kk;
+                    const double mq = pi[4 * q], iv = pi[4 * q + 2], rs = pi[4 * q + 3], zcq = zcc[q];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const double di = (mq - 0.5 * (zr0[8 * k * ZS + q] + zcq)) * iv;
+                        p1[k][kk] = fma(a[k], di, p1[k][kk]);
+                        p2[k][kk] = fma(a[k], fma(di, di, rs), p2[k][kk]);
+                    }
+                }
+        }
+    }
+    // tile-level sums in a fixed order, one latent dim at a time; cell of the workspace: [2][32][Q] d_z sides, [Q], [1]
+    double *pz = part + (((size_t)slab * B + b) * gridDim.x + blockIdx.x) * ((size_t)2 * QP_TILE * Q + Q + 1);
+    double *bufb = buf + QP_TILE * QP_HSTRIDE, *red = bufb + QP_TILE * QP_HSTRIDE;
+#pragma unroll
+    for (int kk = 0; kk < KQ; ++kk)
+        if (kk < nq) {                                         // (uniform)
+            const int q = q0 + kk;
+            const double gq = gm[q];
+            double gv = 0.0;
+            __syncthreads();                                   // (previous dim's sums read)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int r = rg + 8 * k;
+                const double dz = zr0[8 * k * ZS + q] - zcc[q];
+                const double u = gq * p1[k][kk], hd = 0.5 * gq * dz * p0[k];
+                buf[r * QP_HSTRIDE + c] = u - hd;
+                bufb[r * QP_HSTRIDE + c] = u + hd;
+                gv -= fma(0.25 * dz * dz, p0[k], p2[k][kk]);
+            }
+            __syncthreads();
+            if (t < 32) {
+                double acc = 0.0;
+                for (int cc = 0; cc < QP_TILE; ++cc) acc += buf[t * QP_HSTRIDE + cc];
+                pz[(size_t)t * Q + q] = acc;
+            } else if (t < 64) {
+                double acc = 0.0;
+                for (int r = 0; r < QP_TILE; ++r) acc += bufb[r * QP_HSTRIDE + (t - 32)];
+                pz[(size_t)t * Q + q] = acc;
+            }
+            const double tot = qp_block_sum(gv, red, t);
+            if (t == 0) pz[(size_t)2 * QP_TILE * Q + q] = tot;
+        }
+    if (q0 == 0) {                                             // alpha: 2 <g2, Psi2>, by the first chunk
+        const double tot = qp_block_sum(2.0 * ((p0[0] + p0[1]) + (p0[2] + p0[3])), red, t);
+        if (t == 0) pz[(size_t)2 * QP_TILE * Q + Q] = tot;
+    }
+}
+
+// ---- parameter adjoint, Psi1 term: (block of 32 inducing points, n slab, b).  Per step of 32 staged points the threads
+// (inducing point c, points rg + 8 j) form a1 = g1 Psi1 [32][33] with one exponential each, then the items (m, q) of the block
+// (thread t owns t, t + 256, ..) add a1 d / w1 and a1 (s / w1 + d^2 / w1^2) over the step's points into their LDS accumulators
+__global__ __launch_bounds__(256) void qp_param_psi1_kernel(int B, int N, int M, int Q, int n_per_slab, const double *__restrict__ z,
+                                                            const double *__restrict__ mu, const double *__restrict__ s,
+                                                            const double *__restrict__ gamma, const double *__restrict__ alpha,
+                                                            const double *__restrict__ g1, double *__restrict__ part) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int ZS = Q | 1;
+    double *sp = reinterpret_cast<double *>(smem_raw);    // staged points [QP_SN][Q][3]: mu, 1 / w1, s / w1
+    double *sc = sp + (size_t)QP_SN * Q * 3;                // [QP_SN] alpha c1_n
+    double *zt = sc + QP_SN;                                // [32][ZS]
+    double *gm = zt + (size_t)QP_TILE * ZS;                 // [Q]
+    double *sa = gm + Q;                                    // [QP_SN][33] a1 of the step
+    double *acc1 = sa + QP_SN * QP_HSTRIDE;                 // [32][Q]
+    double *acc2 = acc1 + (size_t)QP_TILE * Q;              // [32][Q]
+    double *red = acc2 + (size_t)QP_TILE * Q;               // [256]
+    const int t = threadIdx.x, slab = blockIdx.y, b = blockIdx.z, m0 = blockIdx.x * QP_TILE;
+    const double *zb = z + (size_t)b * M * Q;
+    for (int k = t; k < QP_TILE * Q; k += 256) {
+        const int r = k / Q, q = k % Q;
+        zt[r * ZS + q] = m0 + r < M ? zb[(size_t)(m0 + r) * Q + q] : 0.0;
+        acc1[k] = acc2[k] = 0.0;
+    }
+    for (int q = t; q < Q; q += 256) gm[q] = gamma[(size_t)b * Q + q];
+    const int c = t & 31, rg = t >> 5;
+    const double *zcc = zt + (size_t)c * ZS;
+    double t0 = 0.0;
+    const int n_hi = min(N, (slab + 1) * n_per_slab);
+    for (int nb = slab * n_per_slab; nb < n_hi; nb += QP_SN) {
+        const int nn = min(QP_SN, n_hi - nb);
+        __syncthreads();                                       // (previous step done with the staged points and a1)
+        for (int k = t; k < nn * Q; k += 256) {
+            const double sv = s[(size_t)nb * Q + k], i1 = 1.0 / fma(gm[k % Q], sv, 1.0);
+            sp[3 * k] = mu[(size_t)nb * Q + k];
+            sp[3 * k + 1] = i1;
+            sp[3 * k + 2] = sv * i1;
+        }
+        if (t < nn) {
+            const double *sn = s + (size_t)(nb + t) * Q;
+            double l = 0.0;
+            for (int q = 0; q < Q; ++q) l += log(fma(gm[q], sn[q], 1.0));
+            sc[t] = alpha[b] * exp(-0.5 * l);
+        }
+        __syncthreads();
+        for (int i = rg; i < nn; i += 8) {
+            double a1 = 0.0;
+            if (m0 + c < M) {
+                const double *pi = sp + (size_t)i * Q * 3;
+                double e = 0.0;
+                for (int q = 0; q < Q; ++q) {
+                    const double d = pi[3 * q] - zcc[q];
+                    e = fma(gm[q] * pi[3 * q + 1] * d, d, e);
+                }
+                a1 = g1[((size_t)b * N + nb + i) * M + m0 + c] * sc[i] * exp(-0.5 * e);
+            }
+            sa[i * QP_HSTRIDE + c] = a1;
+            t0 += a1;
+        }
+        __syncthreads();
+        for (int k = t; k < QP_TILE * Q; k += 256) {
+            const int r = k / Q, q = k % Q;
+            const double zq = zt[r * ZS + q];
+            double u1 = 0.0, u2 = 0.0;
+            for (int i = 0; i < nn; ++i) {
+                const double *pq = sp + ((size_t)i * Q + q) * 3;
+                const double a1 = sa[i * QP_HSTRIDE + r], di = (pq[0] - zq) * pq[1];
+                u1 = fma(a1, di, u1);
+                u2 = fma(a1, fma(di, di, pq[2]), u2);
+            }
+            acc1[k] += u1;
+            acc2[k] += u2;
+        }
+    }
+    __syncthreads();
+    // cell of the workspace: [32][Q] d_z, [Q] d_gamma, [1] <g1, Psi1>
+    double *pz = part + (((size_t)slab * B + b) * gridDim.x + blockIdx.x) * ((size_t)QP_TILE * Q + Q + 1);
+    for (int k = t; k < QP_TILE * Q; k += 256) pz[k] = gm[k % Q] * acc1[k];
+    for (int q = t; q < Q; q += 256) {
+        double a = 0.0;
+        for (int r = 0; r < QP_TILE; ++r) a += acc2[r * Q + q];
+        pz[(size_t)QP_TILE * Q + q] = -0.5 * a;
+    }
+    const double tot = qp_block_sum(t0, red, t);
+    if (t == 0) pz[(size_t)QP_TILE * Q + Q] = tot;
+}
+
+// d_z[b][m][q]: over slabs, the column sides of the tiles (I, block of m), I ascending, then the row sides of the tiles
+// (block of m, J), J ascending, then the Psi1 slabs; d_gamma[b][q] and d_alpha[b]: over slabs, then tiles, then the Psi1 cells
+__global__ __launch_bounds__(256) void qp_param_reduce_kernel(int B, int M, int Q, int T, int slabs,
+                                                              int slabs1, const double *__restrict__ alpha,
+                                                              const double *__restrict__ part, const double *__restrict__ part1,
+                                                              double *__restrict__ d_z, double *__restrict__ d_gamma,
+                                                              double *__restrict__ d_alpha) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t nz = (size_t)B * M * Q, ng = (size_t)B * Q;
+    const size_t tiles = (size_t)T * (T + 1) / 2, side = (size_t)QP_TILE * Q, cell = 2 * side + Q + 1, cell1 = side + Q + 1;
+    if (e < nz) {
+        const int b = (int)(e / ((size_t)M * Q)), rem = (int)(e % ((size_t)M * Q)), m = rem / Q, q = rem % Q;
+        const int bm = m / QP_TILE;
+        const size_t off = (size_t)(m % QP_TILE) * Q + q;
+        double acc = 0.0;
+        for (int k = 0; k < slabs; ++k) {
+            const size_t base = ((size_t)k * B + b) * tiles;
+            for (int i = 0; i <= bm; ++i) {
+                const size_t idx = (size_t)i * T - (size_t)(i * (i - 1) / 2) + (bm - i);
+                acc += part[(base + idx) * cell + side + off];
+            }
+            const size_t row = (size_t)bm * T - (size_t)(bm * (bm - 1) / 2);
+            for (int j = bm; j < T; ++j) acc += part[(base + row + (j - bm)) * cell + off];
+        }
+        for (int k = 0; k < slabs1; ++k) acc += part1[(((size_t)k * B + b) * T + bm) * cell1 + off];
+        d_z[e] = acc;
+    } else if (e < nz + ng + B) {                              // d_gamma[b][q], then d_alpha[b] (times alpha: the last entry)
+        const bool isa = e >= nz + ng;
+        const int b = isa ? (int)(e - nz - ng) : (int)((e - nz) / Q);
+        const size_t off = 2 * side + (isa ? (size_t)Q : (e - nz) % Q);
+        double acc = 0.0;
+        for (int k = 0; k < slabs; ++k)
+            for (size_t i = 0; i < tiles; ++i) acc += part[(((size_t)k * B + b) * tiles + i) * cell + off];
+        for (int k = 0; k < slabs1; ++k)
+            for (int i = 0; i < T; ++i) acc += part1[(((size_t)k * B + b) * T + i) * cell1 + off - side];
+        if (isa) d_alpha[b] = acc / alpha[b];
+        else d_gamma[e - nz] = acc;
+    }
+}
+
 struct QpStatsPlan { int T, tiles, slabs, n_per_slab; };
 QpStatsPlan qp_stats_plan(int B, int N, int M) {
     QpStatsPlan p;
@@ -361,6 +667,36 @@ QpAdjPlan qp_adj_plan(int B, int N, int M, int Q) {
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, sl);
     p.slabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);
     return p;
+}
+
+// parameter adjoint: n slabs so that tiles x slabs x B x q chunks fills the GPU (256-thread workgroups, as the stats plan)
+struct QpParamPlan { int T, tiles, qchunks, slabs, n_per_slab, slabs1, n_per_slab1; };
+QpParamPlan qp_param_plan(int B, int N, int M, int Q) {
+    QpParamPlan p;
+    p.T = dpgp_ceil_div(M, QP_TILE);
+    p.tiles = qp_tiles(M);
+    p.qchunks = dpgp_ceil_div(Q, QP_PCHUNK);
+    const int chunks = dpgp_ceil_div(N, QP_SN);
+    const long base = (long)p.tiles * B * p.qchunks;
+    int sl = (int)((QP_TARGET_WGS / 2 + base - 1) / base);
+    sl = sl < 1 ? 1 : (sl > chunks ? chunks : sl);
+    p.n_per_slab = dpgp_ceil_div(chunks, sl) * QP_SN;
+    p.slabs = dpgp_ceil_div(N, p.n_per_slab);
+    sl = dpgp_ceil_div(QP_TARGET_WGS / 2, p.T * B);             // (the Psi1 term: blocks of 32 inducing points x slabs x B)
+    sl = sl < 1 ? 1 : (sl > chunks ? chunks : sl);
+    p.n_per_slab1 = dpgp_ceil_div(chunks, sl) * QP_SN;
+    p.slabs1 = dpgp_ceil_div(N, p.n_per_slab1);
+    return p;
+}
+// doubles per (slab, b, tile): the two d_z sides [2][32][Q], d_gamma [Q], d_alpha; per (Psi1 slab, b, block): one side
+size_t qp_param_part_elems(int Q) { return (size_t)2 * QP_TILE * Q + Q + 1; }
+size_t qp_param_part1_elems(int Q) { return (size_t)QP_TILE * Q + Q + 1; }
+size_t qp_param_psi1_lds(int Q) {
+    return sizeof(double) * ((size_t)3 * QP_SN * Q + QP_SN + (size_t)QP_TILE * (Q | 1) + Q + QP_SN * QP_HSTRIDE +
+                             (size_t)2 * QP_TILE * Q + 256);
+}
+size_t qp_param_lds(int Q) {
+    return sizeof(double) * ((size_t)4 * QP_SN * Q + QP_SN + (size_t)2 * QP_TILE * (Q | 1) + Q + 2 * QP_TILE * QP_HSTRIDE + 256);
 }
 
 size_t qp_stats_lds(int Q) { return sizeof(double) * ((size_t)2 * QP_SN * Q + QP_SN + (size_t)2 * QP_TILE * Q + Q); }
@@ -409,6 +745,28 @@ int qp_dispatch_adjoint(const QpAdjPlan &p, int B, int N, int M, int Q, const do
            : w <= 2 ? qp_launch_adjoint<2, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
            : w <= 4 ? qp_launch_adjoint<4, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st)
                     : qp_launch_adjoint<8, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part, st);
+}
+
+template <int KQ, bool WEIGHTED>
+int qp_launch_param(const QpParamPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                    const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g2,
+                    double *part, hipStream_t st) {
+    const size_t lds = qp_param_lds(Q);
+    if (qp_set_lds(reinterpret_cast<const void *>(qp_param_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL((qp_param_kernel<KQ, WEIGHTED>), dim3(p.tiles, p.slabs, B * p.qchunks), dim3(256), lds, st, B, N, M, Q,
+                       p.T, p.n_per_slab, z, mu, s, gamma, alpha, zfac, wt, g2, part);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
+
+template <bool WEIGHTED>
+int qp_dispatch_param(const QpParamPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                      const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g2,
+                      double *part, hipStream_t st) {
+    return Q <= 1   ? qp_launch_param<1, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g2, part, st)
+           : Q <= 2 ? qp_launch_param<2, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g2, part, st)
+                    : qp_launch_param<QP_PCHUNK, WEIGHTED>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g2, part, st);
 }
 
 bool qp_shape_ok(int B, int N, int M, int Q) {
@@ -508,4 +866,53 @@ extern "C" int dpgp_qx_psi_adjoint_f64(int B, int N, int M, int Q, const double 
                                        const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes, void *stream) {
     return dpgp_qx_psi_adjoint_weighted_f64(B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, g1, g2, d_mu, d_s, ws, ws_bytes,
                                             stream);
+}
+
+extern "C" size_t dpgp_qx_psi_param_adjoint_workspace_bytes(int B, int N, int M, int Q) {
+    if (!qp_shape_ok(B, N, M, Q)) return 0;
+    const QpParamPlan p = qp_param_plan(B, N, M, Q);
+    return sizeof(double) * ((size_t)p.slabs * B * p.tiles * qp_param_part_elems(Q) +
+                             (size_t)p.slabs1 * B * p.T * qp_param_part1_elems(Q));
+}
+
+// the adjoint of the weighted Psi statistics with respect to the kernels' own parameters, per kernel b (not summed over b)
+extern "C" int dpgp_qx_psi_param_adjoint_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu,
+                                                      const double *s, const double *gamma, const double *alpha,
+                                                      const double *zfac, const double *wt, const double *g1, const double *g2,
+                                                      double *d_z, double *d_gamma, double *d_alpha, void *ws, size_t ws_bytes,
+                                                      void *stream) {
+    if (B < 1) return -1;
+    if (N < 1) return -2;
+    if (M < 1) return -3;
+    if (Q < 1 || Q > DPGP_QX_PSI_MAX_Q) return -4;
+    if (!z) return -5;
+    if (!mu) return -6;
+    if (!s) return -7;
+    if (!gamma) return -8;
+    if (!alpha) return -9;
+    if (!g1) return -11;
+    if (!g2) return -12;
+    if (!d_z) return -13;
+    if (!d_gamma) return -14;
+    if (!d_alpha) return -15;
+    if (!ws) return -16;
+    if (ws_bytes < dpgp_qx_psi_param_adjoint_workspace_bytes(B, N, M, Q)) return -17;
+    hipStream_t st = (hipStream_t)stream;
+    const QpParamPlan p = qp_param_plan(B, N, M, Q);
+    double *part = static_cast<double *>(ws), *part1 = part + (size_t)p.slabs * B * p.tiles * qp_param_part_elems(Q);
+    const int rc = wt ? qp_dispatch_param<true>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, wt, g2, part, st)
+                      : qp_dispatch_param<false>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, g2, part, st);
+    if (rc) return rc;
+    const size_t lds1 = qp_param_psi1_lds(Q);
+    if (qp_set_lds(reinterpret_cast<const void *>(qp_param_psi1_kernel), lds1)) return DPGP_ERR_LAUNCH;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL(qp_param_psi1_kernel, dim3(p.T, p.slabs1, B), dim3(256), lds1, st, B, N, M, Q, p.n_per_slab1, z, mu, s, gamma,
+                       alpha, g1, part1);
+    DPGP_LAUNCH_CHECK();
+    const size_t tot = (size_t)B * M * Q + (size_t)B * Q + B;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL(qp_param_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, B, M, Q, p.T, p.slabs, p.slabs1,
+                       alpha, part, part1, d_z, d_gamma, d_alpha);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
 }

@@ -31,6 +31,7 @@ from .dp_gp_lvm import dp_gp_lvm_t
 from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .test_bound import _TestBound, _as_device
+from .masked_bound import MaskedBayesianGPLVM
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -302,12 +303,21 @@ def gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_DIMENSION
 
 def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_DIMENSIONS,
                     num_inducing_points=GP_LVM_DEFAULT_NUM_INDUCING_POINTS, num_latent_samples=0,
-                    device=None, precision=None, initial_values=None):
+                    device=None, precision=None, initial_values=None, observed=None):
     """
     :param y_train: [N x D] numpy array.  :param kernel: optional k_ard_rbf with batch size 1 whose hyper-parameter VALUES
     initialise the model's own trainable ones.  :param num_latent_dims: Q.  :param num_inducing_points: M (< N).
     :param num_latent_samples: must be 0 (closed-form psi statistics).
     Extensions: device, precision ('mixed' | 'f64'), initial_values (x_mean, x_var, x_u, gamma, alpha, beta: values).
+
+    observed (extension): a boolean [N x D] mask of the entries of y_train that were measured, any pattern with at least one
+    True (utils.missing.observed_mask(y) makes it; entries where it is False are ignored and may be NaN).  The model is then
+    the masked fp64 model (precision None or 'f64'): output dim d enters the bound with the rows at which it was measured,
+    columns of one row pattern share a slot of the weighted operators (models/masked_bound.py), a column never observed is
+    left out, a row never observed contributes only its KL.  The objective is -(sum_slots f_b - KL(q(X)) over all N rows +
+    hyper-prior); gradients() returns the same six raw variables.  x_mean defaults to the PCA of y_train with its gaps filled
+    by the columns' observed means.  impute_training_data() fills the gaps with the posterior mean; the test-point methods
+    work with the masked model's own training-side terms, except predict_missing_data (NotImplementedError).
     """
     num_samples, num_dimensions = np.shape(y_train)
     assert isinstance(num_latent_dims, int), 'Number of latent dimensions must be an integer.'
@@ -326,6 +336,11 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         iv.setdefault('alpha', hp[KernelHyperparameters.SIGNAL_VARIANCE].detach().cpu().numpy())
         iv.setdefault('beta', hp[KernelHyperparameters.NOISE_PRECISION].detach().cpu().numpy())
     q = num_latent_dims
+    train_obs = None
+    if observed is not None:
+        assert precision in (None, 'f64'), "with observed, precision must be None or 'f64' (the masked model is fp64)"
+        train_obs = _missing.check_observed(observed, (num_samples, num_dimensions))
+        assert train_obs.any(), 'observed must hold at least one True entry'
     inner_iv = dict(gamma_atoms=np.asarray(iv.get('gamma', np.full((1, q), GP_INIT_GAMMA)), dtype=np.float64).reshape(1, q),
                     alpha_atoms=np.asarray(iv.get('alpha', GP_INIT_ALPHA), dtype=np.float64).reshape(1, 1),
                     beta_atoms=np.asarray(iv.get('beta', GP_INIT_BETA), dtype=np.float64).reshape(1, 1),
@@ -334,9 +349,25 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
     for k in ('x_mean', 'x_u'):
         if k in iv:
             inner_iv[k] = iv[k]
-    inner = dp_gp_lvm_t(y_train, num_latent_dims=num_latent_dims, num_inducing_points=num_inducing_points, truncation_level=1,
-                        device=device, precision=precision, initial_values=inner_iv)
     names = ('x_mean', 'x_var', 'x_u', 'gamma_atoms', 'alpha_atoms', 'beta_atoms')
+    if train_obs is None:
+        inner = dp_gp_lvm_t(y_train, num_latent_dims=num_latent_dims, num_inducing_points=num_inducing_points,
+                            truncation_level=1, device=device, precision=precision, initial_values=inner_iv)
+    else:
+        # the same defaults as dp_gp_lvm_t's, from the PCA of the column-mean-filled data
+        dev_m = torch.device(device) if device is not None else default_device()
+        np.random.seed(seed=0)
+        x_init = np.asarray(inner_iv['x_mean'], dtype=np.float64) if 'x_mean' in inner_iv else \
+            pca(_missing.column_mean_filled(y_train, train_obs), num_latent_dimensions=q)
+        x_u0 = inner_iv['x_u'] if 'x_u' in inner_iv else np.random.permutation(x_init)[:num_inducing_points] + \
+            np.random.normal(loc=0.0, scale=0.01, size=(num_inducing_points, q))
+        pos = lambda key, shape: _as_device(inverse_softplus(np.asarray(inner_iv[key], dtype=np.float64).reshape(shape)), dev_m)
+        for k in ('gamma_atoms', 'alpha_atoms', 'beta_atoms', 'x_var'):
+            assert np.all(np.asarray(inner_iv[k]) > 0), 'Initial value must be positive.'
+        inner = MaskedBayesianGPLVM(_missing.zero_filled(y_train, train_obs), train_obs,
+                                    dict(x_mean=_as_device(x_init, dev_m, (num_samples, q)), x_var=pos('x_var', (num_samples, q)),
+                                         x_u=_as_device(x_u0, dev_m, (num_inducing_points, q)), gamma_atoms=pos('gamma_atoms', (1, q)),
+                                         alpha_atoms=pos('alpha_atoms', (1, 1)), beta_atoms=pos('beta_atoms', (1, 1))), dev_m)
     raw = {k: inner.raw[k] for k in names}
 
     def _gradients():
@@ -359,9 +390,17 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             if callback is not None:
                 callback(it)
 
-    y_np = np.asarray(y_train, dtype=np.float64)
+    y_np = np.asarray(y_train, dtype=np.float64) if train_obs is None else inner.y0       # (zero where unobserved)
     dev_ = inner.raw['x_mean'].device
     pred_state = {}
+
+    def _init_latents(do, y_test, use_pca, x_test_mean, x_test_var):
+        """q(X*) for test points observed in their first `do` output dims; on a mask-trained model the nearest neighbour
+        compares over the columns that the training row observed too."""
+        if train_obs is not None and x_test_mean is None and not use_pca:
+            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(
+                y_np[:, :do], train_obs[:, :do], y_test, np.ones(y_test.shape, dtype=bool), raw['x_mean'].detach().cpu().numpy())
+        return _init_test_latents(y_np[:, :do], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
 
     def _frozen():
         """The trained kernel as a B = 1 test bound's parameters (fp64 values of the raw variables)."""
@@ -393,7 +432,10 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         return bound
 
     def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
-        if x_test_mean is None and not use_pca:
+        if x_test_mean is None and not use_pca and train_obs is not None:
+            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(y_np, train_obs, y0, obs,
+                                                                           raw['x_mean'].detach().cpu().numpy())
+        elif x_test_mean is None and not use_pca:
             x_test_mean = _missing.masked_nearest_neighbour_init(y_np, y0, obs, raw['x_mean'].detach().cpu().numpy())
         return _init_test_latents(None, y0, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
 
@@ -443,8 +485,7 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         else:
             y_test = np.asarray(y_test, dtype=np.float64)
             assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
-            xt, st_ = _init_test_latents(y_np[:, :y_test.shape[1]], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean,
-                                         x_test_var, dev_)
+            xt, st_ = _init_latents(y_test.shape[1], y_test, use_pca, x_test_mean, x_test_var)
             bound = _test_bound(y_test)
 
         def grad_fn(mu, s):
@@ -470,7 +511,7 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             y_test (use_pca), or the given x_test_mean / x_test_var (values; variances 1 by default).  reference_compat: accepted
             for symmetry with dp_gp_lvm; the reference's B = 1 bound has no defect to reproduce, so both settings agree."""
             y_test = _check_observed(y_test, True)
-            xt, st_ = _init_test_latents(y_np, y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
+            xt, st_ = _init_latents(num_dimensions, y_test, use_pca, x_test_mean, x_test_var)
             f_hat, kl, f_test, kl_t = _bound_at(y_test, xt, st_)
             return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), f_test - f_hat
 
@@ -490,7 +531,13 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             with at least one unobserved entry, ascending (property missing_columns); their moments are the same formulas and
             depend on the mask only through q(X*), which starts at the masked nearest neighbour (smallest mean squared
             difference over each row's observed columns; a row with nothing observed starts at 0).  AssertionError for a
-            non-boolean mask, a shape mismatch, a mask that is True everywhere, or reference_compat=True."""
+            non-boolean mask, a shape mismatch, a mask that is True everywhere, or reference_compat=True.
+
+            On a model trained with observed= the per-pattern predictive moments are not built: NotImplementedError (the
+            training data's own gaps are filled by impute_training_data)."""
+            if train_obs is not None:
+                raise NotImplementedError('predict_missing_data is not built for a model trained with observed=: use '
+                                          'impute_training_data for the gaps of the training data')
             if observed is not None:
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
@@ -508,8 +555,7 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             y_test = _check_observed(y_test, False)
             do = y_test.shape[1]
             pred_state['missing_columns'] = np.arange(do, num_dimensions)
-            xt, st_ = _init_test_latents(y_np[:, :do], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var,
-                                         dev_)
+            xt, st_ = _init_latents(do, y_test, use_pca, x_test_mean, x_test_var)
             f_hat, kl, f_test, kl_t = _bound_at(y_test, xt, st_)
             bound = pred_state['bound']
             with torch.no_grad():
@@ -544,6 +590,20 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             1/2 D beta (tr(K_uu^-1 Psi2*) - alpha N*), 1/2 beta^2 |C* Y*|^2, -1/2 beta |Y*|^2."""
             b = pred_state.get('bound')
             return None if b is None else b.terms
+
+        @staticmethod
+        def impute_training_data():
+            """A model trained with observed=: y_train [N x D] with every unobserved entry (n, d) replaced by the posterior mean
+            beta Psi1[n,:] (K_uu + beta Psi2_d)^-1 Psi1^T y_d (Psi2_d and y_d over the rows at which d was observed); observed
+            entries as given, a never-observed column 0.  fp64 device tensor."""
+            assert train_obs is not None, 'impute_training_data needs a model trained with observed='
+            return inner.impute()
+
+        @property
+        def objective_terms(self):
+            """A model trained with observed=: the [slots x 5] terms of sum_slots f_b in the last evaluation (as prediction_terms,
+            with N_b for N*); None for a model trained on complete data."""
+            return None if train_obs is None else inner.bound.terms
 
         @property
         def kernel(self):

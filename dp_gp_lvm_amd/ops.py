@@ -189,6 +189,30 @@ def qx_psi_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None, weights=None):
     return d_mu, d_s
 
 
+def qx_psi_param_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None, weights=None):
+    """(d_z [B,M,Q], d_gamma [B,Q], d_alpha [B]): the adjoints g1 [B,N*,M] and g2 [B,M,M] of qx_psi_adjoint contracted with
+    dPsi/d(z_b, gamma_b, alpha_b) of the (weighted) statistics, PER KERNEL b, not summed over the kernels
+    (dpgp_qx_psi_param_adjoint_weighted_f64; the derivative of the complete Psi2, pair factor included: zfac is only its cached
+    value; fixed summation order, the same bits on every run).  weights: as qx_psi_stats_batched (None: all ones)."""
+    z, mu, s, gamma, alpha, zfac, b, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    g1, g2 = _prep(g1, torch.float64, 'g1'), _prep(g2, torch.float64, 'g2')
+    assert tuple(g1.shape) == (b, n, m) and tuple(g2.shape) == (b, m, m), 'g1 must be [B x N* x M], g2 [B x M x M]'
+    d_z = torch.empty((b, m, q), dtype=torch.float64, device=mu.device)
+    d_gamma = torch.empty((b, q), dtype=torch.float64, device=mu.device)
+    d_alpha = torch.empty(b, dtype=torch.float64, device=mu.device)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_param_adjoint_workspace_bytes(b, n, m, q)
+    ws = _ws(wsb, mu.device)
+    if weights is not None:
+        weights = _qx_weights(weights, b, n, mu)
+    _lib.check(l.dpgp_qx_psi_param_adjoint_weighted_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                        alpha.data_ptr(), None if zfac is None else zfac.data_ptr(),
+                                                        None if weights is None else weights.data_ptr(), g1.data_ptr(),
+                                                        g2.data_ptr(), d_z.data_ptr(), d_gamma.data_ptr(), d_alpha.data_ptr(),
+                                                        ws.data_ptr(), wsb, _stream()), 'dpgp_qx_psi_param_adjoint_weighted_f64')
+    return d_z, d_gamma, d_alpha
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

@@ -81,3 +81,39 @@ def masked_nearest_neighbour_init(y_train, y_test, observed, x_train_mean):
     idx = masked_nearest_neighbour(y_train, y_test, observed)
     init = np.where((idx >= 0)[:, None], x_train_mean[np.maximum(idx, 0)], 0.0)
     return init + np.random.normal(scale=0.01, size=init.shape)
+
+
+def column_mean_filled(y, observed):
+    """y with every unobserved entry replaced by the mean of its column's observed entries (0 for a column never observed):
+    the complete matrix whose PCA starts q(X) when bayesian_gp_lvm trains on data with missing entries."""
+    observed = np.asarray(observed)
+    y0 = zero_filled(y, observed)
+    count = observed.sum(axis=0)
+    mean = np.where(count > 0, y0.sum(axis=0) / np.maximum(count, 1), 0.0)
+    return np.where(observed, y0, mean[None, :])
+
+
+def jointly_observed_nearest_neighbour(y_train, train_observed, y_test, test_observed):
+    """For every test row, the index of the training row with the smallest mean squared difference over the columns observed
+    in BOTH rows; training rows that share no observed column with the test row are skipped; -1 for a test row with no
+    candidate (the nearest neighbour of a model trained on data with missing entries)."""
+    train_observed, test_observed = np.asarray(train_observed), np.asarray(test_observed)
+    y_train, y_test = zero_filled(y_train, train_observed), zero_filled(y_test, test_observed)
+    out = np.full(y_test.shape[0], -1, dtype=np.int64)
+    for n in range(y_test.shape[0]):
+        both = train_observed & test_observed[n][None, :]
+        count = both.sum(axis=1)
+        if not count.any():
+            continue
+        total = np.where(both, (y_train - y_test[n][None, :]) ** 2, 0.0).sum(axis=1)
+        out[n] = np.argmin(np.where(count > 0, total / np.maximum(count, 1), np.inf))
+    return out
+
+
+def jointly_observed_nearest_neighbour_init(y_train, train_observed, y_test, test_observed, x_train_mean):
+    """Initial q(X*) means [N* x Q] as masked_nearest_neighbour_init, from jointly_observed_nearest_neighbour's row (the prior
+    mean 0 for a test row with no candidate)."""
+    x_train_mean = np.asarray(x_train_mean, dtype=np.float64)
+    idx = jointly_observed_nearest_neighbour(y_train, train_observed, y_test, test_observed)
+    init = np.where((idx >= 0)[:, None], x_train_mean[np.maximum(idx, 0)], 0.0)
+    return init + np.random.normal(scale=0.01, size=init.shape)

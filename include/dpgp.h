@@ -130,6 +130,19 @@ int dpgp_ard_rbf_gram_grad_f64(int N, int Q, const double *x, const double *gamm
  *      its pair loops.  w is nullable like zfac and follows it, so the negative bad-argument codes, the order of the checks
  *      and the workspace sizes are those of the unweighted functions.  (An output dim observed at a subset of the test
  *      points is a kernel b with w[b][n] = 1 where it was measured: per-entry missing-data masks.)
+ *   dpgp_qx_psi_param_adjoint_weighted_f64:  the other half of the backward pass, for a model that trains its inducing inputs
+ *      and hyper-parameters through the (weighted) statistics.  With L = sum_b <g1_b, Psi1_b> + <g2_b, sum_n w[b][n] psi2_bn>
+ *      (g2 any matrix) the outputs are dL/dz_b  d_z[B][M][Q], dL/dgamma_b  d_gamma[B][Q] and dL/dalpha_b  d_alpha[B], PER KERNEL
+ *      b (not summed over b: a model whose slots share one kernel adds them).  The derivative is of the complete Psi2, pair
+ *      factor included; zfac is only a cached value of it (NULL computes it in the kernel), w == NULL means all ones.  With
+ *      d1 = mu_n - z_m, d2 = mu_n - (z_m + z_m') / 2, D = z_m - z_m', A1 = g1 Psi1, A2 = g2[m,m'] w[b][n] psi2_bn[m,m']:
+ *        d/dz_mq    = sum_n A1 iw1 d1 + sum_n sum_m' (A2[m,m'] + A2[m',m]) (-1/2 gamma_q D_q + iw2 d2_q)
+ *        d/dgamma_q = sum A1 (-1/2 s/w1 - 1/2 d1^2/w1^2) + sum A2 (-1/4 D_q^2 - s/w2 - d2_q^2/w2^2)
+ *        d/dalpha   = (<g1, Psi1> + 2 <g2, Psi2 weighted>) / alpha
+ *      A pair is visited once; a weight of 0 contributes exactly 0.0 to the Psi2 part and costs no exponential; partial sums
+ *      go through the workspace in a fixed order (no atomics: the same bits on every run).  Bad-argument codes -1 .. -12 are
+ *      those of dpgp_qx_psi_adjoint_weighted_f64, then d_z -13, d_gamma -14, d_alpha -15, ws -16, ws_bytes too small -17.
+ *      ws: dpgp_qx_psi_param_adjoint_workspace_bytes(B,N,M,Q).
  *   The workspace queries are host functions (0 for a shape out of range). */
 #define DPGP_QX_PSI_MAX_Q 64
 size_t dpgp_qx_psi_stats_workspace_bytes(int B, int N, int M, int Q);
@@ -147,6 +160,11 @@ int dpgp_qx_psi_adjoint_weighted_f64(int B, int N, int M, int Q, const double *z
                                      const double *gamma, const double *alpha, const double *zfac, const double *w,
                                      const double *g1, const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes,
                                      void *stream);
+size_t dpgp_qx_psi_param_adjoint_workspace_bytes(int B, int N, int M, int Q);
+int dpgp_qx_psi_param_adjoint_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                           const double *gamma, const double *alpha, const double *zfac, const double *w,
+                                           const double *g1, const double *g2, double *d_z, double *d_gamma, double *d_alpha,
+                                           void *ws, size_t ws_bytes, void *stream);
 
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
