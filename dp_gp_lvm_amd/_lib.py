@@ -67,6 +67,8 @@ SIGNATURES = {
     'dpgp_trtri_lower_batched_f64': (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
     'dpgp_ard_rbf_gram_grad_workspace_bytes': (_sz, [_i, _i]),
     'dpgp_ard_rbf_gram_grad_f64': (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dpgp_ard_rbf_gram_grad_batched_workspace_bytes': (_sz, [_i, _i, _i]),
+    'dpgp_ard_rbf_gram_grad_batched_f64': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dpgp_qx_psi_stats_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'dpgp_qx_psi_stats_batched_f64': (_i, [_i, _i, _i, _i] + [_vp] * 8 + [_vp, _sz, _vp]),
     'dpgp_qx_psi_adjoint_workspace_bytes': (_sz, [_i, _i, _i, _i]),

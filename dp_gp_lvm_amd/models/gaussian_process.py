@@ -31,7 +31,8 @@ from .dp_gp_lvm import dp_gp_lvm_t
 from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .test_bound import _TestBound, _as_device
-from .masked_bound import MaskedBayesianGPLVM
+from .slot_bound import kernel_slots
+from .masked_bound import MaskedBayesianGPLVM, MaskedMRD
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -642,9 +643,21 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
     return BayesianGPLVM()
 
 
+class _MaskedView:
+    """One view of a mask-trained MRD as the accessors and the test bounds see it: the view's four raw variables."""
+
+    def __init__(self, raw):
+        self.raw = raw
+
+    @property
+    def kernel(self):
+        return k_ard_rbf(gamma=F.softplus(self.raw['gamma_atoms']), alpha=F.softplus(self.raw['alpha_atoms']),
+                         beta=F.softplus(self.raw['beta_atoms']))
+
+
 def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT_LATENT_DIMENSIONS,
                                      num_inducing_points=GP_LVM_DEFAULT_NUM_INDUCING_POINTS,
-                                     device=None, precision=None, initial_values=None):
+                                     device=None, precision=None, initial_values=None, observed=None):
     """
     Manifold relevance determination — mirror of the reference's factory (src/models/gaussian_process.py:551-664): V views
     [N x D_v] share q(X); every view has its own B = 1 ARD-RBF kernel and its own M inducing inputs, and
@@ -654,6 +667,16 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
     are the SAME storage; the shared KL is counted once.
     Extensions: device, precision ('mixed' | 'f64'), initial_values (x_mean, x_var [N x Q]; gamma, alpha, beta, x_u: lists
     with one entry per view).
+
+    observed (extension): a list of V entries, each None (the view is complete) or a boolean [N x D_v] mask of the entries of
+    view v that were measured (entries where it is False are ignored and may be NaN); every view needs at least one True.
+    The model is then the masked fp64 model (precision None or 'f64', models/masked_bound.py): within a view the columns of
+    one row pattern share a slot of the weighted operators, the slots of view v use kernel v, a column never observed is left
+    out and a row observed in no view keeps only its KL.  The objective is -(sum_v sum_{b in v} f_b - KL(q(X)) over all N rows
+    + sum_v hyper-prior_v); raw_variables and gradients() keep the unmasked model's names, shapes and order.  x_mean defaults
+    to the PCA of the stacked views with their gaps filled by the columns' observed means.  impute_training_data() fills the
+    gaps with the posterior mean; the test-point methods work with the masked model's own training-side terms, except
+    predict_missing_data (NotImplementedError).
     """
     num_views = len(views_train)
     shapes = np.array([np.shape(v) for v in views_train])
@@ -667,14 +690,37 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         'Number of inducing points must be positive and less than the number of observations in the observed data.'
     iv = dict(initial_values or {})
     q, m = num_latent_dims, num_inducing_points
+    train_obs = None
+    if observed is not None:
+        assert precision in (None, 'f64'), "with observed, precision must be None or 'f64' (the masked model is fp64)"
+        assert isinstance(observed, (list, tuple)) and len(observed) == num_views, 'observed must be a list with one entry per view'
+        train_obs = [np.ones((num_samples, num_dimensions[v]), dtype=bool) if o is None else
+                     _missing.check_observed(o, (num_samples, num_dimensions[v])) for v, o in enumerate(observed)]
+        assert all(o.any() for o in train_obs), 'every view must hold at least one True entry'
     x_init = np.asarray(iv['x_mean'], dtype=np.float64) if 'x_mean' in iv else \
-        pca(np.hstack([np.asarray(v) for v in views_train]), num_latent_dimensions=q)                          # (:591)
+        pca(np.hstack([np.asarray(v) for v in views_train] if train_obs is None else
+                      [_missing.column_mean_filled(v, o) for v, o in zip(views_train, train_obs)]),
+            num_latent_dimensions=q)                                                                            # (:591)
     x_var = np.asarray(iv.get('x_var', np.ones((num_samples, q))), dtype=np.float64)                            # (:593: 1.0)
     inner = []
+    dev_m = torch.device(device) if device is not None else default_device()
+    masked_raw = {}
+    if train_obs is not None:
+        assert np.all(x_var > 0), 'Initial value must be positive.'
+        masked_raw = dict(x_mean=_as_device(x_init, dev_m, (num_samples, q)),
+                          x_var=_as_device(inverse_softplus(x_var), dev_m, (num_samples, q)))
     for v in range(num_views):
         x_u = np.asarray(iv['x_u'][v], dtype=np.float64) if 'x_u' in iv else \
             np.random.permutation(x_init)[:m] + np.random.normal(loc=0.0, scale=0.01, size=(m, q))              # (:599-601)
         pick = lambda key, default, shape: np.asarray(iv[key][v] if key in iv else default, dtype=np.float64).reshape(shape)
+        if train_obs is not None:
+            masked_raw['x_u_%d' % v] = _as_device(x_u, dev_m, (m, q))
+            for k, key, default, shape in (('gamma_atoms', 'gamma', np.full((1, q), GP_INIT_GAMMA), (1, q)),
+                                           ('alpha_atoms', 'alpha', GP_INIT_ALPHA, (1, 1)), ('beta_atoms', 'beta', GP_INIT_BETA, (1, 1))):
+                val = pick(key, default, shape)
+                assert np.all(val > 0), 'Initial value must be positive.'
+                masked_raw['%s_%d' % (k, v)] = _as_device(inverse_softplus(val), dev_m)
+            continue
         inner.append(dp_gp_lvm_t(np.asarray(views_train[v]), num_latent_dims=q, num_inducing_points=m, truncation_level=1,
                                  device=device, precision=precision, _view_of_many=True,
                                  initial_values=dict(x_mean=x_init, x_var=x_var, x_u=x_u,
@@ -682,21 +728,40 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                                                      alpha_atoms=pick('alpha', GP_INIT_ALPHA, (1, 1)),
                                                      beta_atoms=pick('beta', GP_INIT_BETA, (1, 1)),
                                                      phi_logits=np.zeros((num_dimensions[v], 1)))))
-    x_mean_t, x_var_raw = inner[0].raw['x_mean'], inner[0].raw['x_var']
-    for mv in inner[1:]:                                     # one q(X): same storage in every view's model
-        mv.raw['x_mean'].data = x_mean_t.data
-        mv.raw['x_var'].data = x_var_raw.data
     per_view = ('x_u', 'gamma_atoms', 'alpha_atoms', 'beta_atoms')
+    masked = None
+    if train_obs is not None:
+        views_zero = [_missing.zero_filled(v, o) for v, o in zip(views_train, train_obs)]
+        masked = MaskedMRD(views_zero, train_obs, masked_raw, dev_m)
+        inner = [_MaskedView({k: masked_raw['%s_%d' % (k, v)] for k in per_view}) for v in range(num_views)]
+        x_mean_t, x_var_raw = masked_raw['x_mean'], masked_raw['x_var']
+    else:
+        x_mean_t, x_var_raw = inner[0].raw['x_mean'], inner[0].raw['x_var']
+        for mv in inner[1:]:                                 # one q(X): same storage in every view's model
+            mv.raw['x_mean'].data = x_mean_t.data
+            mv.raw['x_var'].data = x_var_raw.data
     raw = dict(x_mean=x_mean_t, x_var=x_var_raw)
     for v, mv in enumerate(inner):
         for k in per_view:
             raw['%s_%d' % (k, v)] = mv.raw[k]
 
+    def _train_terms():
+        """(sum_v f_hat_v, KL(q(X))) of the model's own evaluation."""
+        if masked is not None:
+            _, f_hat, kl, _ = masked.terms()
+            return f_hat, kl
+        terms = [mv.objective_terms for mv in inner]        # (objective_t, f_hat, KL, DP objective, hyper-prior) per view
+        return sum(t_[1] for t_ in terms), terms[0][2]
+
     def _objective():
+        if masked is not None:
+            return masked.terms()[0]
         terms = [mv.objective_terms for mv in inner]          # (objective_t, f_hat, KL, DP objective, hyper-prior) per view
         return sum(t[0] - t[3] for t in terms) - (num_views - 1) * terms[0][2]
 
     def _gradients():
+        if masked is not None:
+            return masked.gradients()
         g = [mv.gradients() for mv in inner]
         s_ = F.softplus(x_var_raw)
         out = dict(x_mean=sum(gv['x_mean'] for gv in g) - (num_views - 1) * x_mean_t,          # KL counted once:
@@ -712,7 +777,7 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         for it in range(num_iterations):
             g = _gradients()
             bad = ~torch.stack([torch.isfinite(v).all() for v in g.values()]).all()
-            for mv in inner:
+            for mv in inner if masked is None else [masked]:
                 bad = bad | (mv.cholesky_info != 0)
             if bool(bad):
                 eff = precision or 'f64'                        # (None resolves to the reference's fp64 in the models it builds)
@@ -724,18 +789,18 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             if callback is not None:
                 callback(it)
 
-    views_np = [np.asarray(v, dtype=np.float64) for v in views_train]
+    views_np = [np.asarray(v, dtype=np.float64) for v in views_train] if masked is None else views_zero
     dev_ = x_mean_t.device
     pred_state = {}
+
+    def _frozen(ks):
+        return ([mv.raw['x_u'].detach() for mv in ks], [F.softplus(mv.raw['gamma_atoms']).detach() for mv in ks],
+                [F.softplus(mv.raw['alpha_atoms']).detach() for mv in ks], [F.softplus(mv.raw['beta_atoms']).detach() for mv in ks])
 
     def _test_bound(views_test):
         """Test bound of the first len(views_test) kernels (the observed views)."""
         with torch.no_grad():
-            ks = inner[:len(views_test)]
-            bound = _TestBound([mv.raw['x_u'].detach() for mv in ks], [F.softplus(mv.raw['gamma_atoms']).detach() for mv in ks],
-                               [F.softplus(mv.raw['alpha_atoms']).detach() for mv in ks],
-                               [F.softplus(mv.raw['beta_atoms']).detach() for mv in ks],
-                               [_as_device(v, dev_) for v in views_test], dev_)
+            bound = _TestBound(*_frozen(inner[:len(views_test)]), [_as_device(v, dev_) for v in views_test], dev_)
         pred_state['bound'] = bound
         return bound
 
@@ -759,17 +824,70 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         bound = _test_bound(views_test)
         with torch.no_grad():
             f_test, _, _ = bound.evaluate(xt, st_)
-            terms = [mv.objective_terms for mv in inner]    # (objective_t, f_hat, KL, DP objective, hyper-prior) per view
-            f_hat = sum(t_[1] for t_ in terms)
-            kl, kl_t = terms[0][2], ops.kl_qx(xt, st_)
+            f_hat, kl = _train_terms()
+            kl_t = ops.kl_qx(xt, st_)
         return f_hat + f_test - kl - kl_t
 
     def _init(views_test, use_pca, x_test_mean, x_test_var):
         vo = len(views_test)
+        if masked is not None and x_test_mean is None and not use_pca:
+            y_t = np.hstack(views_test)
+            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(
+                np.hstack(views_np[:vo]), np.hstack(train_obs[:vo]), y_t, np.ones(y_t.shape, dtype=bool),
+                x_mean_t.detach().cpu().numpy())
         return _init_test_latents(np.hstack(views_np[:vo]), np.hstack(views_test), x_mean_t, q, use_pca, x_test_mean,
                                   x_test_var, dev_)
 
-    def _test_latent_gradients(views_test, x_test_mean, x_test_var):
+    def _masked(views_test, observed, predict=False, reference_compat=False):
+        """The argument checks of the observed= paths; returns (the V test views zero-filled where unobserved, the V masks)."""
+        assert not reference_compat, 'reference_compat has no meaning with observed: the reference has no per-entry masks'
+        assert isinstance(observed, (list, tuple)) and len(observed) == num_views and len(views_test) == num_views, \
+            'with observed, views_test and observed must be lists with one entry per training view'
+        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+        assert all(v.ndim == 2 for v in views_test) and views_test[0].shape[0] >= 1 and \
+            [v.shape for v in views_test] == [(views_test[0].shape[0], d) for d in num_dimensions], \
+            'with observed, each test view must be [N* x D_v]'
+        obs = [np.ones(y.shape, dtype=bool) if o is None else _missing.check_observed(o, y.shape)
+               for y, o in zip(views_test, observed)]
+        assert any(o.any() for o in obs), 'observed must hold at least one True entry'
+        if predict:
+            assert not all(o.all() for o in obs), \
+                'observed is True everywhere: nothing is missing (use predict_new_latent_variables)'
+        return [_missing.zero_filled(y, o) for y, o in zip(views_test, obs)], obs
+
+    def _masked_bound(y0s, obs):
+        """The test bound whose slots are, per view, the column groups of its mask that share one row pattern (a view whose mask
+        is all False has none); the slots of view v use kernel v."""
+        slots = [(v, cols, w) for v in range(num_views) for cols, w in _missing.group_columns_by_pattern(obs[v])]
+        dmax = max(len(c) for _, c, _ in slots)
+        y = np.zeros((len(slots), y0s[0].shape[0], dmax))
+        for i, (v, cols, _) in enumerate(slots):
+            y[i, :, :len(cols)] = y0s[v][:, cols]
+        with torch.no_grad():
+            bound = kernel_slots(*_frozen(inner), [v for v, _, _ in slots], _as_device(y, dev_),
+                                            [len(c) for _, c, _ in slots], _as_device(np.stack([w for _, _, w in slots]), dev_),
+                                            dev_)
+        pred_state['bound'] = bound
+        pred_state['missing_views'] = [v for v in range(num_views) if not obs[v].all()]
+        pred_state['missing_columns'] = [_missing.missing_columns(obs[v]) for v in pred_state['missing_views']]
+        return bound
+
+    def _masked_init(y0s, obs, use_pca, x_test_mean, x_test_var):
+        y_t, o_t = np.hstack(y0s), np.hstack(obs)
+        if x_test_mean is None and not use_pca:
+            xm = x_mean_t.detach().cpu().numpy()
+            x_test_mean = _missing.masked_nearest_neighbour_init(np.hstack(views_np), y_t, o_t, xm) if masked is None else \
+                _missing.jointly_observed_nearest_neighbour_init(np.hstack(views_np), np.hstack(train_obs), y_t, o_t, xm)
+        return _init_test_latents(None, y_t, x_mean_t, q, use_pca, x_test_mean, x_test_var, dev_)
+
+    def _test_latent_gradients(views_test, x_test_mean, x_test_var, observed=None):
+        if observed is not None:
+            bound = _masked_bound(*_masked(views_test, observed))
+            xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
+            with torch.no_grad():
+                _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
+                _, k_mu, k_s = _kl_test(xt, st_)
+            return d_mu - k_mu, d_s - k_s
         views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
         assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
             'views_test must be the first Vo <= V views, each [N* x D_v]'
@@ -781,12 +899,17 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         return d_mu - k_mu, d_s - k_s
 
     def _optimise_test_latents(views_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
-                               x_test_var=None):
-        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
-        assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
-            'views_test must be the first Vo <= V views, each [N* x D_v]'
-        xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
-        bound = _test_bound(views_test)
+                               x_test_var=None, observed=None):
+        if observed is not None:
+            y0s, obs = _masked(views_test, observed)
+            xt, st_ = _masked_init(y0s, obs, use_pca, x_test_mean, x_test_var)
+            bound = _masked_bound(y0s, obs)
+        else:
+            views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+            assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
+                'views_test must be the first Vo <= V views, each [N* x D_v]'
+            xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
+            bound = _test_bound(views_test)
 
         def grad_fn(mu, s):
             _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
@@ -812,44 +935,101 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             return _bound_at(views_test, xt, st_), xt, torch.diag_embed(st_)
 
         @staticmethod
-        def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+        def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
+                                 observed=None):
             """views_test: the FIRST Vo < V views of the test points (gaussian_process.py:834-990).  Returns
                 (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_means, predicted_covars)
             with one entry per unobserved view v = Vo .. V-1: mean [N* x D_v], covariance [D_v x N* x N*].
             reference_compat=True reproduces the reference's predicted means, which use the LAST training view's
             C = L_A^-1 L_uu^-1 Psi1^T for every unobserved view (a variable leaked from the training loop, :938); the default
-            uses view v's own C.  The bound and the covariances are the same either way."""
+            uses view v's own C.  The bound and the covariances are the same either way.
+
+            observed (extension): a list of V entries, each None (the view is complete) or a boolean [N* x D_v] mask of the
+            measured entries of views_test[v] (an all-False mask: the view is absent); views_test then holds all V arrays,
+            whose unobserved entries are ignored and may be NaN.  The bound is sum_v f_hat_v + sum_slots f_hat*_b - KL(q(X)) -
+            KL(q(X*)), the slots of view v being the column groups of its mask that share one row pattern, with kernel v.  The
+            moments are returned for every view with at least one unobserved entry, in view order (property missing_views),
+            over that view's columns with at least one unobserved entry (property missing_columns, aligned), always with the
+            view's own C.  q(X*) starts at the masked nearest neighbour over the stacked views (a row with nothing observed
+            starts at 0).  AssertionError for lists of the wrong length, non-boolean masks, shape mismatches, masks that are
+            True everywhere, no True entry anywhere, or reference_compat=True.
+
+            On a model trained with observed= the per-pattern predictive moments are not built: NotImplementedError (the
+            training data's own gaps are filled by impute_training_data)."""
+            if masked is not None:
+                raise NotImplementedError('predict_missing_data is not built for a model trained with observed=: use '
+                                          'impute_training_data for the gaps of the training data')
+            if observed is not None:
+                y0s, obs = _masked(views_test, observed, predict=True, reference_compat=reference_compat)
+                xt, st_ = _masked_init(y0s, obs, use_pca, x_test_mean, x_test_var)
+                bound = _masked_bound(y0s, obs)
+                mv_, mc = pred_state['missing_views'], pred_state['missing_columns']
+                with torch.no_grad():
+                    f_test, _, _ = bound.evaluate(xt, st_)
+                    f_hat, kl = _train_terms()
+                    kl_t = ops.kl_qx(xt, st_)
+                    bound_u = _TestBound(*_frozen([inner[v] for v in mv_]),
+                                         [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(mv_), dev_)
+                    means, covars = _predictive_moments(bound_u, list(range(len(mv_))), x_mean_t.detach(),
+                                                        F.softplus(x_var_raw).detach(),
+                                                        [_as_device(views_np[v][:, c], dev_) for v, c in zip(mv_, mc)], xt, st_)
+                return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means, covars
             views_test = _check_views(views_test, True)
             vo = len(views_test)
+            pred_state['missing_views'] = list(range(vo, num_views))
+            pred_state['missing_columns'] = [np.arange(num_dimensions[v]) for v in range(vo, num_views)]
             xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
             lb = _bound_at(views_test, xt, st_)
             ku = inner[vo:]
             with torch.no_grad():
-                bound_u = _TestBound([mv.raw['x_u'].detach() for mv in ku], [F.softplus(mv.raw['gamma_atoms']).detach() for mv in ku],
-                                     [F.softplus(mv.raw['alpha_atoms']).detach() for mv in ku],
-                                     [F.softplus(mv.raw['beta_atoms']).detach() for mv in ku],
-                                     [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(ku), dev_)
+                bound_u = _TestBound(*_frozen(ku), [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(ku), dev_)
                 c_index = [len(ku) - 1] * len(ku) if reference_compat else list(range(len(ku)))
                 means, covars = _predictive_moments(bound_u, c_index, x_mean_t.detach(), F.softplus(x_var_raw).detach(),
                                                     [_as_device(v, dev_) for v in views_np[vo:]], xt, st_)
             return lb, xt, torch.diag_embed(st_), means, covars
 
         @staticmethod
-        def test_latent_gradients(views_test, x_test_mean, x_test_var):
+        def test_latent_gradients(views_test, x_test_mean, x_test_var, observed=None):
             """d(sum_v f_hat*_v - KL(q(X*))) / d(x_test_mean, x_test_var) over the given first Vo <= V views (one batched
-            qx_psi_stats_batched / qx_psi_adjoint over the Vo kernels)."""
-            return _test_latent_gradients(views_test, x_test_mean, x_test_var)
+            qx_psi_stats_batched / qx_psi_adjoint over the Vo kernels).  observed: as predict_missing_data (all V views; True
+            everywhere is allowed here)."""
+            return _test_latent_gradients(views_test, x_test_mean, x_test_var, observed)
 
         @staticmethod
         def optimise_test_latents(views_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
-                                  x_test_var=None):
+                                  x_test_var=None, observed=None):
             """Adam on q(X*) maximising sum_v f_hat*_v - KL(q(X*)) over the given first Vo views; returns (x_test_mean,
-            x_test_var).  No host synchronisation inside the loop."""
-            return _optimise_test_latents(views_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var)
+            x_test_var).  No host synchronisation inside the loop.  observed: as predict_missing_data."""
+            return _optimise_test_latents(views_test, num_iterations, learning_rate, use_pca, x_test_mean, x_test_var, observed)
+
+        @property
+        def missing_views(self):
+            """The views whose moments the last predict_missing_data returned (ascending), or None."""
+            return pred_state.get('missing_views')
+
+        @property
+        def missing_columns(self):
+            """Aligned with missing_views: the columns of each such view whose moments were returned (ascending), or None."""
+            return pred_state.get('missing_columns')
+
+        @staticmethod
+        def impute_training_data():
+            """A model trained with observed=: a list of V fp64 device tensors [N x D_v], view v with every unobserved entry
+            (n, d) replaced by the posterior mean beta_v Psi1_v[n,:] (K_uu_v + beta_v Psi2_d)^-1 Psi1_v^T y_d (Psi2_d and y_d
+            over the rows at which d was observed); observed entries as given, a never-observed column 0."""
+            assert masked is not None, 'impute_training_data needs a model trained with observed='
+            return masked.impute()
+
+        @property
+        def objective_terms(self):
+            """A model trained with observed=: the [slots x 5] terms of sum_slots f_b in the last evaluation, ordered by view
+            and then by first column; None for a model trained on complete views."""
+            return None if masked is None else masked.bound.terms
 
         @property
         def prediction_terms(self):
-            """[Vo x 5] terms of f_hat*_v of the last prediction evaluation (as bayesian_gp_lvm.prediction_terms, per view)."""
+            """[Vo x 5] terms of f_hat*_v of the last prediction evaluation (as bayesian_gp_lvm.prediction_terms, per view);
+            [slots x 5] after an evaluation with observed=."""
             b = pred_state.get('bound')
             return None if b is None else b.terms
 

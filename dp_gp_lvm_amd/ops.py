@@ -100,6 +100,39 @@ def ard_rbf_gram_grad(x, gamma, alpha, w):
     return r, sx, sq
 
 
+def ard_rbf_gram_grad_batched(x, gamma, alpha, w):
+    """ard_rbf_gram_grad for B kernels in one launch pair (dpgp_ard_rbf_gram_grad_batched_f64, fp64): x [B,N,Q], gamma [B,Q],
+    alpha [B], w [B,N,N] (any; a view with unit column stride, e.g. big[:, :N, :N], is used in place).  Returns r [B,N],
+    sx [B,N,Q], sq [B,N,Q]: for every b what ard_rbf_gram_grad returns for b's own inputs."""
+    f64 = torch.float64
+    x = _prep(x, f64, 'x')
+    assert x.dim() == 3, 'x must be [B x N x Q]'
+    b, n, q = x.shape
+    gamma = _prep(gamma, f64, 'gamma')
+    alpha = _prep(alpha, f64, 'alpha').reshape(-1)
+    assert gamma.numel() == b * q and alpha.numel() == b, 'gamma must be [B x Q], alpha [B]'
+    gamma = gamma.reshape(b, q)
+    if not isinstance(w, torch.Tensor) or not w.is_cuda:
+        raise RuntimeError('w must live on the GPU: dp_gp_lvm_amd runs its operators in HIP only')
+    assert w.dim() == 3 and tuple(w.shape) == (b, n, n), 'w must be [B x N x N]'
+    w = w.to(f64)
+    if w.stride(2) != 1 or w.stride(1) < max(1, n) or (b > 1 and w.stride(0) < (n - 1) * w.stride(1) + n):
+        w = w.contiguous()
+    r = torch.empty((b, n), dtype=f64, device=x.device)
+    sx = torch.empty((b, n, q), dtype=f64, device=x.device)
+    sq = torch.empty((b, n, q), dtype=f64, device=x.device)
+    if b == 0 or n == 0:
+        return r, sx, sq
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_gram_grad_batched_workspace_bytes(b, n, q)
+    ws = _ws(wsb, x.device)
+    _lib.check(l.dpgp_ard_rbf_gram_grad_batched_f64(b, n, q, x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(), w.data_ptr(),
+                                                    w.stride(1), w.stride(0), r.data_ptr(), sx.data_ptr(), sq.data_ptr(),
+                                                    ws.data_ptr(), wsb, _stream()),
+               'dpgp_ard_rbf_gram_grad_batched_f64')
+    return r, sx, sq
+
+
 def _qx_args(z, mu, s, gamma, alpha, zfac):
     f64 = torch.float64
     z, mu, s = _prep(z, f64, 'z'), _prep(mu, f64, 'mu'), _prep(s, f64, 's')

@@ -106,6 +106,16 @@ int dpgp_ard_rbf_gram_f64(int B, int N0, int N1, int Q, const double *x0, const 
 size_t dpgp_ard_rbf_gram_grad_workspace_bytes(int N, int Q);
 int dpgp_ard_rbf_gram_grad_f64(int N, int Q, const double *x, const double *gamma, const double *alpha, const double *w, int ldw,
                                double *r, double *sx, double *sq, void *ws, size_t ws_bytes, void *stream);
+/*   dpgp_ard_rbf_gram_grad_batched_f64: the same contraction for B kernels in one launch pair (the K_uu term of a masked
+ *      multi-view bound: V kernels with their own inducing inputs).  x[B][N][Q], gamma[B][Q], alpha[B], kernel b's w at
+ *      w + b * w_stride with leading dimension ldw (ldw >= N; w_stride >= (N - 1) ldw + N when B > 1), r[B][N], sx[B][N][Q],
+ *      sq[B][N][Q]: for every b what dpgp_ard_rbf_gram_grad_f64 returns for b's own inputs (the bits may differ where the slab
+ *      plans do: the batched plan divides its workgroup target by B).  B == 0 or N == 0 does nothing and reads no pointer.  The
+ *      workspace query returns 0 for a shape out of range.  No atomics, the same bits on every run. */
+size_t dpgp_ard_rbf_gram_grad_batched_workspace_bytes(int B, int N, int Q);
+int dpgp_ard_rbf_gram_grad_batched_f64(int B, int N, int Q, const double *x, const double *gamma, const double *alpha,
+                                       const double *w, int ldw, long long w_stride, double *r, double *sx, double *sq, void *ws,
+                                       size_t ws_bytes, void *stream);
 
 /* ---- Psi statistics of a test-point q(X*) for B kernels with their own inducing inputs, and their adjoint (the prediction
  *      paths of bayesian_gp_lvm / manifold_relevance_determination: gaussian_process.py:329-538 and :729-990 evaluate
