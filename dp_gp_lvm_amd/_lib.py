@@ -77,6 +77,12 @@ SIGNATURES = {
     'dpgp_qx_psi_adjoint_weighted_f64': (_i, [_i, _i, _i, _i] + [_vp] * 11 + [_vp, _sz, _vp]),
     'dpgp_qx_psi_param_adjoint_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'dpgp_qx_psi_param_adjoint_weighted_f64': (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp]),
+    'dpgp_qx_psi_stats_grouped_workspace_bytes': (_sz, [_i] * 5),
+    'dpgp_qx_psi_stats_grouped_f64': (_i, [_i] * 5 + [_vp] * 9 + [_vp, _sz, _vp]),
+    'dpgp_qx_psi_adjoint_grouped_workspace_bytes': (_sz, [_i] * 5),
+    'dpgp_qx_psi_adjoint_grouped_f64': (_i, [_i] * 5 + [_vp] * 11 + [_vp, _sz, _vp]),
+    'dpgp_qx_psi_param_adjoint_grouped_workspace_bytes': (_sz, [_i] * 5),
+    'dpgp_qx_psi_param_adjoint_grouped_f64': (_i, [_i] * 5 + [_vp] * 12 + [_vp, _sz, _vp]),
     'dpgp_gemm_strided_f64': (_i, [_i, _i, _i, _i, _d, _vp, _ll, _ll, _ll, _vp, _ll, _ll, _ll, _d, _vp, _ll, _ll, _ll, _vp]),
 }
 for _t in ('f32', 'f64'):

@@ -28,6 +28,7 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
+from .masked_bound_t import _MaskedBoundT
 from .test_bound import _TestBound
 
 
@@ -698,7 +699,7 @@ def dp_gp_lvm_t(y_train,
                 alpha_prior_params=DP_DEFAULT_ALPHA_PRIOR_PARAMS,
                 mask_size=1,
                 seed=0,
-                device=None, precision=None, initial_values=None, _view_of_many=False, process_group=None):
+                device=None, precision=None, initial_values=None, _view_of_many=False, process_group=None, observed=None):
     """
     Over-T formulation — mirror of the reference's ``dp_gp_lvm_t`` factory (src/models/dp_gp_lvm.py:513-676), SURVEY.md
     §8(f) row 3: the kernel batch is the T atoms, the mixture weights phi [T x D] enter outside the kernel, so an evaluation
@@ -717,6 +718,14 @@ def dp_gp_lvm_t(y_train,
     (shard_bounds): the T-atom chain is replicated (it does not depend on D), V = Psi1^T Y, the solves and every sum over d
     run on the local columns; an evaluation exchanges ONE scalar (the local f_hat), a gradient evaluation ONE packed
     all-reduce of all raw-variable gradients plus the trouble flag of optimise().
+    observed (extension): a boolean [N x D] mask of the entries of y_train that were measured, any pattern with at least one True
+    (entries where it is False are ignored and may be NaN).  f_hat is then the sum over the columns d observed somewhere of
+    -1/2 N_d log 2 pi + sum_t phi_td F_t(y_d on its rows R_d): T x P slots, P the number of distinct row patterns
+    (models/masked_bound_t.py), fp64 (precision None or 'f64'), one GPU (process_group None).  KL(q(X)) runs over all N rows, the
+    DP objective over all D columns, the hyper-prior over the T atoms; a column never observed contributes its DP terms only, a
+    row never observed its KL only.  x_mean defaults to the PCA of the column-mean-filled data.  impute_training_data() fills
+    the gaps with the mixture's posterior mean.  DPGP_GROUPED_PSI=0 runs the Psi statistics and their adjoints in the slot form
+    on the weighted operators (cross-checks only).
     """
     num_samples, num_dimensions = np.shape(y_train)
     # (_view_of_many: one view of a multi-view model, whose own check is against the views' total dimensionality)
@@ -729,6 +738,13 @@ def dp_gp_lvm_t(y_train,
         'The truncation level must be positive and less than or equal to the dimensionality of the observed data and ' \
         'less than or equal to the number of observations.'
     assert isinstance(seed, int) and seed >= 0, 'Seed must be a 32-bit unsigned integer, i.e., 0 <= seed <= 2^32 - 1.'
+    train_obs = None
+    if observed is not None:
+        assert precision in (None, 'f64'), "with observed, precision must be None or 'f64' (the masked model is fp64)"
+        assert process_group is None, 'with observed, process_group must be None (the masked model is not sharded)'
+        train_obs = _missing.check_observed(observed, (num_samples, num_dimensions))
+        assert train_obs.any(), 'observed must hold at least one True entry'
+        y_train = _missing.zero_filled(y_train, train_obs)
     precision = 'f64' if precision is None else precision     # (default: the reference's arithmetic, as in dp_gp_lvm)
     assert precision in ('mixed', 'f64'), "precision must be 'mixed' or 'f64'"
     np.random.seed(seed=seed)
@@ -744,7 +760,8 @@ def dp_gp_lvm_t(y_train,
         return create_positive_variable(init, shape, device=device)
 
     x_init = np.asarray(iv['x_mean'], dtype=np.float64) if 'x_mean' in iv else \
-        pca(np.asarray(y_train), num_latent_dimensions=num_latent_dims)
+        pca(np.asarray(y_train) if train_obs is None else _missing.column_mean_filled(y_train, train_obs),
+            num_latent_dimensions=num_latent_dims)
     x_mean = _t(x_init)
     x_var_raw = _raw_pos('x_var', 1.0, (num_samples, num_latent_dims))
     x_u = _t(iv['x_u']) if 'x_u' in iv else \
@@ -783,8 +800,12 @@ def dp_gp_lvm_t(y_train,
     # the fused forward pass (csrc/elbo.hip, dpgp_elbo_fhat_t): M <= 128 and at least T local output dims; otherwise, and
     # whenever gradients are wanted, f_hat is composed of the library's operators (_FHatT)
     fused_t = ops.ElboTWorkspace(truncation_level, d_, n_, m_, num_latent_dims, precision, device) \
-        if (ops.elbo_fhat_t_supported(m_) and d_ >= truncation_level and device.type == 'cuda'
+        if (ops.elbo_fhat_t_supported(m_) and d_ >= truncation_level and device.type == 'cuda' and train_obs is None
             and os.environ.get('DPGP_FUSED_T', '1') != '0') else None       # (DPGP_FUSED_T=0: cross-checks only)
+    # observed=: f_hat and its derivatives come from the T x P slot bound (models/masked_bound_t.py); everything around them
+    # (transforms, KL, DP objective, hyper-prior, chain rule to the raw variables) is the unmasked model's
+    masked = _MaskedBoundT(np.asarray(y_train, dtype=np.float64), train_obs, truncation_level, device) \
+        if train_obs is not None else None
 
     def _chain(x_u_, x_mean_, s_, gat, aat, bat):
         """Psi statistics and the Cholesky factors of the T atoms (library operators)."""
@@ -900,7 +921,11 @@ def dp_gp_lvm_t(y_train,
             phi = torch.repeat_interleave(phi, mask_size, dim=0)
         phit = phi[d_lo:d_hi].transpose(0, 1).contiguous()                                        # local dims
         mu = r['x_mean']
-        f_hat = _FHatT.apply(mu, s, r['x_u'], gat, aat, bat, phit)
+        if masked is not None:                                                                    # (values only: no torch graph)
+            f_hat = masked.evaluate(r['x_u'], mu, s, gat, aat, bat, phit)
+            last_info[0] = masked.info
+        else:
+            f_hat = _FHatT.apply(mu, s, r['x_u'], gat, aat, bat, phit)
         kl = 0.5 * (torch.sum(mu * mu) + torch.sum(s - torch.log(s)) - mu.shape[0] * mu.shape[1])     # gp_expressions.py:10-24
         hyper = torch.sum(log_normal_log_pdf(gat)) + torch.sum(log_normal_log_pdf(aat)) + torch.sum(log_normal_log_pdf(bat))
         w = F.softplus(r['dp_w'])
@@ -965,7 +990,10 @@ def dp_gp_lvm_t(y_train,
     def _objective_terms_graph():
         """The same evaluation replayed from a HIP graph (torch.cuda.CUDAGraph = hipGraph on ROCm): this composed objective
         is ~200 small launches, i.e. launch-bound; capturing them once removes the per-launch host cost.  The raw variables
-        are read in place, so updates by an optimiser are seen by the replay."""
+        are read in place, so updates by an optimiser are seen by the replay.  With observed= the evaluation is launched eagerly,
+        as in gradients() and optimise(): the masked bound is not captured."""
+        if masked is not None:
+            return evaluate()[0].clone()
         if 'g' not in graph:
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
@@ -1005,7 +1033,7 @@ def dp_gp_lvm_t(y_train,
         its derivatives with respect to (x_mean, S, x_u, atoms, phi) from the library's operators (_fhat_forward / _fhat_backward),
         dpgp_model_backward_t (chain rule to the raw variables, KL, DP objective, hyper-prior): ~200 launches instead of ~540.
         Sharded: the replicated terms are added on rank 0 only (add_constants); the ranks' packed gradients sum to the gradient."""
-        if os.environ.get('DPGP_T_AUTOGRAD', '0') == '1':
+        if os.environ.get('DPGP_T_AUTOGRAD', '0') == '1' and masked is None:
             return _local_flat_autograd()
         lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
         r = dp_model.raw
@@ -1022,8 +1050,13 @@ def dp_gp_lvm_t(y_train,
                 hbuf['scal'].data_ptr(), st), 'dpgp_model_prepare_t')
             at = hbuf['atoms']
             gat, aat, bat = at[:t_ * q_].view(t_, q_), at[t_ * q_:t_ * q_ + t_], at[t_ * q_ + t_:]
-            _, saved = _fhat_forward(x_mean, hbuf['s'], x_u, gat, aat, bat, hbuf['phi'].t().contiguous())
-            dmu, ds, dz, dgam, d_alpha, d_beta, d_phit = _fhat_backward(saved)
+            if masked is not None:
+                _, g = masked.evaluate(x_u, x_mean, hbuf['s'], gat, aat, bat, hbuf['phi'].t().contiguous(), grad=True)
+                last_info[0] = masked.info
+                dmu, ds, dz, dgam, d_alpha, d_beta, d_phit = (g[k] for k in ('mu', 's', 'z', 'gamma', 'alpha', 'beta', 'phit'))
+            else:
+                _, saved = _fhat_forward(x_mean, hbuf['s'], x_u, gat, aat, bat, hbuf['phi'].t().contiguous())
+                dmu, ds, dz, dgam, d_alpha, d_beta, d_phit = _fhat_backward(saved)
             dab = torch.stack([d_alpha, d_beta], dim=1).contiguous()
             dphi = d_phit.t().contiguous()
             sizes = {k: v.numel() for k, v in raw_vars.items()}
@@ -1052,7 +1085,7 @@ def dp_gp_lvm_t(y_train,
         graph=True (the default of optimise(); DPGP_GRAPH_T=0 turns it off): the local part — ~250 launches of library operators,
         element-wise kernels and their autograd, host-bound at ~4.6 ms per call whatever the problem size — is captured ONCE into a
         HIP graph (torch.cuda.CUDAGraph) and replayed; the raw variables are read in place, so optimiser updates are seen."""
-        use_graph = bool(graph) and os.environ.get('DPGP_GRAPH_T', '1') != '0'
+        use_graph = bool(graph) and os.environ.get('DPGP_GRAPH_T', '1') != '0' and masked is None   # (observed=: launched eagerly)
         if use_graph:
             if 'g' not in grad_graph:
                 cur = torch.cuda.current_stream()
@@ -1097,6 +1130,19 @@ def dp_gp_lvm_t(y_train,
             opt.step()
             if callback is not None:
                 callback(it)
+
+    def _impute_training_data():
+        """A model trained with observed=: y_train [N x D] with every unobserved entry (n, d) replaced by the mixture's posterior mean
+        sum_t phi_td beta_t Psi1_t[n,:] (K_t + beta_t Psi2_{t,p(d)})^-1 Psi1_t^T y_d (Psi2 and y_d over the rows at which d was
+        observed); observed entries as given; a column never observed gets 0."""
+        assert masked is not None, 'impute_training_data needs a model trained with observed='
+        with torch.no_grad():
+            gat, aat, bat = F.softplus(gamma_atoms_raw), F.softplus(sig_var_atoms_raw)[:, 0], F.softplus(beta_atoms_raw)[:, 0]
+            phi = torch.softmax(dp_model.raw['logits'], dim=-1)
+            if mask_size != 1:
+                phi = torch.repeat_interleave(phi, mask_size, dim=0)
+            means = masked.posterior_means(x_u, x_mean, F.softplus(x_var_raw), gat, aat, bat, phi.transpose(0, 1).contiguous())
+            return torch.where(torch.as_tensor(train_obs, device=device), y_dev, means)
 
     class DP_GP_LVM_T(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
@@ -1147,5 +1193,6 @@ def dp_gp_lvm_t(y_train,
         objective_terms_graph = staticmethod(_objective_terms_graph)
         gradients = staticmethod(_gradients)
         optimise = staticmethod(_optimise)
+        impute_training_data = staticmethod(_impute_training_data)
 
     return DP_GP_LVM_T()

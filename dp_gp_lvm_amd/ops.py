@@ -246,6 +246,75 @@ def qx_psi_param_adjoint(z, mu, s, gamma, alpha, g1, g2, zfac=None, weights=None
     return d_z, d_gamma, d_alpha
 
 
+def _qx_grouped_args(z, mu, s, gamma, alpha, weights, zfac):
+    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    if not isinstance(weights, torch.Tensor) or weights.dim() != 2:
+        raise TypeError('weights must be a [P x N] float64 torch.Tensor (required by the grouped operators)')
+    weights = _qx_weights(weights, weights.shape[0], n, mu)
+    assert weights.shape[0] >= 1, 'weights must hold at least one row'
+    return z, mu, s, gamma, alpha, zfac, weights, k, weights.shape[0], n, m, q
+
+
+def qx_psi_stats_grouped(z, mu, s, gamma, alpha, weights, zfac=None):
+    """Psi1 [K,N,M] (once per kernel, not weighted) and Psi2 [K,P,M,M] = sum_n weights[p,n] psi2_kn of q(X) = (mu, s) [N,Q] for K
+    kernels z [K,M,Q], gamma [K,Q], alpha [K] and P weight rows [P,N] shared by the kernels (dpgp_qx_psi_stats_grouped_f64):
+    what qx_psi_stats_batched(weights=) gives for the K P slots (k, p), with every exponential evaluated once per chunk of
+    patterns.  weights: fp64 contiguous on the inputs' device, required."""
+    z, mu, s, gamma, alpha, zfac, weights, k, p, n, m, q = _qx_grouped_args(z, mu, s, gamma, alpha, weights, zfac)
+    psi_1 = torch.empty((k, n, m), dtype=torch.float64, device=mu.device)
+    psi_2 = torch.empty((k, p, m, m), dtype=torch.float64, device=mu.device)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_stats_grouped_workspace_bytes(k, p, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_stats_grouped_f64(k, p, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                               alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), weights.data_ptr(),
+                                               psi_1.data_ptr(), psi_2.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_stats_grouped_f64')
+    return psi_1, psi_2
+
+
+def _qx_grouped_adjoints(g1, g2, k, p, n, m):
+    g1, g2 = _prep(g1, torch.float64, 'g1'), _prep(g2, torch.float64, 'g2')
+    assert tuple(g1.shape) == (k, n, m) and tuple(g2.shape) == (k, p, m, m), 'g1 must be [K x N x M], g2 [K x P x M x M]'
+    return g1, g2
+
+
+def qx_psi_adjoint_grouped(z, mu, s, gamma, alpha, g1, g2, weights, zfac=None):
+    """(d_mu, d_s) [N,Q] of sum_k <g1_k, Psi1_k> + sum_kp <g2_kp, Psi2_kp> for the statistics of qx_psi_stats_grouped: g1 [K,N,M]
+    (already summed over the patterns), g2 [K,P,M,M] (any matrices) (dpgp_qx_psi_adjoint_grouped_f64; fixed summation order)."""
+    z, mu, s, gamma, alpha, zfac, weights, k, p, n, m, q = _qx_grouped_args(z, mu, s, gamma, alpha, weights, zfac)
+    g1, g2 = _qx_grouped_adjoints(g1, g2, k, p, n, m)
+    d_mu = torch.empty((n, q), dtype=torch.float64, device=mu.device)
+    d_s = torch.empty_like(d_mu)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_adjoint_grouped_workspace_bytes(k, p, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_adjoint_grouped_f64(k, p, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                 alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), weights.data_ptr(),
+                                                 g1.data_ptr(), g2.data_ptr(), d_mu.data_ptr(), d_s.data_ptr(), ws.data_ptr(), wsb,
+                                                 _stream()), 'dpgp_qx_psi_adjoint_grouped_f64')
+    return d_mu, d_s
+
+
+def qx_psi_param_adjoint_grouped(z, mu, s, gamma, alpha, g1, g2, weights, zfac=None):
+    """(d_z [K,M,Q], d_gamma [K,Q], d_alpha [K]) of the same sum, per kernel, summed over that kernel's patterns; the derivative
+    of the complete Psi2, pair factor included (dpgp_qx_psi_param_adjoint_grouped_f64; fixed summation order)."""
+    z, mu, s, gamma, alpha, zfac, weights, k, p, n, m, q = _qx_grouped_args(z, mu, s, gamma, alpha, weights, zfac)
+    g1, g2 = _qx_grouped_adjoints(g1, g2, k, p, n, m)
+    d_z = torch.empty((k, m, q), dtype=torch.float64, device=mu.device)
+    d_gamma = torch.empty((k, q), dtype=torch.float64, device=mu.device)
+    d_alpha = torch.empty(k, dtype=torch.float64, device=mu.device)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_param_adjoint_grouped_workspace_bytes(k, p, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_param_adjoint_grouped_f64(k, p, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                       alpha.data_ptr(), None if zfac is None else zfac.data_ptr(),
+                                                       weights.data_ptr(), g1.data_ptr(), g2.data_ptr(), d_z.data_ptr(),
+                                                       d_gamma.data_ptr(), d_alpha.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_param_adjoint_grouped_f64')
+    return d_z, d_gamma, d_alpha
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

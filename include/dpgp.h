@@ -176,6 +176,42 @@ int dpgp_qx_psi_param_adjoint_weighted_f64(int B, int N, int M, int Q, const dou
                                            const double *g1, const double *g2, double *d_z, double *d_gamma, double *d_alpha,
                                            void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Pattern-grouped forms of the three operators above: K kernels (z[K][M][Q], gamma[K][Q], alpha[K], zfac NULL or
+ *      [K][M][M]) and P weight rows w[P][N] shared by all K kernels (any finite reals; 0 / 1 for row patterns of a missing-data
+ *      mask; required, not nullable).  The semantics are those of the weighted operators called with B = K P slots, slot (k, p)
+ *      carrying kernel k's replicated inputs and weight row p and g1 split in any way over the slots of a kernel; the grouped
+ *      forms evaluate each (kernel, point, pair) exponential once per chunk of PC patterns instead of once per slot, and read
+ *      Psi1 / g1 once per kernel.  1 <= K, P, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.  No atomics: partial sums go through the
+ *      workspace in a fixed order, the same bits on every run.  A point whose weights are 0 for a whole chunk costs no
+ *      exponential and contributes exactly 0.0.
+ *   dpgp_qx_psi_stats_grouped_f64:  psi1[K][N][M] (once per kernel, not weighted), psi2[K][P][M][M] = sum_n w[p][n] psi2_kn,
+ *      exactly symmetric.  PC = 8 / 4 / 2 / 1 for P >= 5 / 3 / 2 / 1.
+ *   dpgp_qx_psi_adjoint_grouped_f64:  g1[K][N][M] (already summed over the patterns), g2[K][P][M][M] (any matrices);
+ *      d_mu[N][Q], d_s[N][Q] = the derivative of sum_k <g1_k, Psi1_k> + sum_kp <g2_kp, Psi2_kp>.  PC as for the stats, halved
+ *      until PC tiles [32][33] fit the 160 KiB of LDS beside one wave's points: 8 for Q <= 46, 4 for Q <= 63, 2 at Q = 64.
+ *   dpgp_qx_psi_param_adjoint_grouped_f64:  the same inputs; d_z[K][M][Q], d_gamma[K][Q], d_alpha[K] of the same sum, per
+ *      kernel, summed over that kernel's patterns; the derivative of the complete Psi2, pair factor included.  PC as for the
+ *      stats.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, P -2, N -3, M -4, Q -5, z -6, mu -7, s -8,
+ *      gamma -9, alpha -10, (zfac: nullable, no code), w -12; then stats: psi1 -13, psi2 -14, ws -15, ws_bytes too small -16;
+ *      adjoint: g1 -13, g2 -14, d_mu -15, d_s -16, ws -17, ws_bytes too small -18;  parameter adjoint: g1 -13, g2 -14, d_z -15,
+ *      d_gamma -16, d_alpha -17, ws -18, ws_bytes too small -19.
+ *   ws: the ..._grouped_workspace_bytes(K,P,N,M,Q) of the operator (host functions; 0 for a shape out of range). */
+size_t dpgp_qx_psi_stats_grouped_workspace_bytes(int K, int P, int N, int M, int Q);
+int dpgp_qx_psi_stats_grouped_f64(int K, int P, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                  const double *gamma, const double *alpha, const double *zfac, const double *w, double *psi1,
+                                  double *psi2, void *ws, size_t ws_bytes, void *stream);
+size_t dpgp_qx_psi_adjoint_grouped_workspace_bytes(int K, int P, int N, int M, int Q);
+int dpgp_qx_psi_adjoint_grouped_f64(int K, int P, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                    const double *gamma, const double *alpha, const double *zfac, const double *w,
+                                    const double *g1, const double *g2, double *d_mu, double *d_s, void *ws, size_t ws_bytes,
+                                    void *stream);
+size_t dpgp_qx_psi_param_adjoint_grouped_workspace_bytes(int K, int P, int N, int M, int Q);
+int dpgp_qx_psi_param_adjoint_grouped_f64(int K, int P, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                          const double *gamma, const double *alpha, const double *zfac, const double *w,
+                                          const double *g1, const double *g2, double *d_z, double *d_gamma, double *d_alpha,
+                                          void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);
