@@ -61,11 +61,10 @@ __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1,
             }
     }
     const T al = (T)alpha[b];
-    T diag_add = 0;
-    if (symmetric & 1) {
-        if (flags & DPGP_FLAG_NOISE) diag_add += (T)1 / (T)beta[b];
-        if (flags & DPGP_FLAG_JITTER) diag_add += jitter;
-    }
+    // noise and jitter are added to the diagonal ONE AFTER THE OTHER, (alpha + 1/beta) + jitter, as the reference adds its two
+    // diagonal matrices (rbf_kernel.py:80-91) and as diag_kernel below does: their sum added at once rounds differently
+    const bool add_noise = (symmetric & 1) && (flags & DPGP_FLAG_NOISE), add_jitter = (symmetric & 1) && (flags & DPGP_FLAG_JITTER);
+    const T noise = add_noise ? (T)1 / (T)beta[b] : (T)0;
     const T scale = (T)(-0.5 * DPGP_LOG2E);
     T *ob = out + (size_t)b * batch_stride;
 #pragma unroll
@@ -77,7 +76,10 @@ __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1,
         for (int c = 0; c < 4; ++c) {
             int j = j0 + tx * 4 + c;
             v[c] = al * dpgp_exp2_hot(scale * acc[r][c], etab);
-            if ((symmetric & 1) && i == j) v[c] += diag_add;
+            if (i == j) {
+                if (add_noise) v[c] += noise;
+                if (add_jitter) v[c] += jitter;
+            }
         }
         int j = j0 + tx * 4;
         T *p = ob + (size_t)i * ld_out + j;
