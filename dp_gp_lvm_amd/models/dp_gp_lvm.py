@@ -30,6 +30,7 @@ from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
 from .masked_bound_t import _MaskedBoundT
 from .test_bound import _TestBound
+from .test_bound_t import _MomentsT, _TestBoundT
 
 
 def shard_bounds(num_dimensions, rank, world_size):
@@ -1144,6 +1145,76 @@ def dp_gp_lvm_t(y_train,
             means = masked.posterior_means(x_u, x_mean, F.softplus(x_var_raw), gat, aat, bat, phi.transpose(0, 1).contiguous())
             return torch.where(torch.as_tensor(train_obs, device=device), y_dev, means)
 
+    # ---- prediction (models/test_bound_t.py): fp64, one GPU; the reference's own over-T predict_* raise NameError, so there is
+    # nothing to mirror: the bound is the model's own masked bound on the test rows with everything trained held fixed
+    pred_state = {}
+
+    def _frozen():
+        """The trained values the prediction paths hold fixed: (gamma [T,Q], alpha [T], beta [T], phi^T [T,D], S [N,Q])."""
+        assert precision == 'f64' and not sharded, 'prediction paths of dp_gp_lvm_t run in fp64 on one GPU'
+        with torch.no_grad():
+            phi = torch.softmax(dp_model.raw['logits'], dim=-1)
+            if mask_size != 1:
+                phi = torch.repeat_interleave(phi, mask_size, dim=0)
+            return (F.softplus(gamma_atoms_raw), F.softplus(sig_var_atoms_raw)[:, 0].contiguous(),
+                    F.softplus(beta_atoms_raw)[:, 0].contiguous(), phi.transpose(0, 1).contiguous(), F.softplus(x_var_raw))
+
+    def _test_arguments(y_test, observed, predict=False):
+        """(y_test zero-filled [N* x D], mask): `observed` given -> the checks of utils.missing.masked_arguments; None -> y_test
+        holds the first Do <= D output dims of every test point."""
+        assert precision == 'f64' and not sharded, 'prediction paths of dp_gp_lvm_t run in fp64 on one GPU'
+        if observed is not None:
+            return _missing.masked_arguments(y_test, observed, num_dimensions, predict)
+        y_test = np.asarray(y_test, dtype=np.float64)
+        assert y_test.ndim == 2 and y_test.shape[0] >= 1 and 1 <= y_test.shape[1] <= num_dimensions, \
+            'y_test must be [N* x Do] with 1 <= Do <= D'
+        if predict:
+            assert y_test.shape[1] < num_dimensions, \
+                'Observed dimensionality for missing data scenario must be less than total dimensionality of training data.'
+        obs = np.zeros((y_test.shape[0], num_dimensions), dtype=bool)
+        obs[:, :y_test.shape[1]] = True
+        y0 = np.zeros(obs.shape)
+        y0[:, :y_test.shape[1]] = y_test
+        return y0, obs
+
+    def _test_bound(y0, obs):
+        gat, aat, bat, phit, _ = _frozen()
+        return _TestBoundT(x_u.detach(), gat, aat, bat, phit, y0, obs, device)
+
+    def _values(v):
+        return _t(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
+
+    def _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var):
+        """q(X*) at the start: the given values, or the PCA of the zero-filled test rows, or the training latent mean of the
+        nearest training row over the jointly observed columns plus N(0, 0.01^2) noise; variances 1 unless given."""
+        n_t = y0.shape[0]
+        if x_test_mean is not None:
+            init = _values(x_test_mean).reshape(n_t, num_latent_dims)
+        elif use_pca:
+            init = _t(pca(y0, num_latent_dimensions=num_latent_dims))
+        elif train_obs is None:
+            init = _t(_missing.masked_nearest_neighbour_init(np.asarray(y_train), y0, obs, x_mean.detach().cpu().numpy()))
+        else:
+            init = _t(_missing.jointly_observed_nearest_neighbour_init(np.asarray(y_train), train_obs, y0, obs,
+                                                                       x_mean.detach().cpu().numpy()))
+        var = _values(x_test_var).reshape(n_t, num_latent_dims) if x_test_var is not None else \
+            torch.ones((n_t, num_latent_dims), dtype=TORCH_DTYPE, device=device)
+        return init, var
+
+    def _moments():
+        """The training side of the predictive moments (test_bound_t._MomentsT), formed once per call."""
+        gat, aat, bat, phit, s = _frozen()
+        train = masked if masked is not None else \
+            _MaskedBoundT(np.asarray(y_train, dtype=np.float64), np.ones((num_samples, num_dimensions), dtype=bool),
+                          truncation_level, device)
+        with torch.no_grad():
+            return _MomentsT(train, x_u.detach(), x_mean.detach(), s, gat, aat, bat, phit)
+
+    def _columns_arg(columns):
+        cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
+        assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+        return torch.as_tensor(cols, dtype=torch.long, device=device)
+
     class DP_GP_LVM_T(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
@@ -1194,5 +1265,104 @@ def dp_gp_lvm_t(y_train,
         gradients = staticmethod(_gradients)
         optimise = staticmethod(_optimise)
         impute_training_data = staticmethod(_impute_training_data)
+
+        @property
+        def prediction_terms(self):
+            """F_t(d) [T P x Dmax] of the test bound in the last prediction call (slot t P + p, the places of pattern p's columns;
+            the layout of masked_bound_t._MaskedBoundT), or None."""
+            return pred_state.get('terms')
+
+        @property
+        def missing_columns(self):
+            """The output dims whose moments the last predict_missing_data returned (ascending), or None."""
+            return pred_state.get('missing_columns')
+
+        @staticmethod
+        def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None):
+            """q(X*) for fully observed test data y_test [N* x D] and the prediction lower bound
+                f_hat + f_hat* - KL(q(X)) - KL(q(X*)),    test log-likelihood = f_hat* - KL(q(X*)),
+            f_hat* the model's own bound on (y_test, q(X*)) with everything trained held fixed (models/test_bound_t.py).  Returns
+            (prediction_lower_bound, x_test_mean [N* x Q], x_test_covar [N* x Q x Q], test_log_likelihood) at the initial q(X*):
+            nearest training neighbour + N(0, 0.01^2) noise, or PCA of y_test (`use_pca`), or the given values; variances 1.
+            fp64 and one GPU (AssertionError for a 'mixed' or sharded model)."""
+            y0, obs = _test_arguments(y_test, None)
+            assert np.shape(y_test)[1] == num_dimensions, \
+                'Observed dimensionality for prediction must be equal to the dimensionality of the training data.'
+            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            out = evaluate()[0].clone()                                           # (objective, f_hat, KL, DP, hyper)
+            bound = _test_bound(y0, obs)
+            with torch.no_grad():
+                f_hat_test, _, _ = bound.evaluate(xt, st_)
+                pred_state['terms'] = bound.terms
+                test_ll = f_hat_test - ops.kl_qx(xt, st_)
+            return out[1] - out[2] + test_ll, xt, torch.diag_embed(st_), test_ll
+
+        @staticmethod
+        def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
+            """d (f_hat* - KL(q(X*))) / d (x_test_mean, x_test_var) with the trained model fixed.  y_test [N* x Do] (the first
+            Do <= D output dims), or [N* x D] with a boolean mask `observed` of any pattern (entries where it is False are ignored
+            and may be NaN; True everywhere is allowed here)."""
+            bound = _test_bound(*_test_arguments(y_test, observed))
+            xt, st_ = _values(x_test_mean), _values(x_test_var)
+            with torch.no_grad():
+                _, dmu, ds = bound.evaluate(xt, st_, grad=True)
+                pred_state['terms'] = bound.terms
+            return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)                        # minus the KL gradient
+
+        @staticmethod
+        def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
+                                  x_test_var=None, observed=None):
+            """Adam on q(X*) (mean and softplus-parametrised variances) maximising f_hat* - KL(q(X*)); returns (x_test_mean,
+            x_test_var) to hand to predict_*.  The frozen bound is formed once and nothing is read back on the host inside the
+            loop.  observed: as test_latent_gradients; the start is then the masked nearest neighbour."""
+            y0, obs = _test_arguments(y_test, observed)
+            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            bound = _test_bound(y0, obs)
+            raw = torch.log(torch.expm1(st_))
+            opt = torch.optim.Adam([xt, raw], lr=learning_rate)
+            with torch.no_grad():
+                for _ in range(num_iterations):
+                    sv = F.softplus(raw)
+                    _, g_mu, g_s = bound.evaluate(xt, sv, grad=True)
+                    xt.grad, raw.grad = -(g_mu - xt), -(g_s - 0.5 * (1.0 - 1.0 / sv)) * torch.sigmoid(raw)
+                    opt.step()
+                pred_state['terms'] = bound.terms
+                return xt, F.softplus(raw)
+
+        @staticmethod
+        def predictive_marginals(x_test_mean, x_test_var, columns=None):
+            """(mean, var), each [N* x len(columns)]: the per-entry moments of the mixture sum_t phi_td N(mean_t, var_t) of the
+            output dims `columns` (default: all D) at q(X*) = (x_test_mean, x_test_var [N* x Q]); formulas in
+            models/test_bound_t._MomentsT, the Psi2 parts by ops.qx_psi_pointwise.  A column never observed in training has mean
+            0 and variance sum_t phi_td (alpha_t + 1 / beta_t)."""
+            cols = _columns_arg(columns)
+            with torch.no_grad():
+                return _moments().at(_values(x_test_mean), _values(x_test_var), cols)
+
+        @staticmethod
+        def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):
+            """y_test [N* x Do] holds the first Do < D output dims of the test points, or, with `observed` (a boolean [N* x D]
+            mask of any pattern, not True everywhere; unobserved entries are ignored and may be NaN), y_test is [N* x D].
+            Returns (lower_bound, x_test_mean, x_test_covar [N* x Q x Q], predicted_mean [N* x Du], predicted_var [N* x Du]) at
+            the initial q(X*) (see predict_new_latent_variables; with a mask the masked nearest neighbour) for the Du dims
+            Do .. D-1, or, with `observed`, the columns with at least one unobserved test entry, ascending (missing_columns).
+            lower_bound = f_hat + f_hat* - KL(q(X)) - KL(q(X*)).
+
+            predicted_var is the PER-ENTRY marginal variance of the mixture over the atoms (observation noise 1 / beta_t
+            included), not the [Du x N* x N*] array the other models return in the reference's shape.  That array is built from
+            Psi2* summed over all test points: one scalar per output dim plus a diagonal, the same for every test point, so it
+            cannot say how sure the model is about one filled-in value.  The per-entry variance needs each test point's own
+            Psi2*, contracted on the fly by ops.qx_psi_pointwise; the reference has no working over-T prediction to mirror."""
+            y0, obs = _test_arguments(y_test, observed, predict=True)
+            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            out = evaluate()[0].clone()
+            bound = _test_bound(y0, obs)
+            pred_state['missing_columns'] = _missing.missing_columns(obs)
+            with torch.no_grad():
+                f_hat_test, _, _ = bound.evaluate(xt, st_)
+                pred_state['terms'] = bound.terms
+                lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                mean, var = _moments().at(xt, st_, _columns_arg(pred_state['missing_columns']))
+            return lower_bound, xt, torch.diag_embed(st_), mean, var
 
     return DP_GP_LVM_T()

@@ -315,6 +315,37 @@ def qx_psi_param_adjoint_grouped(z, mu, s, gamma, alpha, g1, g2, weights, zfac=N
     return d_z, d_gamma, d_alpha
 
 
+def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
+    """Per-point Psi2 contractions (dpgp_qx_psi_pointwise_f64): with psi2_kn [M,M] test point n's own term of kernel k's Psi2 at
+    q(X) = (mu, s) [N,Q] (kernels z [K,M,Q], gamma [K,Q], alpha [K] as in qx_psi_stats_grouped), returns
+        tr [K,N,G]   = sum_{m,m'} c[k,g,m,m'] psi2_kn[m,m']            c [K,G,M,M], any matrices
+        quad [K,N,J] = sum_{m,m'} r[k,m,j] r[k,m',j] psi2_kn[m,m']     r [K,M,J]
+    without forming psi2_kn in memory; fixed summation order, the same bits on every run.  c and r: float64 tensors on the
+    inputs' device (TypeError otherwise), of these shapes (ValueError otherwise)."""
+    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    for name, a in (('c', c), ('r', r)):
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % name)
+        if a.device != mu.device:
+            raise RuntimeError('%s must live on the device of the inputs' % name)
+    if c.dim() != 4 or c.shape[0] != k or c.shape[1] < 1 or tuple(c.shape[2:]) != (m, m):
+        raise ValueError('c must be [K x G x M x M] with G >= 1, got %s' % (tuple(c.shape),))
+    if r.dim() != 3 or r.shape[0] != k or r.shape[1] != m or r.shape[2] < 1:
+        raise ValueError('r must be [K x M x J] with J >= 1, got %s' % (tuple(r.shape),))
+    c, r = c.contiguous(), r.contiguous()
+    g, j = c.shape[1], r.shape[2]
+    tr = torch.empty((k, n, g), dtype=torch.float64, device=mu.device)
+    quad = torch.empty((k, n, j), dtype=torch.float64, device=mu.device)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_pointwise_workspace_bytes(k, g, j, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_pointwise_f64(k, g, j, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                           alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), c.data_ptr(), r.data_ptr(),
+                                           tr.data_ptr(), quad.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_pointwise_f64')
+    return tr, quad
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

@@ -212,6 +212,25 @@ int dpgp_qx_psi_param_adjoint_grouped_f64(int K, int P, int N, int M, int Q, con
                                           const double *g1, const double *g2, double *d_z, double *d_gamma, double *d_alpha,
                                           void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Per-point Psi2 contractions (csrc/qx_psi_point.hip): K kernels (z[K][M][Q], gamma[K][Q], alpha[K], zfac NULL or
+ *      [K][M][M]) that share q(X) = (mu[N][Q], s[N][Q]), as in the grouped operators.  With psi2_kn[m,m'] test point n's own
+ *      term of kernel k's Psi2 (pair factor included; sum_n psi2_kn is psi2 of dpgp_qx_psi_stats_batched_f64):
+ *        tr[K][N][G]   = sum_{m,m'} c_kg[m,m'] psi2_kn[m,m']                  c[K][G][M][M], any matrices: symmetry not assumed
+ *        quad[K][N][J] = sum_{m,m'} r_k[m,j] r_k[m',j] psi2_kn[m,m']          r[K][M][J]
+ *      (the per-entry predictive variance of a sparse GP at an uncertain input needs both: c = K^-1 - P per row pattern, r the
+ *      posterior weights per output column).  One product E[N x pairs] W[pairs x (G + J)] per kernel on the fp64 matrix pipe:
+ *      E is made on the fly, one exponential per (k, n, pair) and per chunk of up to 128 columns (64 for Q > 32), and nothing of
+ *      size N M M or pairs x J is written to memory.  The workspace holds partial sums of the two outputs only (the pair tiles
+ *      are split over workgroups when N K is small); a second launch adds them in a fixed order: no atomics, the same bits on
+ *      every run.  1 <= K, G, J, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, G -2, J -3, N -4, M -5, Q -6, z -7, mu -8, s -9,
+ *      gamma -10, alpha -11, (zfac: nullable, no code), c -13, r -14, tr -15, quad -16, ws -17, ws_bytes too small -18.
+ *   ws: dpgp_qx_psi_pointwise_workspace_bytes(K,G,J,N,M,Q) (a host function; 0 for a shape out of range). */
+size_t dpgp_qx_psi_pointwise_workspace_bytes(int K, int G, int J, int N, int M, int Q);
+int dpgp_qx_psi_pointwise_f64(int K, int G, int J, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                              const double *gamma, const double *alpha, const double *zfac, const double *c, const double *r,
+                              double *tr, double *quad, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);

@@ -1,0 +1,387 @@
+"""GPU tests of the over-T model's prediction paths (models/test_bound_t.py, DP_GP_LVM_T.predict_* / test_latent_gradients /
+optimise_test_latents / predictive_marginals): the frozen test bound and its gradient against the committed fp64 oracle composed per
+column on its observed test rows (phi and every trained value constants), the per-entry moments against a NumPy restatement of
+their four formulas, T = 1 against bayesian_gp_lvm, one-hot phi against the over-D dp_gp_lvm, and fitting q(X*) end to end.
+Tolerances: rtol 1e-10 for bounds, 1e-8 of the largest entry for gradients, 1e-9 for moments (the project's figures for its
+other prediction paths)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import golden
+from test_gpu_predict_b1 import build_bgplvm, close
+from test_gpu_predict_masked import masks_of
+from test_gpu_train_masked import build_masked, synthetic
+from test_gpu_train_masked_t import FIXTURES, build_masked_t, oracle_masked_t, raw_of, softplus
+
+pytestmark = pytest.mark.gpu
+TRAIN = {}
+
+
+def build_t(g, dev, kind, mask_size=1, **kw):
+    """The fixture's model: kind None -> trained on complete data (no observed=); 'all' -> observed= all True; else a masks_of kind."""
+    if kind is None:
+        return build_masked_t(g, dev, None, mask_size=mask_size, **kw), np.ones(g['y'].shape, dtype=bool)
+    obs = np.ones(g['y'].shape, dtype=bool) if kind == 'all' else masks_of(*g['y'].shape, 23)[kind]
+    return build_masked_t(g, dev, obs, y=np.where(obs, g['y'], np.nan), mask_size=mask_size, **kw), obs
+
+
+def train_side(fixture, kind, mask_size=1):
+    """(f_hat, KL) of the training side from the oracle, once per (fixture, training mask)."""
+    key = (fixture, kind, mask_size)
+    if key not in TRAIN:
+        g = golden(fixture)
+        obs = np.ones(g['y'].shape, dtype=bool) if kind in (None, 'all') else masks_of(*g['y'].shape, 23)[kind]
+        TRAIN[key] = oracle_masked_t(g['y'], obs, g, mask_size)[2:]
+    return TRAIN[key]
+
+
+def points_of(g, n_t, seed):
+    """Permuted training rows plus 0.1 noise, and a q(X*) near their latent points."""
+    rs = np.random.default_rng(seed)
+    idx = np.resize(rs.permutation(g['y'].shape[0]), n_t)
+    y_test = g['y'][idx] + 0.1 * rs.standard_normal((n_t, g['y'].shape[1]))
+    xm = g['x_mean'][idx] + 0.05 * rs.standard_normal((n_t, g['x_mean'].shape[1]))
+    return y_test, xm, rs.uniform(0.3, 1.0, xm.shape)
+
+
+def mask_of(n_t, d, kind, seed):
+    if kind == 'complete':
+        return np.ones((n_t, d), dtype=bool)
+    if kind == 'hole':                                      # a row with nothing observed and a column never observed
+        obs = np.random.default_rng(seed).random((n_t, d)) >= 0.3
+        obs[n_t // 3, :] = False
+        obs[:, 1] = False
+        return obs
+    if n_t == 1:                                            # (masks_of needs more than two rows: its random30 recipe on one row)
+        obs = np.random.default_rng(seed).random((1, d)) >= 0.3
+        assert kind == 'random30' and obs.any() and not obs.all()
+        return obs
+    return masks_of(n_t, d, seed)[kind]
+
+
+def values_of(g, mask_size=1):
+    """The trained values as fp64 torch CPU tensors: z, gamma [T,Q], alpha [T], beta [T], phi [D,T]."""
+    t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64))
+    raw = raw_of(g, mask_size)
+    phi = torch.softmax(t(raw['dp_logits']), dim=-1)
+    if mask_size != 1:
+        phi = torch.repeat_interleave(phi, mask_size, dim=0)
+    return dict(z=t(raw['x_u']), gat=t(softplus(raw['gamma_atoms_raw'])), aat=t(softplus(raw['alpha_atoms_raw']))[:, 0],
+                bat=t(softplus(raw['beta_atoms_raw']))[:, 0], phi=phi, mu=t(raw['x_mean']), s=t(softplus(raw['x_var_raw'])))
+
+
+def reference(v, y_test, obs, xm, xv):
+    """(f_hat*, KL*, d(f_hat* - KL*)/d mean, d/d var): ot.fhat_t per column on its observed rows, as oracle_masked_t composes it."""
+    from oracle import dpgp_oracle_torch as ot
+    mu = torch.tensor(xm, dtype=torch.float64, requires_grad=True)
+    s = torch.tensor(xv, dtype=torch.float64, requires_grad=True)
+    yt = torch.as_tensor(np.where(obs, y_test, 0.0), dtype=torch.float64)
+    f = torch.zeros((), dtype=torch.float64)
+    for d in range(obs.shape[1]):
+        r = np.flatnonzero(obs[:, d])
+        if r.size:
+            f = f + ot.fhat_t(yt[r, d:d + 1], v['z'], mu[r], s[r], v['phi'][d:d + 1], v['gat'], v['aat'], v['bat'])
+    kl = 0.5 * (torch.sum(mu * mu) + torch.sum(s - torch.log(s)) - mu.shape[0] * mu.shape[1])
+    d_mu, d_s = torch.autograd.grad(f - kl, [mu, s])
+    return float(f.detach()), float(kl.detach()), d_mu.numpy(), d_s.numpy()
+
+
+def check_gradient(name, have, want):
+    scale = np.abs(want).max()
+    have = have.cpu().numpy()
+    print('%s: max |err| %.3e of %.3e (bound 1e-8 of that)' % (name, np.abs(have - want).max(), scale))
+    np.testing.assert_allclose(have, want, rtol=0, atol=1e-8 * scale, err_msg=name)
+
+
+#        fixture, training mask, N*, test mask
+CASES = [(0, None, 7, 'complete'), (0, None, 1, 'random30'), (0, 'all', 70, 'random30'), (1, 'random30', 70, 'block'),
+         (1, 'random30', 7, 'odd'), (1, None, 7, 'hole'), (0, 'block', 1, 'complete')]
+
+
+@pytest.mark.parametrize('grouped', ['1', '0'])
+@pytest.mark.parametrize('fix,kind,n_t,test_kind', CASES)
+def test_bound_and_gradient_match_the_oracle(dev, fix, kind, n_t, test_kind, grouped, monkeypatch):
+    """DPGP_GROUPED_PSI plays no role in the test bound: both settings must pass with the same figures."""
+    monkeypatch.setenv('DPGP_GROUPED_PSI', grouped)
+    g = golden(FIXTURES[fix])
+    model, _ = build_t(g, dev, kind)
+    f_train, kl_train = train_side(FIXTURES[fix], kind)
+    y_test, xm, xv = points_of(g, n_t, 100 * fix + n_t)
+    obs = mask_of(n_t, y_test.shape[1], test_kind, 29 + n_t)
+    f, kl, d_mu, d_s = reference(values_of(g), y_test, obs, xm, xv)
+    y_nan = np.where(obs, y_test, np.nan)
+    if test_kind == 'complete':
+        lb, mean, covar, ll = model.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+        assert tuple(covar.shape) == xm.shape + (xm.shape[1],)
+        close(mean, xm, 1e-15)
+        print('f_hat* - KL* %.15g (oracle %.15g); bound %.15g (oracle %.15g)' % (float(ll), f - kl, float(lb), f_train + f - kl_train - kl))
+        np.testing.assert_allclose(float(ll), f - kl, rtol=1e-10)
+        np.testing.assert_allclose(float(lb), f_train + f - kl_train - kl, rtol=1e-10)
+        g_mu, g_s = model.test_latent_gradients(y_test, xm, xv)                      # [N* x Do] with Do = D
+    else:
+        lb, mean, covar, pm, pv = model.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=obs)
+        cols = np.flatnonzero(~obs.all(axis=0))
+        assert list(model.missing_columns) == list(cols) and tuple(pm.shape) == (n_t, cols.size) == tuple(pv.shape)
+        print('bound %.15g (oracle %.15g)' % (float(lb), f_train + f - kl_train - kl))
+        np.testing.assert_allclose(float(lb), f_train + f - kl_train - kl, rtol=1e-10)
+        g_mu, g_s = model.test_latent_gradients(y_nan, xm, xv, observed=obs)
+    patterns = len({obs[:, d].tobytes() for d in range(obs.shape[1]) if obs[:, d].any()})
+    terms = model.prediction_terms
+    assert terms.shape[0] == g['dp_logits'].shape[1] * patterns and terms.dim() == 2
+    check_gradient('d/dmean', g_mu, d_mu)
+    check_gradient('d/dvar', g_s, d_s)
+
+
+def test_first_columns_form_and_all_true_mask(dev):
+    """y_test [N* x Do] is the mask 'first Do columns'; a mask that is True everywhere is allowed in the gradient."""
+    g = golden(FIXTURES[0])
+    model, _ = build_t(g, dev, None)
+    y_test, xm, xv = points_of(g, 7, 3)
+    do = 4
+    obs = np.zeros(y_test.shape, dtype=bool)
+    obs[:, :do] = True
+    _, _, d_mu, d_s = reference(values_of(g), y_test, obs, xm, xv)
+    g_mu, g_s = model.test_latent_gradients(y_test[:, :do], xm, xv)
+    check_gradient('d/dmean (first Do)', g_mu, d_mu)
+    check_gradient('d/dvar (first Do)', g_s, d_s)
+    out = model.predict_missing_data(y_test[:, :do], x_test_mean=xm, x_test_var=xv)
+    assert list(model.missing_columns) == list(range(do, y_test.shape[1])) and tuple(out[3].shape) == (7, y_test.shape[1] - do)
+    full = np.ones(y_test.shape, dtype=bool)
+    _, _, d_mu, d_s = reference(values_of(g), y_test, full, xm, xv)
+    g_mu, g_s = model.test_latent_gradients(y_test, xm, xv, observed=full)
+    check_gradient('d/dmean (all True)', g_mu, d_mu)
+    check_gradient('d/dvar (all True)', g_s, d_s)
+
+
+def test_mask_size_two(dev):
+    g = golden(FIXTURES[1])
+    model, _ = build_t(g, dev, 'random30', mask_size=2)
+    f_train, kl_train = train_side(FIXTURES[1], 'random30', 2)
+    y_test, xm, xv = points_of(g, 7, 11)
+    obs = mask_of(7, y_test.shape[1], 'random30', 31)
+    f, kl, d_mu, d_s = reference(values_of(g, 2), y_test, obs, xm, xv)
+    lb = model.predict_missing_data(np.where(obs, y_test, np.nan), x_test_mean=xm, x_test_var=xv, observed=obs)[0]
+    print('bound %.15g (oracle %.15g)' % (float(lb), f_train + f - kl_train - kl))
+    np.testing.assert_allclose(float(lb), f_train + f - kl_train - kl, rtol=1e-10)
+    g_mu, g_s = model.test_latent_gradients(np.where(obs, y_test, np.nan), xm, xv, observed=obs)
+    check_gradient('d/dmean', g_mu, d_mu)
+    check_gradient('d/dvar', g_s, d_s)
+
+
+def moments_numpy(v, y, train_obs, xm, xv, cols):
+    """The four formulas of the moments in NumPy: per-point Psi statistics from the oracle on single points, np.linalg.solve."""
+    from oracle import dpgp_oracle as orc
+    z, mu, s = v['z'].numpy(), v['mu'].numpy(), v['s'].numpy()
+    gat, aat, bat, phi = v['gat'].numpy(), v['aat'].numpy(), v['bat'].numpy(), v['phi'].numpy()
+    t_, m, n_t = gat.shape[0], z.shape[0], xm.shape[0]
+    dz = z[:, None, :] - z[None, :, :]
+    k_uu = [aat[a] * np.exp(-0.5 * np.einsum('q,ijq->ij', gat[a], dz * dz)) + 1e-8 * np.eye(m) for a in range(t_)]
+    psi1_train = orc.psi1(z, mu, s, gat, aat)                                                  # [T, N, M]
+    psi1_test = orc.psi1(z, xm, xv, gat, aat)                                                  # [T, N*, M]
+    psi2_test = np.stack([orc.psi2(z, xm[i:i + 1], xv[i:i + 1], gat, aat) for i in range(n_t)], axis=1)   # [T, N*, M, M]
+    mean, var = np.zeros((n_t, len(cols))), np.zeros((n_t, len(cols)))
+    cache = {}
+    for j, d in enumerate(cols):
+        r = np.flatnonzero(train_obs[:, d])
+        if r.size and r.tobytes() not in cache:
+            cache[r.tobytes()] = orc.psi2(z, mu[r], s[r], gat, aat)
+        m1, m2 = np.zeros(n_t), np.zeros(n_t)
+        for a in range(t_):
+            if r.size == 0:
+                mean_t, var_t = np.zeros(n_t), np.full(n_t, aat[a] + 1.0 / bat[a])
+            else:
+                big = k_uu[a] + bat[a] * cache[r.tobytes()][a]
+                rt = bat[a] * np.linalg.solve(big, psi1_train[a][r].T @ y[r, d])
+                mean_t = psi1_test[a] @ rt
+                var_t = np.array([aat[a] - np.trace(np.linalg.solve(k_uu[a], psi2_test[a, i]) - np.linalg.solve(big, psi2_test[a, i]))
+                                  + rt @ psi2_test[a, i] @ rt for i in range(n_t)]) - mean_t ** 2 + 1.0 / bat[a]
+            m1 += phi[d, a] * mean_t
+            m2 += phi[d, a] * (var_t + mean_t ** 2)
+        mean[:, j], var[:, j] = m1, m2 - m1 * m1
+    return mean, var
+
+
+@pytest.mark.parametrize('fix,kind,n_t', [(0, None, 7), (1, 'random30', 70), (1, 'odd', 7)])
+def test_moments_match_the_numpy_restatement(dev, fix, kind, n_t):
+    """kind None: complete training data (G = 1 training pattern); random30 / odd: G > 1, odd with a column never observed."""
+    g = golden(FIXTURES[fix])
+    model, train_obs = build_t(g, dev, kind)
+    v = values_of(g)
+    y = np.where(train_obs, g['y'], 0.0)
+    y_test, xm, xv = points_of(g, n_t, 7 + n_t)
+    d = y.shape[1]
+    obs = mask_of(n_t, d, 'random30', 41)
+    want_mean, want_var = moments_numpy(v, y, train_obs, xm, xv, list(range(d)))
+    mean, var = model.predictive_marginals(xm, xv)
+    assert tuple(mean.shape) == (n_t, d) == tuple(var.shape)
+    for name, have, want in (('mean', mean, want_mean), ('var', var, want_var)):
+        print('%s: max |err| %.3e of %.3e (bound 1e-9)' % (name, np.abs(have.cpu().numpy() - want).max(), np.abs(want).max()))
+        close(have, want, 1e-9, name)
+    print('variances in [%.3e, %.3e]' % (float(var.min()), float(var.max())))
+    assert float(var.min()) > 0.0
+    some = [d - 1, 0, 2]
+    mean_s, var_s = model.predictive_marginals(xm, xv, columns=some)
+    close(mean_s, want_mean[:, some], 1e-9, 'mean of chosen columns')
+    close(var_s, want_var[:, some], 1e-9, 'var of chosen columns')
+    out = model.predict_missing_data(np.where(obs, y_test, np.nan), x_test_mean=xm, x_test_var=xv, observed=obs)
+    cols = list(model.missing_columns)
+    close(out[3], want_mean[:, cols], 1e-9, 'predicted_mean')
+    close(out[4], want_var[:, cols], 1e-9, 'predicted_var')
+    assert float(out[4].min()) > 0.0
+
+
+def test_one_atom_equals_bayesian_gp_lvm(dev):
+    """T = 1: the bound, its gradient and the predicted mean are those of bayesian_gp_lvm built from the same values, trained
+    with a mask (bound, gradient) and on complete data (bound, gradient, predicted mean)."""
+    from dp_gp_lvm_amd.models.dp_gp_lvm import dp_gp_lvm_t
+    g = golden('bgplvm_ref_70_9_20_4')
+    p = golden('predb1_bgplvm_70_9_20_4')
+    y, y_test, xm, xv = g['y'], p['y_test'], p['x_test_mean'], p['x_test_var']
+    obs = masks_of(*y.shape, 23)['random30']
+    obs_t = masks_of(*y_test.shape, 29)['random30']
+    y_t_nan = np.where(obs_t, y_test, np.nan)
+    iv = dict(x_mean=g['x_mean'], x_var=softplus(g['x_var_raw']), x_u=g['x_u'], gamma_atoms=softplus(g['gamma_raw']),
+              alpha_atoms=softplus(g['alpha_raw']), beta_atoms=softplus(g['beta_raw']))
+    make = lambda yy, **kw: dp_gp_lvm_t(yy, num_latent_dims=g['x_mean'].shape[1], num_inducing_points=g['x_u'].shape[0],
+                                        truncation_level=1, device=dev, initial_values=iv, **kw)
+    pairs = [('masked', build_masked(g, dev, obs, y=np.where(obs, y, np.nan)), make(np.where(obs, y, np.nan), observed=obs)),
+             ('plain', build_bgplvm(g, dev), make(y))]
+    for tag, one, model in pairs:
+        want = one.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+        have = model.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+        # (the B-GPLVM's fourth output mirrors the reference's "test log-likelihood", f_hat* - f_hat: another quantity)
+        print('%s: bound %.15g (B-GPLVM %.15g)' % (tag, float(have[0]), float(want[0])))
+        np.testing.assert_allclose(float(have[0]), float(want[0]), rtol=1e-10)
+        w_mu, w_s = one.test_latent_gradients(y_t_nan, xm, xv, observed=obs_t)
+        h_mu, h_s = model.test_latent_gradients(y_t_nan, xm, xv, observed=obs_t)
+        check_gradient(tag + ' d/dmean', h_mu, w_mu.cpu().numpy())
+        check_gradient(tag + ' d/dvar', h_s, w_s.cpu().numpy())
+    _, one, model = pairs[1]
+    want = one.predict_missing_data(y_t_nan, x_test_mean=xm, x_test_var=xv, observed=obs_t)
+    have = model.predict_missing_data(y_t_nan, x_test_mean=xm, x_test_var=xv, observed=obs_t)
+    np.testing.assert_allclose(float(have[0]), float(want[0]), rtol=1e-10)
+    print('predicted_mean: max |err| %.3e (bound 1e-9)' % float((have[3] - want[3]).abs().max()))
+    close(have[3], want[3].cpu().numpy(), 1e-9, 'predicted_mean')
+    assert float(have[4].min()) > 0.0
+
+
+@pytest.mark.parametrize('fix', [0, 1])
+def test_one_hot_assignments_equal_the_over_d_model(dev, fix):
+    """Logits of +-50: phi is one-hot to the last bit, so the over-T bound is the over-D model's (precision='f64'), which is pinned
+    to the reference's predict_ref_* fixtures."""
+    from dp_gp_lvm_amd.models.dp_gp_lvm import dp_gp_lvm
+    g = dict(golden(FIXTURES[fix]))
+    raw = raw_of(g)
+    d, t = raw['dp_logits'].shape
+    logits = np.full((d, t), -50.0)
+    logits[np.arange(d), np.arange(d) % t] = 50.0
+    g['dp_logits'] = logits
+    assert np.array_equal(np.sort(torch.softmax(torch.as_tensor(logits), dim=-1).numpy(), axis=1)[:, -1], np.ones(d))
+    model, _ = build_t(g, dev, None)
+    sp = softplus
+    over_d = dp_gp_lvm(g['y'], num_latent_dims=raw['x_mean'].shape[1], num_inducing_points=raw['x_u'].shape[0], truncation_level=t,
+                       alpha_prior_params=np.array([float(g['s_1']), float(g['s_2'])]), device=dev, precision='f64',
+                       initial_values=dict(x_mean=raw['x_mean'], x_var=sp(raw['x_var_raw']), x_u=raw['x_u'], phi_logits=logits,
+                                           gamma_atoms=sp(raw['gamma_atoms_raw']), alpha_atoms=sp(raw['alpha_atoms_raw']),
+                                           beta_atoms=sp(raw['beta_atoms_raw']), gamma_1=sp(raw['gamma_1_raw']),
+                                           gamma_2=sp(raw['gamma_2_raw']), w_1=float(sp(raw['w_1_raw'])), w_2=float(sp(raw['w_2_raw']))))
+    y_test, xm, xv = points_of(g, 7, 5 + fix)
+    want = over_d.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+    have = model.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+    print('bound %.15g (over-D %.15g), test log-likelihood %.15g (%.15g)' % (float(have[0]), float(want[0]), float(have[3]), float(want[3])))
+    np.testing.assert_allclose(float(have[0]), float(want[0]), rtol=1e-10)
+    np.testing.assert_allclose(float(have[3]), float(want[3]), rtol=1e-10)
+
+
+@pytest.mark.parametrize('seed', [5, 6, 7])
+def test_fitting_test_latents_end_to_end(dev, seed):
+    """60 complete training rows of test_gpu_train_masked.synthetic's generator, 20 further rows with a 30 % mask; T = 3, Q = 2,
+    M = 10 from test_training_and_imputation's start (the DP's gamma_1, gamma_2, w_1, w_2, which that test leaves to the random
+    generator, at 1), 300 Adam steps at 0.05, then optimise_test_latents(100, 0.05) from the masked nearest neighbour.
+    Reference figures (CPU oracle + torch Adam on the model's full objective, DP and hyper-prior terms included, seeds 5 / 6 / 7):
+    objective after training 202.5 / 203.2 / 204.4; f_hat* - KL* -219.4 / -204.0 / -208.3 at the start, -104.1 / -102.5 / -101.6
+    after the fit; held-out RMSE 0.271 / 0.267 / 0.276 at the start, 0.171 / 0.115 / 0.176 after the fit, 0.701 / 0.693 / 0.696 for
+    the training column means; every held-out entry within 2 predictive standard deviations; smallest variance 0.106."""
+    from dp_gp_lvm_amd.models.dp_gp_lvm import dp_gp_lvm_t
+    from dp_gp_lvm_amd.utils.expressions import principal_component_analysis as pca
+    y, _ = synthetic(seed)
+    rs = np.random.default_rng(seed + 50)
+    tt = np.sort(rs.uniform(-2.5, 2.5, 20))
+    y_test = np.sin(1.3 * tt[:, None] + np.pi * np.arange(8)[None, :] / 8.0) + 0.05 * rs.standard_normal((20, 8))
+    mask = rs.random((20, 8)) >= 0.3
+    n, d, t = y.shape[0], y.shape[1], 3
+    x0 = pca(y, num_latent_dimensions=2)
+    x0 = (x0 - x0.mean(axis=0)) / x0.std(axis=0)
+    x_u = x0[np.random.default_rng(seed + 100).permutation(n)[:10]]
+    model = dp_gp_lvm_t(y, num_latent_dims=2, num_inducing_points=10, truncation_level=t, device=dev,
+                        alpha_prior_params=np.array([1.0, 1.0]),
+                        initial_values=dict(x_mean=x0, x_var=np.full((n, 2), 0.5), x_u=x_u, phi_logits=np.zeros((d, t)),
+                                            gamma_atoms=np.ones((t, 2)), alpha_atoms=np.ones((t, 1)), beta_atoms=np.ones((t, 1)),
+                                            gamma_1=np.ones(t - 1), gamma_2=np.ones(t - 1), w_1=1.0, w_2=1.0))
+    model.optimise(300, learning_rate=0.05)
+    y_nan = np.where(mask, y_test, np.nan)
+    np.random.seed(seed)
+    start = model.predict_missing_data(y_nan, observed=mask)
+    xm0, xv0 = start[1], torch.diagonal(start[2], dim1=-2, dim2=-1)
+    ll0 = float(start[0] - model.objective_terms[1] + model.objective_terms[2])
+    xm1, xv1 = model.optimise_test_latents(y_nan, 100, learning_rate=0.05, x_test_mean=xm0, x_test_var=xv0, observed=mask)
+    fit = model.predict_missing_data(y_nan, x_test_mean=xm1, x_test_var=xv1, observed=mask)
+    ll1 = float(fit[0] - model.objective_terms[1] + model.objective_terms[2])
+    cols = list(model.missing_columns)
+    held = ~mask[:, cols]
+    truth = y_test[:, cols]
+    rmse = lambda a: float(np.sqrt(np.mean((a.cpu().numpy()[held] - truth[held]) ** 2)))
+    rmse_mean = float(np.sqrt(np.mean((np.broadcast_to(y.mean(axis=0), y_test.shape)[:, cols][held] - truth[held]) ** 2)))
+    zscore = np.abs(fit[3].cpu().numpy() - truth)[held] / np.sqrt(fit[4].cpu().numpy()[held])
+    print('seed %d: f_hat* - KL* %.4f -> %.4f; held-out RMSE %.4f -> %.4f (column means %.4f); within 2 sigma %.3f, 3 sigma %.3f' %
+          (seed, ll0, ll1, rmse(start[3]), rmse(fit[3]), rmse_mean, np.mean(zscore <= 2.0), np.mean(zscore <= 3.0)))
+    assert ll1 > ll0
+    assert rmse(fit[3]) < 0.5 * rmse_mean and rmse(fit[3]) < rmse(start[3])
+    assert float(fit[4].min()) > 0.0 and float(start[4].min()) > 0.0
+    assert np.mean(zscore <= 3.0) >= 0.95
+
+
+def test_argument_checks(dev):
+    import torch.distributed as dist
+    g = golden(FIXTURES[0])
+    model, _ = build_t(g, dev, None)
+    y_test, xm, xv = points_of(g, 7, 1)
+    obs = mask_of(7, y_test.shape[1], 'random30', 2)
+    model.predict_missing_data(y_test, x_test_mean=xm, x_test_var=xv, observed=obs)                  # fine
+    with pytest.raises(AssertionError):
+        model.predict_missing_data(y_test, x_test_mean=xm, x_test_var=xv, observed=obs.astype(np.float64))   # not boolean
+    with pytest.raises(AssertionError):
+        model.test_latent_gradients(y_test, xm, xv, observed=obs[:-1])                               # shape mismatch
+    with pytest.raises(AssertionError):
+        model.optimise_test_latents(y_test[:, :-1], 1, observed=obs)                                 # shape mismatch
+    with pytest.raises(AssertionError):
+        model.predict_missing_data(y_test, x_test_mean=xm, x_test_var=xv, observed=np.ones(obs.shape, dtype=bool))
+    with pytest.raises(AssertionError):
+        model.predict_missing_data(y_test, x_test_mean=xm, x_test_var=xv)                            # Do = D: nothing is missing
+    with pytest.raises(AssertionError):
+        model.predict_new_latent_variables(y_test[:, :-1], x_test_mean=xm, x_test_var=xv)
+    mixed, _ = build_t(g, dev, None, precision='mixed')
+    for call in (lambda: mixed.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv),
+                 lambda: mixed.test_latent_gradients(y_test, xm, xv),
+                 lambda: mixed.optimise_test_latents(y_test, 1),
+                 lambda: mixed.predict_missing_data(y_test, observed=obs),
+                 lambda: mixed.predictive_marginals(xm, xv)):
+        with pytest.raises(AssertionError):
+            call()
+    os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+    os.environ.setdefault('MASTER_PORT', str(29600 + os.getpid() % 1000))
+    created = not dist.is_initialized()
+    if created:
+        dist.init_process_group('gloo', rank=0, world_size=1)
+    try:
+        sharded, _ = build_t(g, dev, None, process_group=dist.group.WORLD)
+        with pytest.raises(AssertionError):
+            sharded.predict_new_latent_variables(y_test, x_test_mean=xm, x_test_var=xv)
+        with pytest.raises(AssertionError):
+            sharded.predict_missing_data(y_test, observed=obs)
+    finally:
+        if created:
+            dist.destroy_process_group()
