@@ -268,7 +268,258 @@ int pw_dispatch(const PwPlan &p, int K, int G, int J, int N, int M, int Q, const
                        : pw_launch<8, QREG>(p, K, G, J, N, M, Q, z, mu, s, gamma, alpha, zfac, c, r, part, st);
 }
 
+// ---- per-entry moments (dpgp_qx_psi_point_moments_f64): the second launch of the operator above replaced by one that also forms
+// the psi1 . r term and finishes.  Workgroup (block of 64 points, chunk of columns j, kernel k), 256 threads; psi1's exponentials
+// are made on the fly, 32 inducing points at a time (their z rows and rows of r staged in LDS), and never stored to memory:
+//   mean[k][n][j] = sum_m psi1_kn[m] r_k[m,j],  psi1_kn[m] = alpha_k prod_q (gamma_q s_nq + 1)^-1/2 exp(-gamma_q (mu_nq - z_mq)^2 / (2 (gamma_q s_nq + 1)))
+//   var[k][n][j]  = alpha_k + 1/beta_k - tr[gidx[k][j]] + quad[j] - mean^2,   tr / quad: pw_kernel's slab partials added in slab order
+// J >= 16 (pm_finish_mfma_kernel): the [64 x 32] [32 x 16 FT] product runs on v_mfma_f64_16x16x4 as in pw_kernel: a wave owns 16
+// points and FT <= 4 column tiles, lane (point i, m = 4 step + (lane >> 4)) evaluates one exponential per step as the A operand.
+// J < 16 (pm_finish_fma_kernel): a tile of 16 columns would be mostly padding; the psi1 tile [64][32] goes through LDS and thread
+// (point, column group) runs plain FMAs over its <= 4 columns.  Both sum over m in ascending order and use no atomics.
+#define PM_MAXFT 4
+
+// the points' mu, -log2(e) gamma / (2 (gamma s + 1)) and alpha prod_q (gamma s + 1)^-1/2 (0 past N) of the block into LDS
+__device__ __forceinline__ void pm_stage_points(int t, int n0, int N, int Q, double al, const double *__restrict__ gk,
+                                                const double *__restrict__ mu, const double *__restrict__ s, double *smu,
+                                                double *siw, double *sc1) {
+    for (int e = t; e < PW_NP * Q; e += 256) {
+        const int i = e / Q, q = e % Q;
+        const bool live = n0 + i < N;
+        const double g = gk[q], sv = live ? s[(size_t)n0 * Q + e] : 0.0;
+        smu[q * PW_NP + i] = live ? mu[(size_t)n0 * Q + e] : 0.0;
+        siw[q * PW_NP + i] = live ? -0.5 * DPGP_LOG2E * g / fma(g, sv, 1.0) : 0.0;
+    }
+    if (t < PW_NP) {
+        double v = 0.0;
+        if (n0 + t < N) {
+            const double *sn = s + (size_t)(n0 + t) * Q;
+            double l = 0.0;
+            for (int q = 0; q < Q; ++q) l += log(fma(gk[q], sn[q], 1.0));
+            v = al * exp(-0.5 * l);
+        }
+        sc1[t] = v;
+    }
+}
+
+// one entry: the slabs added in slab order, the trace term gathered (none for gidx outside [0, G)), the terms combined
+__device__ __forceinline__ void pm_finish_entry(int G, int J, int N, int K, int slabs, int k, int n, int j, double base,
+                                                double mean_v, const int *__restrict__ gidx, const double *__restrict__ part,
+                                                double *__restrict__ mean, double *__restrict__ var) {
+    const size_t C = (size_t)G + J, tot = (size_t)K * N * C, row = ((size_t)k * N + n) * C;
+    const int g = gidx[(size_t)k * J + j];
+    double quad = 0.0, tr = 0.0;
+    for (int sl = 0; sl < slabs; ++sl) quad += part[(size_t)sl * tot + row + G + j];
+    if ((unsigned)g < (unsigned)G)
+        for (int sl = 0; sl < slabs; ++sl) tr += part[(size_t)sl * tot + row + g];
+    const size_t o = ((size_t)k * N + n) * J + j;
+    mean[o] = mean_v;
+    var[o] = base - tr + quad - mean_v * mean_v;
+}
+
+template <int FT>
+__global__ __launch_bounds__(256) void pm_finish_mfma_kernel(int K, int G, int J, int N, int M, int Q, int ntn, int nchunks,
+                                                             int nft_plan, int slabs, const double *__restrict__ z,
+                                                             const double *__restrict__ mu, const double *__restrict__ s,
+                                                             const double *__restrict__ gamma, const double *__restrict__ alpha,
+                                                             const double *__restrict__ r, const int *__restrict__ gidx,
+                                                             const double *__restrict__ beta, const double *__restrict__ part,
+                                                             double *__restrict__ mean, double *__restrict__ var) {
+    constexpr int CW = 16 * FT, RS = CW + PW_WPAD;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    double *smu = reinterpret_cast<double *>(smem_raw);    // [Q][64]
+    double *siw = smu + (size_t)Q * PW_NP;                  // [Q][64]
+    double *sc1 = siw + (size_t)Q * PW_NP;                  // [64]
+    double *zt = sc1 + PW_NP;                               // [32][Q]  z rows of the tile
+    double *rT = zt + (size_t)PW_TILE * Q;                  // [32][RS] r rows of the tile, the chunk's columns
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int nt = blockIdx.x % ntn, rest = blockIdx.x / ntn, chunk = rest % nchunks, k = rest / nchunks;
+    const int tiles16 = (J + 15) / 16, nft = min(nft_plan, tiles16 - chunk * nft_plan), j0 = 16 * chunk * nft_plan;
+    const int n0 = nt * PW_NP;
+    const double *zk = z + (size_t)k * M * Q, *rk = r + (size_t)k * M * J;
+    const double al = alpha[k];
+    pm_stage_points(t, n0, N, Q, al, gamma + (size_t)k * Q, mu, s, smu, siw, sc1);
+    __syncthreads();
+    const int pi = wave * 16 + (lane & 15), kk = lane >> 4;
+    const bool wave_live = n0 + wave * 16 < N;
+    const double c1 = sc1[pi];
+    f64x4 acc[FT];
+#pragma unroll
+    for (int ct = 0; ct < FT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int m0 = 0; m0 < M; m0 += PW_TILE) {
+        const int nr = min(PW_TILE, M - m0);
+        __syncthreads();                                       // (previous tile consumed)
+        for (int e = t; e < PW_TILE * Q; e += 256) zt[e] = e / Q < nr ? zk[(size_t)m0 * Q + e] : 0.0;
+        for (int e = t; e < PW_TILE * CW; e += 256) {
+            const int p = e / CW, cl = e % CW, j = j0 + cl;
+            rT[p * RS + cl] = (p < nr && j < J && cl < 16 * nft) ? rk[(size_t)(m0 + p) * J + j] : 0.0;
+        }
+        __syncthreads();
+        if (!wave_live) continue;                              // (wave-uniform)
+        for (int st = 0; st < (nr + 3) >> 2; ++st) {
+            const int mm = 4 * st + kk;                        // (a row past M: z = 0 gives a finite a, its r row is 0)
+            const double *zq = zt + (size_t)mm * Q;
+            double e = 0.0;
+            for (int q = 0; q < Q; ++q) {
+                const double d = smu[q * PW_NP + pi] - zq[q];
+                e = fma(siw[q * PW_NP + pi] * d, d, e);
+            }
+            const double a = c1 * dpgp_exp2(e);
+            const double *rrow = rT + mm * RS + (lane & 15);
+#pragma unroll
+            for (int ct = 0; ct < FT; ++ct)
+                if (ct < nft) acc[ct] = Mfma<double>::mma(a, rrow[16 * ct], acc[ct]);
+        }
+    }
+    if (!wave_live) return;
+    const double base = al + 1.0 / beta[k];
+#pragma unroll
+    for (int ct = 0; ct < FT; ++ct)
+        if (ct < nft) {
+            const int j = j0 + 16 * ct + (lane & 15);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int n = n0 + wave * 16 + Mfma<double>::row(lane, rr);
+                if (n < N && j < J) pm_finish_entry(G, J, N, K, slabs, k, n, j, base, acc[ct][rr], gidx, part, mean, var);
+            }
+        }
+}
+
+__global__ __launch_bounds__(256) void pm_finish_fma_kernel(int K, int G, int J, int N, int M, int Q, int ntn, int slabs,
+                                                            const double *__restrict__ z, const double *__restrict__ mu,
+                                                            const double *__restrict__ s, const double *__restrict__ gamma,
+                                                            const double *__restrict__ alpha, const double *__restrict__ r,
+                                                            const int *__restrict__ gidx, const double *__restrict__ beta,
+                                                            const double *__restrict__ part, double *__restrict__ mean,
+                                                            double *__restrict__ var) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    double *smu = reinterpret_cast<double *>(smem_raw);    // [Q][64]
+    double *siw = smu + (size_t)Q * PW_NP;                  // [Q][64]
+    double *sc1 = siw + (size_t)Q * PW_NP;                  // [64]
+    double *zt = sc1 + PW_NP;                               // [32][Q]
+    double *rT = zt + (size_t)PW_TILE * Q;                  // [32][16]  (J < 16)
+    double *sP = rT + PW_TILE * 16;                         // [64][33]  psi1 of the tile
+    const int t = threadIdx.x, nt = blockIdx.x % ntn, k = blockIdx.x / ntn, n0 = nt * PW_NP;
+    const int pt = t & 63, jg = t >> 6;                     // the thread's point and its columns jg, jg + 4, jg + 8, jg + 12
+    const double *zk = z + (size_t)k * M * Q, *rk = r + (size_t)k * M * J;
+    const double al = alpha[k];
+    pm_stage_points(t, n0, N, Q, al, gamma + (size_t)k * Q, mu, s, smu, siw, sc1);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int m0 = 0; m0 < M; m0 += PW_TILE) {
+        const int nr = min(PW_TILE, M - m0);
+        __syncthreads();                                       // (the points are staged; previous tile consumed)
+        for (int e = t; e < PW_TILE * Q; e += 256) zt[e] = e / Q < nr ? zk[(size_t)m0 * Q + e] : 0.0;
+        for (int e = t; e < PW_TILE * 16; e += 256) {
+            const int p = e >> 4, j = e & 15;
+            rT[e] = (p < nr && j < J) ? rk[(size_t)(m0 + p) * J + j] : 0.0;
+        }
+        __syncthreads();
+        for (int e = t; e < PW_NP * PW_TILE; e += 256) {
+            const int i = e & 63, p = e >> 6;
+            double v = 0.0;
+            if (p < nr) {
+                const double *zq = zt + (size_t)p * Q;
+                double x = 0.0;
+                for (int q = 0; q < Q; ++q) {
+                    const double d = smu[q * PW_NP + i] - zq[q];
+                    x = fma(siw[q * PW_NP + i] * d, d, x);
+                }
+                v = sc1[i] * dpgp_exp2(x);
+            }
+            sP[i * PW_FSTRIDE + p] = v;
+        }
+        __syncthreads();
+        for (int p = 0; p < nr; ++p) {
+            const double a = sP[pt * PW_FSTRIDE + p];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = fma(a, rT[p * 16 + jg + 4 * i], acc[i]);
+        }
+    }
+    const int n = n0 + pt;
+    if (n >= N) return;
+    const double base = al + 1.0 / beta[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = jg + 4 * i;
+        if (j < J) pm_finish_entry(G, J, N, K, slabs, k, n, j, base, acc[i], gidx, part, mean, var);
+    }
+}
+
+struct PmPlan { int mfma, nft, nchunks, ft; };
+PmPlan pm_plan(int J) {
+    PmPlan p;
+    p.mfma = J >= 16;
+    const int tiles16 = dpgp_ceil_div(J, 16);
+    p.nft = dpgp_ceil_div(tiles16, dpgp_ceil_div(tiles16, PM_MAXFT));   // chunks of equal width
+    p.nchunks = dpgp_ceil_div(tiles16, p.nft);
+    p.ft = p.nft <= 1 ? 1 : p.nft <= 2 ? 2 : 4;
+    return p;
+}
+
+size_t pm_lds(int Q, const PmPlan &p) {
+    const size_t pts = (size_t)2 * Q * PW_NP + PW_NP + (size_t)PW_TILE * Q;
+    return sizeof(double) * (pts + (p.mfma ? (size_t)PW_TILE * (16 * p.ft + PW_WPAD) : (size_t)PW_TILE * 16 + PW_NP * PW_FSTRIDE));
+}
+
+template <typename KERNEL, typename... ARGS>
+int pm_launch(KERNEL kernel, unsigned grid, size_t lds, hipStream_t st, ARGS... args) {
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return DPGP_ERR_LAUNCH;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, args...);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
+
 }  // namespace
+
+extern "C" size_t dpgp_qx_psi_point_moments_workspace_bytes(int K, int G, int J, int N, int M, int Q) {
+    return dpgp_qx_psi_pointwise_workspace_bytes(K, G, J, N, M, Q);     // pw_kernel's slab partials and nothing else
+}
+
+extern "C" int dpgp_qx_psi_point_moments_f64(int K, int G, int J, int N, int M, int Q, const double *z, const double *mu,
+                                             const double *s, const double *gamma, const double *alpha, const double *zfac,
+                                             const double *c, const double *r, const int *gidx, const double *beta, double *mean,
+                                             double *var, void *ws, size_t ws_bytes, void *stream) {
+    if (K < 1) return -1;
+    if (G < 1) return -2;
+    if (J < 1) return -3;
+    if (N < 1) return -4;
+    if (M < 1) return -5;
+    if (Q < 1 || Q > DPGP_QX_PSI_MAX_Q) return -6;
+    if (!z) return -7;
+    if (!mu) return -8;
+    if (!s) return -9;
+    if (!gamma) return -10;
+    if (!alpha) return -11;
+    if (!c) return -13;
+    if (!r) return -14;
+    if (!gidx) return -15;
+    if (!beta) return -16;
+    if (!mean) return -17;
+    if (!var) return -18;
+    if (!ws) return -19;
+    const size_t need = dpgp_qx_psi_point_moments_workspace_bytes(K, G, J, N, M, Q);
+    if (need == 0 || ws_bytes < need) return -20;
+    hipStream_t st = (hipStream_t)stream;
+    const PwPlan p = pw_plan(K, G, J, N, M, Q);
+    double *part = static_cast<double *>(ws);
+    const int rc = Q <= PW_QR ? pw_dispatch<true>(p, K, G, J, N, M, Q, z, mu, s, gamma, alpha, zfac, c, r, part, st)
+                              : pw_dispatch<false>(p, K, G, J, N, M, Q, z, mu, s, gamma, alpha, zfac, c, r, part, st);
+    if (rc) return rc;
+    const PmPlan f = pm_plan(J);
+    const size_t lds = pm_lds(Q, f);
+    if (!f.mfma)
+        return pm_launch(pm_finish_fma_kernel, (unsigned)((long)p.ntn * K), lds, st, K, G, J, N, M, Q, p.ntn, p.slabs, z, mu, s, gamma,
+                         alpha, r, gidx, beta, (const double *)part, mean, var);
+    const unsigned grid = (unsigned)((long)p.ntn * f.nchunks * K);
+#define PM_MFMA(FT)                                                                                                               \
+    pm_launch(pm_finish_mfma_kernel<FT>, grid, lds, st, K, G, J, N, M, Q, p.ntn, f.nchunks, f.nft, p.slabs, z, mu, s, gamma, alpha, r, \
+              gidx, beta, (const double *)part, mean, var)
+    return f.ft == 1 ? PM_MFMA(1) : f.ft == 2 ? PM_MFMA(2) : PM_MFMA(4);
+#undef PM_MFMA
+}
 
 extern "C" size_t dpgp_qx_psi_pointwise_workspace_bytes(int K, int G, int J, int N, int M, int Q) {
     if (!pw_shape_ok(K, G, J, N, M, Q)) return 0;

@@ -455,6 +455,35 @@ def dp_gp_lvm(y_train,
             torch.eye(num_test_points, dtype=TORCH_DTYPE, device=device)
         return predicted_mean, predicted_covar
 
+    def _marginals_at(cols, xt, st_):
+        """Per-entry predictive moments (mean, var) [N* x len(cols)] of the output dims `cols` at q(X*): every column is its own
+        mixed kernel (gamma_d, alpha_d, beta_d of the last evaluation), so the operator runs in its K = len(cols), G = J = 1
+        layout: c_d = K_d^-1 - P_d, P_d = (K_d + beta_d Psi2_d)^-1, r_d = beta_d P_d Psi1_d^T y_d; no Psi1* [K, N*, M] is formed.
+        The trace term enters with the derived sign, - tr((K_d^-1 - P_d) Psi2*(n)).  _predictive_moments' tr_term is the same
+        quantity, + tr((K_d^-1 - P_d) Psi2*) summed over the test points, and is ADDED there (following the reference), so
+            sum_n var(n,d) = predicted_covar[d,0,0] + (N* - 1)/beta_d - 2 tr_term_d."""
+        m_ = num_inducing_points
+        idx = torch.as_tensor(np.asarray(cols), device=device)
+        f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
+        gu, au, bu = f64(buf['gamma'][idx]), f64(buf['alpha'][:, 0][idx]), f64(buf['beta'][:, 0][idx])
+        z, mu, s_train = f64(x_u.detach()), f64(x_mean.detach()), f64(F.softplus(x_var_raw).detach())
+        psi_1 = ops.psi1(z, mu, s_train, gu, au)                                 # [K x N x M] (training)
+        psi_2 = ops.psi2(z, mu, s_train, gu, au)
+        k_uu = ops.ard_rbf_gram(z, None, gu, au, bu, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)
+        l_uu, _ = ops.potrf_batched(k_uu)
+        li = ops.tril_inverse_batched(l_uu)
+        tm = ops.matmul(ops.matmul(li, psi_2), li.transpose(1, 2))
+        l_a, _ = ops.potrf_batched((bu[:, None, None] * tm + torch.eye(m_, dtype=TORCH_DTYPE, device=device)).contiguous())
+        r0 = ops.matmul(ops.tril_inverse_batched(l_a), li)
+        pm = ops.matmul(r0.transpose(1, 2), r0)                                  # P_d
+        y_u = _t(np.asarray(y_train)[:, np.asarray(cols)]).to(TORCH_DTYPE).transpose(0, 1).contiguous()[:, :, None]
+        r = bu[:, None, None] * ops.matmul(pm, ops.matmul(psi_1.transpose(1, 2), y_u))           # [K x M x 1]
+        c = (ops.matmul(li.transpose(1, 2), li) - pm)[:, None]
+        gidx = torch.zeros((len(cols), 1), dtype=torch.int32, device=device)
+        mean, var = ops.qx_psi_point_moments(z[None].expand(len(cols), -1, -1).contiguous(), f64(xt), f64(st_), gu, au, c.contiguous(),
+                                             r.contiguous(), gidx, bu)
+        return mean[:, :, 0].transpose(0, 1).contiguous(), var[:, :, 0].transpose(0, 1).contiguous()
+
     class DP_GP_LVM(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508)."""
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
@@ -647,8 +676,22 @@ def dp_gp_lvm(y_train,
             return xt, F.softplus(raw)
 
         @staticmethod
+        def predictive_marginals(x_test_mean, x_test_var, columns=None):
+            """(mean, var), each [N* x len(columns)]: the per-entry predictive moments of the output dims `columns` (default: all
+            D) at q(X*) = (x_test_mean, x_test_var [N* x Q]) under each column's mixed kernel of this evaluation, observation
+            noise 1/beta_d included; one call of ops.qx_psi_point_moments (see _marginals_at for the formulas and for the sign
+            of the trace term against predict_missing_data's array).  fp64, one GPU, torch.no_grad."""
+            assert not sharded and world == 1, 'prediction paths run on one GPU'
+            cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
+            assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+            val = lambda a: _t(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+            evaluate()
+            with torch.no_grad():
+                return _marginals_at(cols, val(x_test_mean), val(x_test_var))
+
+        @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
-                                 observed=None):
+                                 observed=None, marginal_variance=False):
             """Mirror of dp_gp_lvm.py:311-500: y_test [N* x Do] holds the FIRST Do output dims of the test points; returns
             (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
             for the remaining Du = D - Do dims at the initial q(X*) (see predict_new_latent_variables).  Composed of the
@@ -661,7 +704,10 @@ def dp_gp_lvm(y_train,
             KL(q(X*)) runs over all N* rows.  The Du predicted dims are the columns with at least one unobserved entry,
             ascending (property missing_columns); q(X*) starts at the masked nearest neighbour (a row with nothing observed
             at 0).  AssertionError for a non-boolean mask, a shape mismatch, a mask that is True everywhere, or
-            reference_compat=True."""
+            reference_compat=True.
+
+            marginal_variance=True (extension): the last entry is the per-entry variance [N* x Du] of predictive_marginals on
+            the predicted dims in place of the [Du x N* x N*] array."""
             if observed is not None:
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
@@ -671,6 +717,8 @@ def dp_gp_lvm(y_train,
                     pred_state['terms'] = bound.terms
                     lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
                     predicted_mean, predicted_covar = _predictive_moments(pred_state['missing_columns'], xt, st_)
+                    if marginal_variance:
+                        predicted_covar = _marginals_at(pred_state['missing_columns'], xt, st_)[1]
                 return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
             assert not sharded and world == 1, 'prediction paths run on one GPU'
             y_test = np.asarray(y_test, dtype=np.float64)
@@ -688,6 +736,9 @@ def dp_gp_lvm(y_train,
             # predictive mean / covariance of the unobserved dims (:426-498), output dims do .. D-1 only
             pred_state['missing_columns'] = np.arange(do, num_dimensions)
             predicted_mean, predicted_covar = _predictive_moments(pred_state['missing_columns'], xt, st_)
+            if marginal_variance:
+                with torch.no_grad():
+                    predicted_covar = _marginals_at(pred_state['missing_columns'], xt, st_)[1]
             return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
 
     return DP_GP_LVM()
@@ -1132,11 +1183,18 @@ def dp_gp_lvm_t(y_train,
             if callback is not None:
                 callback(it)
 
-    def _impute_training_data():
+    def _impute_training_data(return_variance=False):
         """A model trained with observed=: y_train [N x D] with every unobserved entry (n, d) replaced by the mixture's posterior mean
         sum_t phi_td beta_t Psi1_t[n,:] (K_t + beta_t Psi2_{t,p(d)})^-1 Psi1_t^T y_d (Psi2 and y_d over the rows at which d was
-        observed); observed entries as given; a column never observed gets 0."""
+        observed); observed entries as given; a column never observed gets 0.  return_variance=True: (filled, var), var [N x D]
+        the per-entry variance of predictive_marginals at the training q(X) at the unobserved entries and 0 at the observed ones;
+        filled is the same tensor either way."""
         assert masked is not None, 'impute_training_data needs a model trained with observed='
+        if return_variance:
+            filled = _impute_training_data()
+            with torch.no_grad():
+                _, var = _moments().at(x_mean.detach(), F.softplus(x_var_raw).detach(), _columns_arg(None))
+                return filled, torch.where(torch.as_tensor(train_obs, device=device), torch.zeros_like(var), var)
         with torch.no_grad():
             gat, aat, bat = F.softplus(gamma_atoms_raw), F.softplus(sig_var_atoms_raw)[:, 0], F.softplus(beta_atoms_raw)[:, 0]
             phi = torch.softmax(dp_model.raw['logits'], dim=-1)

@@ -32,7 +32,8 @@ from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .test_bound import _TestBound, _as_device
 from .slot_bound import kernel_slots
-from .masked_bound import MaskedBayesianGPLVM, MaskedMRD
+from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
+from . import marginals as _marginals
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -495,6 +496,20 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         with torch.no_grad():
             return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
 
+    def _train_marginals():
+        """The training side of the per-entry moments (models/marginals.py), formed once per call: the model's own masked bound,
+        or the same bound with an all-True mask on a model trained on complete data."""
+        z, g, a, b = _frozen()
+        bound = inner.bound if train_obs is not None else \
+            _MaskedBound(y_np, np.ones((num_samples, num_dimensions), dtype=bool), dev_)
+        return _marginals.of_masked_bound(bound, z[0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(), g[0], a[0], b[0],
+                                          num_dimensions)
+
+    def _marginals_at(xt, st_, columns):
+        with torch.no_grad():
+            mean, var = _train_marginals().at(xt, st_, _marginals.columns_arg(columns, num_dimensions, dev_))
+        return mean[0], var[0]
+
     class BayesianGPLVM(Trainable):
         """Accessors as in the reference (gaussian_process.py:276-340), and its two prediction methods (:329-538) with the same
         keywords and return tuples as dp_gp_lvm's, plus test_latent_gradients / optimise_test_latents / prediction_terms.
@@ -517,8 +532,18 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), f_test - f_hat
 
         @staticmethod
+        def predictive_marginals(x_test_mean, x_test_var, columns=None):
+            """(mean, var), each [N* x len(columns)]: the per-entry predictive moments of the output dims `columns` (default: all
+            D) at q(X*) = (x_test_mean, x_test_var [N* x Q]), observation noise 1/beta included (formulas in models/marginals.py;
+            one call of ops.qx_psi_point_moments).  Works on a model trained on complete data and on one trained with
+            observed= (column d then sees the training rows at which it was observed; a column never observed in training has
+            mean 0 and variance alpha + 1/beta): optimise_test_latents(..., observed=) followed by this is how a mask-trained
+            model predicts at test points.  fp64, torch.no_grad."""
+            return _marginals_at(_as_device(x_test_mean, dev_), _as_device(x_test_var, dev_), columns)
+
+        @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
-                                 observed=None):
+                                 observed=None, marginal_variance=False):
             """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
                 (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
             for the remaining Du = D - Do dims, at the initial q(X*) of predict_new_latent_variables (nearest neighbour over
@@ -534,8 +559,12 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             difference over each row's observed columns; a row with nothing observed starts at 0).  AssertionError for a
             non-boolean mask, a shape mismatch, a mask that is True everywhere, or reference_compat=True.
 
-            On a model trained with observed= the per-pattern predictive moments are not built: NotImplementedError (the
-            training data's own gaps are filled by impute_training_data)."""
+            marginal_variance=True (extension): the last entry is the per-entry variance [N* x Du] of predictive_marginals on
+            the predicted dims in place of the [Du x N* x N*] array (one scalar per dim plus a diagonal, the same for every
+            test point).
+
+            On a model trained with observed= this method is not built: NotImplementedError (predictive_marginals gives the
+            moments at test points, impute_training_data fills the training data's own gaps)."""
             if train_obs is not None:
                 raise NotImplementedError('predict_missing_data is not built for a model trained with observed=: use '
                                           'impute_training_data for the gaps of the training data')
@@ -552,7 +581,8 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
                     plain = _TestBound(z, g, a, b, [torch.zeros((y0.shape[0], 1), dtype=TORCH_DTYPE, device=dev_)], dev_)
                     means, covars = _predictive_moments(plain, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
                                                         [_as_device(y_np[:, mc], dev_)], xt, st_)
-                return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covars[0]
+                covar = _marginals_at(xt, st_, mc)[1] if marginal_variance else covars[0]
+                return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covar
             y_test = _check_observed(y_test, False)
             do = y_test.shape[1]
             pred_state['missing_columns'] = np.arange(do, num_dimensions)
@@ -562,7 +592,8 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             with torch.no_grad():
                 means, covars = _predictive_moments(bound, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
                                                     [_as_device(y_np[:, do:], dev_)], xt, st_)
-            return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covars[0]
+            covar = _marginals_at(xt, st_, pred_state['missing_columns'])[1] if marginal_variance else covars[0]
+            return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means[0], covar
 
         @staticmethod
         def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
@@ -593,12 +624,18 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             return None if b is None else b.terms
 
         @staticmethod
-        def impute_training_data():
+        def impute_training_data(return_variance=False):
             """A model trained with observed=: y_train [N x D] with every unobserved entry (n, d) replaced by the posterior mean
             beta Psi1[n,:] (K_uu + beta Psi2_d)^-1 Psi1^T y_d (Psi2_d and y_d over the rows at which d was observed); observed
-            entries as given, a never-observed column 0.  fp64 device tensor."""
+            entries as given, a never-observed column 0.  fp64 device tensor.  return_variance=True: (filled, var), var
+            [N x D] the per-entry predictive variance of predictive_marginals at the training q(X) at the unobserved entries
+            and 0 at the observed ones; filled is the same tensor either way."""
             assert train_obs is not None, 'impute_training_data needs a model trained with observed='
-            return inner.impute()
+            filled = inner.impute()
+            if not return_variance:
+                return filled
+            var = _marginals_at(raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(), None)[1]
+            return filled, _marginals.unobserved_variance(var, train_obs)
 
         @property
         def objective_terms(self):
@@ -917,6 +954,25 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         with torch.no_grad():
             return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
 
+    def _train_marginals():
+        """The training side of the per-entry moments of every view (models/marginals.py), formed once per call: the model's own
+        masked bound, or the same bound with all-True masks on a model trained on complete views."""
+        z, g, a, b = _frozen(inner)
+        bound = masked.bound if masked is not None else \
+            _MaskedViewsBound(views_np, [np.ones(v.shape, dtype=bool) for v in views_np], dev_)
+        flat = lambda ts: torch.stack([t.reshape(-1) for t in ts]).contiguous()
+        return _marginals.of_masked_views_bound(bound, torch.stack(z).contiguous(), x_mean_t.detach(),
+                                                F.softplus(x_var_raw).detach(), flat(g), flat(a).reshape(-1), flat(b).reshape(-1),
+                                                num_dimensions)
+
+    def _marginals_at(xt, st_, views, columns=None):
+        """Two lists (means, variances) over `views`; columns[i]: the columns of views[i] (default all)."""
+        with torch.no_grad():
+            train = _train_marginals()
+            out = [train[v].at(xt, st_, _marginals.columns_arg(None if columns is None else columns[i], num_dimensions[v], dev_))
+                   for i, v in enumerate(views)]
+        return [o[0][0] for o in out], [o[1][0] for o in out]
+
     class ManifoldRelevanceDetermination(Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
         test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
@@ -935,8 +991,21 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             return _bound_at(views_test, xt, st_), xt, torch.diag_embed(st_)
 
         @staticmethod
+        def predictive_marginals(x_test_mean, x_test_var, views=None):
+            """(means, variances): two lists with one tensor [N* x D_v] per view of `views` (default: all V, in order): the
+            per-entry predictive moments at q(X*) = (x_test_mean, x_test_var [N* x Q]), observation noise 1/beta_v included
+            (formulas in models/marginals.py; one call of ops.qx_psi_point_moments per view).  Works on a model trained on
+            complete views and on one trained with observed= (column d of view v then sees the training rows at which it was
+            observed; a column never observed in training has mean 0 and variance alpha_v + 1/beta_v):
+            optimise_test_latents(..., observed=) followed by this is how a mask-trained model predicts at test points.
+            fp64, torch.no_grad."""
+            vs = list(range(num_views)) if views is None else [int(v) for v in views]
+            assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
+            return _marginals_at(_as_device(x_test_mean, dev_), _as_device(x_test_var, dev_), vs)
+
+        @staticmethod
         def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
-                                 observed=None):
+                                 observed=None, marginal_variance=False):
             """views_test: the FIRST Vo < V views of the test points (gaussian_process.py:834-990).  Returns
                 (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_means, predicted_covars)
             with one entry per unobserved view v = Vo .. V-1: mean [N* x D_v], covariance [D_v x N* x N*].
@@ -954,8 +1023,11 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             starts at 0).  AssertionError for lists of the wrong length, non-boolean masks, shape mismatches, masks that are
             True everywhere, no True entry anywhere, or reference_compat=True.
 
-            On a model trained with observed= the per-pattern predictive moments are not built: NotImplementedError (the
-            training data's own gaps are filled by impute_training_data)."""
+            marginal_variance=True (extension): predicted_covars holds, per returned view, the per-entry variance [N* x Du] of
+            predictive_marginals on the predicted columns in place of the [Du x N* x N*] array.
+
+            On a model trained with observed= this method is not built: NotImplementedError (predictive_marginals gives the
+            moments at test points, impute_training_data fills the training data's own gaps)."""
             if masked is not None:
                 raise NotImplementedError('predict_missing_data is not built for a model trained with observed=: use '
                                           'impute_training_data for the gaps of the training data')
@@ -973,6 +1045,8 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                     means, covars = _predictive_moments(bound_u, list(range(len(mv_))), x_mean_t.detach(),
                                                         F.softplus(x_var_raw).detach(),
                                                         [_as_device(views_np[v][:, c], dev_) for v, c in zip(mv_, mc)], xt, st_)
+                if marginal_variance:
+                    covars = _marginals_at(xt, st_, mv_, mc)[1]
                 return f_hat + f_test - kl - kl_t, xt, torch.diag_embed(st_), means, covars
             views_test = _check_views(views_test, True)
             vo = len(views_test)
@@ -986,6 +1060,8 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                 c_index = [len(ku) - 1] * len(ku) if reference_compat else list(range(len(ku)))
                 means, covars = _predictive_moments(bound_u, c_index, x_mean_t.detach(), F.softplus(x_var_raw).detach(),
                                                     [_as_device(v, dev_) for v in views_np[vo:]], xt, st_)
+            if marginal_variance:
+                covars = _marginals_at(xt, st_, pred_state['missing_views'])[1]
             return lb, xt, torch.diag_embed(st_), means, covars
 
         @staticmethod
@@ -1013,12 +1089,19 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             return pred_state.get('missing_columns')
 
         @staticmethod
-        def impute_training_data():
+        def impute_training_data(return_variance=False):
             """A model trained with observed=: a list of V fp64 device tensors [N x D_v], view v with every unobserved entry
             (n, d) replaced by the posterior mean beta_v Psi1_v[n,:] (K_uu_v + beta_v Psi2_d)^-1 Psi1_v^T y_d (Psi2_d and y_d
-            over the rows at which d was observed); observed entries as given, a never-observed column 0."""
+            over the rows at which d was observed); observed entries as given, a never-observed column 0.
+            return_variance=True: (filled, variances), variances a list of V tensors [N x D_v]: the per-entry predictive
+            variance of predictive_marginals at the training q(X) at the unobserved entries and 0 at the observed ones; filled
+            is the same list either way."""
             assert masked is not None, 'impute_training_data needs a model trained with observed='
-            return masked.impute()
+            filled = masked.impute()
+            if not return_variance:
+                return filled
+            _, variances = _marginals_at(x_mean_t.detach(), F.softplus(x_var_raw).detach(), list(range(num_views)))
+            return filled, [_marginals.unobserved_variance(v, o) for v, o in zip(variances, train_obs)]
 
         @property
         def objective_terms(self):

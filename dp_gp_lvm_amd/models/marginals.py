@@ -1,0 +1,86 @@
+"""
+Per-entry predictive moments of the sparse GP models at a test-point q(X*) = (mu, s), on ONE operator call
+(ops.qx_psi_point_moments, csrc/qx_psi_point.hip).  With p(d) the training row pattern of output column d (the rows at which d was
+observed; one pattern for complete training data), P_p = (K_uu + beta Psi2_p)^-1 and r_d = beta P_p(d) Psi1^T y_d over those rows,
+
+    mean(n,d) = psi1*(n) . r_d
+    var(n,d)  = alpha + 1/beta - tr((K_uu^-1 - P_p(d)) Psi2*(n)) + r_d^T Psi2*(n) r_d - mean(n,d)^2
+
+psi1*(n), Psi2*(n) test point n's own statistics.  Observation noise 1/beta is included; a column never observed in training has
+r_d = 0 and no trace term: mean 0, variance alpha + 1/beta.  The training side (the chain of models/masked_bound.py) is formed once
+per _Marginals; summed over the test points the variance is the reference-shaped array's entry,
+    sum_n var(n,d) = covar[d,0,0] + (N* - 1)/beta                            (gaussian_process._predictive_moments).
+"""
+import numpy as np
+import torch
+
+from .. import ops
+from ..utils.types import TORCH_DTYPE
+
+
+class _Marginals:
+    """K kernels' training side: z [K,M,Q], gamma [K,Q], alpha [K], beta [K], zfac [K,M,M] or None, c [K,G,M,M] = K_uu^-1 - P per
+    pattern, r [K,M,D] the posterior weights per output column and gidx [K,D] (int32) each column's pattern, -1: never observed."""
+
+    def __init__(self, z, gamma, alpha, beta, zfac, c, r, gidx):
+        self.z, self.gamma, self.alpha, self.beta = z.contiguous(), gamma.contiguous(), alpha.contiguous(), beta.contiguous()
+        self.zfac = None if zfac is None else zfac.contiguous()
+        self.c, self.r, self.gidx = c.contiguous(), r.contiguous(), gidx.contiguous()
+
+    def at(self, mu, s, cols=None):
+        """(mean, var) [K, N*, len(cols)] at q(X*) = (mu, s); cols: a long tensor of output columns on the device (default all)."""
+        r, gidx = self.r, self.gidx
+        if cols is not None:
+            r, gidx = r.index_select(2, cols).contiguous(), gidx.index_select(1, cols).contiguous()
+        return ops.qx_psi_point_moments(self.z, mu.contiguous(), s.contiguous(), self.gamma, self.alpha, self.c, r, gidx, self.beta,
+                                        zfac=self.zfac)
+
+
+def columns_arg(columns, d, device):
+    cols = np.arange(d) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
+    assert cols.size >= 1 and cols.min() >= 0 and cols.max() < d, 'columns must be output dims in [0, D)'
+    return torch.as_tensor(cols, dtype=torch.long, device=device)
+
+
+def one_kernel(c, y, beta, slots, columns, d):
+    """The _Marginals (K = 1) of the kernel that the slots `slots` (indices into the chain's batch) share: c the dict of
+    _MaskedBound.chain / _MaskedViewsBound.chain, y [B,N,Dmax] the bound's zero-filled outputs, beta the kernel's noise precision
+    (one element), columns[i] the output columns of slot slots[i] (their places in y), d the number of output columns."""
+    device, m = y.device, c['r0'].shape[1]
+    sel = torch.as_tensor(slots, dtype=torch.long, device=device)
+    take = lambda t: t.index_select(0, sel).contiguous()
+    r0 = take(c['r0'])
+    pm = ops.matmul(r0.transpose(1, 2).contiguous(), r0)                                         # P_p [P, M, M]
+    v = ops.matmul(take(c['psi_1']).transpose(1, 2).contiguous(), take(y))                      # Psi1^T Y_p [P, M, Dmax]
+    be = beta.reshape(1)
+    rb = be[:, None, None] * ops.matmul(pm, v)
+    r = torch.zeros((m, d), dtype=TORCH_DTYPE, device=device)
+    gidx = torch.full((d,), -1, dtype=torch.int32, device=device)
+    for p, cols in enumerate(columns):
+        ct = torch.as_tensor(np.asarray(cols), dtype=torch.long, device=device)
+        r[:, ct] = rb[p, :, :len(cols)]
+        gidx[ct] = p
+    i0 = slots[0]
+    return _Marginals(c['z'][i0:i0 + 1], c['gamma'][i0:i0 + 1], c['alpha'][i0:i0 + 1].reshape(1), be, c['zfac'][i0:i0 + 1],
+                      (take(c['kinv']) - pm)[None], r[None], gidx[None])
+
+
+def of_masked_bound(bound, z, mu, s, gamma, alpha, beta, d):
+    """bayesian_gp_lvm: bound a masked_bound._MaskedBound (an all-True mask for complete training data)."""
+    c = bound.chain(z, mu, s, gamma, alpha, beta)
+    return one_kernel(c, bound.y, beta, list(range(bound.b)), [cols for cols, _ in bound.groups], d)
+
+
+def of_masked_views_bound(bound, z, mu, s, gamma, alpha, beta, dims):
+    """MRD: bound a masked_bound._MaskedViewsBound, z [V,M,Q], gamma [V,Q], alpha [V], beta [V]; one _Marginals per view."""
+    c = bound.chain(z, mu, s, gamma, alpha, beta)
+    out = []
+    for v, d in enumerate(dims):
+        slots = [i for i, (vv, _, _) in enumerate(bound.slots) if vv == v]
+        out.append(one_kernel(c, bound.y, beta[v], slots, [bound.slots[i][1] for i in slots], d))
+    return out
+
+
+def unobserved_variance(var, observed):
+    """var [N x D] at the unobserved entries, 0 at the observed ones."""
+    return torch.where(torch.as_tensor(observed, device=var.device), torch.zeros_like(var), var)

@@ -315,14 +315,7 @@ def qx_psi_param_adjoint_grouped(z, mu, s, gamma, alpha, g1, g2, weights, zfac=N
     return d_z, d_gamma, d_alpha
 
 
-def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
-    """Per-point Psi2 contractions (dpgp_qx_psi_pointwise_f64): with psi2_kn [M,M] test point n's own term of kernel k's Psi2 at
-    q(X) = (mu, s) [N,Q] (kernels z [K,M,Q], gamma [K,Q], alpha [K] as in qx_psi_stats_grouped), returns
-        tr [K,N,G]   = sum_{m,m'} c[k,g,m,m'] psi2_kn[m,m']            c [K,G,M,M], any matrices
-        quad [K,N,J] = sum_{m,m'} r[k,m,j] r[k,m',j] psi2_kn[m,m']     r [K,M,J]
-    without forming psi2_kn in memory; fixed summation order, the same bits on every run.  c and r: float64 tensors on the
-    inputs' device (TypeError otherwise), of these shapes (ValueError otherwise)."""
-    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+def _qx_point_args(c, r, k, m, mu):
     for name, a in (('c', c), ('r', r)):
         if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % name)
@@ -332,7 +325,51 @@ def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
         raise ValueError('c must be [K x G x M x M] with G >= 1, got %s' % (tuple(c.shape),))
     if r.dim() != 3 or r.shape[0] != k or r.shape[1] != m or r.shape[2] < 1:
         raise ValueError('r must be [K x M x J] with J >= 1, got %s' % (tuple(r.shape),))
-    c, r = c.contiguous(), r.contiguous()
+    return c.contiguous(), r.contiguous()
+
+
+def qx_psi_point_moments(z, mu, s, gamma, alpha, c, r, gidx, beta, zfac=None):
+    """Per-entry predictive moments (dpgp_qx_psi_point_moments_f64): with psi1_kn [M], psi2_kn [M,M] test point n's own
+    statistics of kernel k at q(X) = (mu, s) [N,Q] (kernels, c [K,G,M,M] and r [K,M,J] as in qx_psi_pointwise), returns
+        mean [K,N,J] = sum_m psi1_kn[m] r[k,m,j]
+        var [K,N,J]  = alpha_k + 1/beta_k - <c[k,gidx[k,j]], psi2_kn> + r_kj^T psi2_kn r_kj - mean^2
+    from one operator call; neither psi1 [K,N,M] nor psi2_kn is formed in memory.  gidx [K,J]: an int32 tensor, any value outside
+    [0, G) means no trace term; beta [K] fp64.  Fixed summation order, the same bits on every run."""
+    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    c, r = _qx_point_args(c, r, k, m, mu)
+    g, j = c.shape[1], r.shape[2]
+    if not isinstance(gidx, torch.Tensor) or gidx.dtype != torch.int32:
+        raise TypeError('gidx must be an int32 torch.Tensor')
+    if not isinstance(beta, torch.Tensor) or beta.dtype != torch.float64:
+        raise TypeError('beta must be a float64 torch.Tensor')
+    if gidx.device != mu.device or beta.device != mu.device:
+        raise RuntimeError('gidx and beta must live on the device of the inputs')
+    if tuple(gidx.shape) != (k, j):
+        raise ValueError('gidx must be [K x J], got %s' % (tuple(gidx.shape),))
+    if tuple(beta.shape) != (k,):
+        raise ValueError('beta must be [K], got %s' % (tuple(beta.shape),))
+    gidx, beta = gidx.contiguous(), beta.contiguous()
+    mean = torch.empty((k, n, j), dtype=torch.float64, device=mu.device)
+    var = torch.empty_like(mean)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_point_moments_workspace_bytes(k, g, j, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_point_moments_f64(k, g, j, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                               alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), c.data_ptr(),
+                                               r.data_ptr(), gidx.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr(),
+                                               ws.data_ptr(), wsb, _stream()), 'dpgp_qx_psi_point_moments_f64')
+    return mean, var
+
+
+def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
+    """Per-point Psi2 contractions (dpgp_qx_psi_pointwise_f64): with psi2_kn [M,M] test point n's own term of kernel k's Psi2 at
+    q(X) = (mu, s) [N,Q] (kernels z [K,M,Q], gamma [K,Q], alpha [K] as in qx_psi_stats_grouped), returns
+        tr [K,N,G]   = sum_{m,m'} c[k,g,m,m'] psi2_kn[m,m']            c [K,G,M,M], any matrices
+        quad [K,N,J] = sum_{m,m'} r[k,m,j] r[k,m',j] psi2_kn[m,m']     r [K,M,J]
+    without forming psi2_kn in memory; fixed summation order, the same bits on every run.  c and r: float64 tensors on the
+    inputs' device (TypeError otherwise), of these shapes (ValueError otherwise)."""
+    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    c, r = _qx_point_args(c, r, k, m, mu)
     g, j = c.shape[1], r.shape[2]
     tr = torch.empty((k, n, g), dtype=torch.float64, device=mu.device)
     quad = torch.empty((k, n, j), dtype=torch.float64, device=mu.device)

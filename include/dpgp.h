@@ -231,6 +231,25 @@ int dpgp_qx_psi_pointwise_f64(int K, int G, int J, int N, int M, int Q, const do
                               const double *gamma, const double *alpha, const double *zfac, const double *c, const double *r,
                               double *tr, double *quad, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Per-entry predictive moments on the same contractions (csrc/qx_psi_point.hip).  Inputs as above, plus gidx[K][J] (int32: the
+ *      trace column of output column j; any value outside [0, G) means "no trace term", a column never observed in training) and
+ *      beta[K].  With psi1_kn[m], psi2_kn[m,m'] test point n's own statistics of kernel k and tr_kn[g] = <c_kg, psi2_kn>:
+ *        mean[K][N][J] = sum_m psi1_kn[m] r_k[m,j]
+ *        var[K][N][J]  = alpha_k + 1/beta_k - tr_kn[gidx[k][j]] + r_kj^T psi2_kn r_kj - mean^2
+ *      Two launches: the pair kernel of dpgp_qx_psi_pointwise_f64 (its partial sums go to the workspace as there), then one
+ *      kernel that forms psi1's exponentials on the fly, multiplies them with r (on the fp64 matrix pipe for J >= 16, plain FMA
+ *      below), adds the slab partials in slab order, gathers the trace term and combines.  Nothing of size K N M, N M M or
+ *      pairs x J is written to memory; no atomics, the same bits on every run.  Ranges as above.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, G -2, J -3, N -4, M -5, Q -6, z -7, mu -8, s -9,
+ *      gamma -10, alpha -11, (zfac: nullable, no code), c -13, r -14, gidx -15, beta -16, mean -17, var -18, ws -19,
+ *      ws_bytes too small -20.
+ *   ws: dpgp_qx_psi_point_moments_workspace_bytes(K,G,J,N,M,Q) (a host function; 0 for a shape out of range). */
+size_t dpgp_qx_psi_point_moments_workspace_bytes(int K, int G, int J, int N, int M, int Q);
+int dpgp_qx_psi_point_moments_f64(int K, int G, int J, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                  const double *gamma, const double *alpha, const double *zfac, const double *c, const double *r,
+                                  const int *gidx, const double *beta, double *mean, double *var, void *ws, size_t ws_bytes,
+                                  void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);
