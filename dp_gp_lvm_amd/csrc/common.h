@@ -55,12 +55,13 @@ template <> struct Mfma<double> {
 
 // base-2 exponential: fp32 -> the bare v_exp_f32 (results below 2^-126 flush to 0, which is what a sum of such terms
 // next to O(1) terms needs); fp64 -> 2^x = 2^k 2^f, k = rint(x), |f| <= 1/2, 2^f by the degree-12 Taylor polynomial of
-// exp(f ln 2) (truncation (ln2 / 2)^13 / 13! = 1.7e-16 relative), 2^k by an exponent-field add; arguments below -1020 give
-// 0, above 1020 inf, NaN stays NaN (the kernels only exponentiate log-densities <= ~0).  About half the
+// exp(f ln 2) (truncation (ln2 / 2)^13 / 13! = 1.7e-16 relative), 2^k by an exponent-field add; arguments below -1022 (results
+// below the smallest normal number; down to there k + the exponent field of 2^f stays >= 1) give 0, above 1020 inf, NaN stays
+// NaN (the kernels only exponentiate log-densities <= ~0).  About half the
 // instructions of the device library's exp2, which handles the full range and denormal results.
 __device__ __forceinline__ float dpgp_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ double dpgp_exp2(double x) {
-    const double xc = x < -1020.0 ? -1020.0 : x;
+    const double xc = x < -1022.0 ? -1022.0 : x;
     const double k = __builtin_rint(xc), f = xc - k;
     const double c[13] = {
         1.00000000000000000e+00,
@@ -81,7 +82,7 @@ __device__ __forceinline__ double dpgp_exp2(double x) {
     for (int i = 11; i >= 0; --i) p = __builtin_fma(p, f, c[i]);
     long long bits = __builtin_bit_cast(long long, p) + ((long long)(int)k << 52);
     if (!(x <= 1020.0)) return (x != x) ? x : __builtin_inf();     // NaN stays NaN, overflow -> inf
-    return x < -1020.0 ? 0.0 : __builtin_bit_cast(double, bits);
+    return x < -1022.0 ? 0.0 : __builtin_bit_cast(double, bits);
 }
 // fp64 base-2 exponential for the streaming hot loops (one exp2 per (n, m, m')): 2^x = 2^k T[j] 2^r with x = k + j/64 + r,
 // |r| <= 1/128.  k and j come out of ONE addition of 1.5 * 2^46 (the sum's ulp is 1/64, so its low dword is round(64 x) in

@@ -11,7 +11,8 @@
 //     A_n[m, 0:Q] = X[n,:] * z[m,:],  A_n[m,Q] = P[n,m],  A_n[m,Q+1] = 1
 //     B_n[0:Q,m'] = z[m',:]^T,        B_n[Q,m'] = 1,      B_n[Q+1,m'] = P[n,m']
 //   evaluated with v_mfma_{f32,f64}_16x16x4; then psi2[m,m'] += exp2(E_n[m,m']) element-wise in registers.
-//   (identical to the reference formula: tests/test_psi2.py checks against the literal oracle)
+//   (identical to the reference formula: tests/test_gpu_kernels.py and tests/test_gpu_psi2_edges.py check against the
+//    literal oracle and its longdouble restatement)
 //
 // Decomposition: workgroup = (patch of the lower triangle, b, n-split); patch = PT x PT tiles of 16x16 (64x64 fp32,
 // 32x32 fp64); the 4 waves of a workgroup work on the SAME patch and split the n of every 32-row tile 4 ways
@@ -1726,8 +1727,14 @@ int psi2_nsplit(int B, int N, int M) {
     // list schedule, in rows, is minimised over ns <= 8 (>= 128 rows per split).  Config 2 (B = 64): 8 splits are 1536 + 64
     // workgroups = 3 rounds and a 4th one for the chain tasks (4 x 256 rows); 5 splits are 1024 = 2 rounds of 448 rows.
     if (const char *e = getenv("DPGP_PSI2_NS")) {                // (experiments only)
-        const int v = atoi(e);
-        if (v >= 1 && v <= 8 && N / v >= 1) return v;
+        int v = atoi(e);
+        if (v >= 1 && v <= 8) {
+            // stepped down to the largest count for which no split of ceil(N / v) rows starts behind the last observation:
+            // the pair-tile kernel stores from inside its chunk loop and would leave the slab of an empty split unwritten
+            // (the rule below keeps >= 128 rows per split)
+            while (v > 1 && (long long)(v - 1) * dpgp_ceil_div(N, v) >= N) --v;
+            return v;
+        }
     }
     const int np64 = dpgp_ceil_div(M, 64), patches = np64 * (np64 + 1) / 2, R = 512, CK = 250;
     const long long nchain = (M <= 128) ? B : 0;
@@ -1937,7 +1944,7 @@ int launch_psi2_partial(int B, int N, int M, int Q, const TIN *z, const TIN *mu,
     }
     // fp32 results: f16-split operands on the matrix pipe unless the exact-fp32 MFMA kernel is asked for; the pair-tile
     // kernel (psi2_pairs.hip) by default, the per-observation patch kernel on request
-    // (more than 20 latent dims: 12 K-steps per pair tile leave no room for resident column operands; patch kernel)
+    // (more than 21 latent dims: 12 K-steps per pair tile leave no room for resident column operands; patch kernel)
     if (sizeof(T) == 4 && (algo == DPGP_ALGO_PATCH_F16 || (algo != DPGP_ALGO_MFMA_F32 && psi2_pairs_ksteps(Q) > 8)))
         return Psi2F16Dispatch<TIN, T>::run(B, N, M, Q, z, mu, s, gamma, alpha, part, ns, task, consts, consts_ready, st);
     if (sizeof(T) == 4 && algo != DPGP_ALGO_MFMA_F32)

@@ -294,7 +294,8 @@ __global__ __launch_bounds__(64 * NW, PP_WAVES) void psi2_pairs_kernel(int N, in
                 for (int q = 0; q < 3 * Q; ++q) dst[q] = 0u;
             }
             // c'' is the largest number in the exponent and common to a whole row: three f16 pieces (33 bits) where a K slot
-            // is free (always, except Q = 5), so that its rounding does not show in every term of the observation
+            // is free (always, except Q = 5 and Q = 21, where 6Q + 2 fills the 16 KS slots exactly and c'' is carried in two
+            // pieces, 22 bits), so that its rounding does not show in every term of the observation
             cc = dpgp_pin(cc);
             const _Float16 ch = (_Float16)cc;
             const float r1 = dpgp_pin(cc - (float)ch);
