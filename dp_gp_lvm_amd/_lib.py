@@ -87,6 +87,9 @@ SIGNATURES = {
     'dpgp_qx_psi_pointwise_f64': (_i, [_i] * 6 + [_vp] * 10 + [_vp, _sz, _vp]),
     'dpgp_qx_psi_point_moments_workspace_bytes': (_sz, [_i] * 6),
     'dpgp_qx_psi_point_moments_f64': (_i, [_i] * 6 + [_vp] * 12 + [_vp, _sz, _vp]),
+    'dpgp_psi2_weighted_f64': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    'dpgp_elbo_grad_psi_weighted_f64': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                             _vp, _vp, _vp, _vp]),
     'dpgp_gemm_strided_f64': (_i, [_i, _i, _i, _i, _d, _vp, _ll, _ll, _ll, _vp, _ll, _ll, _ll, _d, _vp, _ll, _ll, _ll, _vp]),
 }
 for _t in ('f32', 'f64'):

@@ -352,10 +352,12 @@ extern "C" int dpgp_elbo_grad_psi(int D, int N, int M, int Q, const double *y, i
 }
 // g_psi1 != NULL: a full adjoint [D][N][Mp] of Psi1 replaces the rank-1 form g_v[d][a] y[n][d] (then y may be NULL and g_v is
 // not read): the over-T model's data-fit term couples every atom with all columns of y.  Mixed precision only.
-extern "C" int dpgp_elbo_grad_psi_ex(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu,
-                                     const double *s, const double *gamma, const double *alpha, const double *g_psi2,
-                                     const double *w_kuu, const double *g_v, const double *g_psi1, int prec, void *ws,
-                                     size_t ws_bytes, double *d_mu, double *d_s, double *d_z, double *d_gamma, void *stream) {
+// wts != NULL (DPGP_PREC_F64, through dpgp_elbo_grad_psi_weighted_f64 only): weights [D][N] on the Psi2 term.
+static int elbo_grad_psi_impl(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu,
+                              const double *s, const double *gamma, const double *alpha, const double *g_psi2,
+                              const double *w_kuu, const double *g_v, const double *g_psi1, int prec, void *ws,
+                              size_t ws_bytes, double *d_mu, double *d_s, double *d_z, double *d_gamma, void *stream,
+                              const double *wts) {
     if (D <= 0) return -1;
     if (N <= 0) return -2;
     if (M <= 0) return -3;
@@ -385,7 +387,22 @@ extern "C" int dpgp_elbo_grad_psi_ex(int D, int N, int M, int Q, const double *y
                               d_mu, d_s, d_z, d_gamma, (hipStream_t)stream, nullptr, nullptr, nullptr, fast ? 1 : 0);
     if (dpgp_round_up(M, 16) > 128) return -30;
     return launch_psi_grad<double>(D, N, M, Q, y, ldy, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, (double *)ws, d_mu, d_s,
-                                   d_z, d_gamma, 1, (hipStream_t)stream);
+                                   d_z, d_gamma, 1, (hipStream_t)stream, wts);
+}
+extern "C" int dpgp_elbo_grad_psi_ex(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu,
+                                     const double *s, const double *gamma, const double *alpha, const double *g_psi2,
+                                     const double *w_kuu, const double *g_v, const double *g_psi1, int prec, void *ws,
+                                     size_t ws_bytes, double *d_mu, double *d_s, double *d_z, double *d_gamma, void *stream) {
+    return elbo_grad_psi_impl(D, N, M, Q, y, ldy, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, g_psi1, prec, ws, ws_bytes, d_mu,
+                              d_s, d_z, d_gamma, stream, nullptr);
+}
+extern "C" int dpgp_elbo_grad_psi_weighted_f64(int D, int N, int M, int Q, const double *y, int ldy, const double *z,
+                                               const double *mu, const double *s, const double *gamma, const double *alpha,
+                                               const double *w, const double *g_psi2, const double *w_kuu, const double *g_v,
+                                               void *ws, size_t ws_bytes, double *d_mu, double *d_s, double *d_z,
+                                               double *d_gamma, void *stream) {
+    return elbo_grad_psi_impl(D, N, M, Q, y, ldy, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, nullptr, DPGP_PREC_F64, ws,
+                              ws_bytes, d_mu, d_s, d_z, d_gamma, stream, w);
 }
 
 extern "C" int dpgp_elbo_fhat_ex(int D, int N, int M, int Q, const double *y, int ldy, const double *z,

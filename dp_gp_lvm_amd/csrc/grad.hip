@@ -13,6 +13,7 @@
 // One 256-thread workgroup per output dim, fp64, LDS-resident (M <= 128): B is assembled, factored (potrf_lds) and
 // inverted in place (potri_lds) in LDS; K^-1 P K^-1 is two passes of 16x16 fp64 MFMA tile products over the symmetric
 // matrices in global memory.  It runs after a forward evaluation on the same workspace (K, K^-1 and the Psi slabs are there).
+#include <type_traits>
 #include "internal.h"
 #include "linalg_dev.h"
 #include "psi2_consts.h"
@@ -261,7 +262,12 @@ template int launch_chain_grad<double>(int, int, int, const double *, int, const
 __device__ __forceinline__ float pg_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 __device__ __forceinline__ double pg_exp(double x) { return exp(x); }
 // QP: latent dims padded to a multiple of 4 (compile time, so that the per-thread q-arrays stay in registers)
-template <typename TC, int QP>
+// WEIGHTED (dpgp_elbo_grad_psi_weighted_f64): observation n of output dim d enters the Psi2 term with the weight wts[d][n] >= 0
+// (the sums R and T of its w[n,a,m'] are scaled: everything after them is linear in them); the Psi1 term is governed by y alone.
+// An iteration whose two observations have weight 0 and y = 0 contributes nothing: it writes its zeros to the d/dmu, d/dS
+// partials and skips the pair loop (the condition is read from global memory by every thread alike: uniform for the workgroup,
+// as the barriers inside the loop need).
+template <typename TC, int QP, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, 2) void psi_grad_kernel(int D, int N, int M, int Mp, int Q, const double *__restrict__ y, int ldy,
                                                        const double *__restrict__ z, const double *__restrict__ mu,
                                                        const double *__restrict__ s, const double *__restrict__ gamma,
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void psi_grad_kernel(int D, int N, int M, i
                                                        const double *__restrict__ WK, const double *__restrict__ Gv,
                                                        int n_per_split, int do_psi2, double *__restrict__ dmu_part,
                                                        double *__restrict__ ds_part, double *__restrict__ dz_part,
-                                                       double *__restrict__ dg_part) {
+                                                       double *__restrict__ dg_part, const double *__restrict__ wts) {
     // do_psi2 == 0: the Psi2 and Psi1 terms are left to psi2_grad_kernel (psi2.hip, matrix pipe) and psi1_grad_*_kernel; this
     // kernel then only does the K_uu term (no pass over the observations, d/dmu and d/dS partials not written)
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -322,6 +328,23 @@ __global__ __launch_bounds__(256, 2) void psi_grad_kernel(int D, int N, int M, i
     for (int n0 = nbeg; n0 < nend; n0 += 2) {
         const int n = n0 + nl;
         const bool live = (n < nend);
+        TC wn = 1;
+        if constexpr (WEIGHTED) {
+            const bool two = (n0 + 1 < nend);
+            const double wa = wts[(size_t)d * N + n0], wb = two ? wts[(size_t)d * N + n0 + 1] : 0.0;
+            const double ya = y[(size_t)n0 * ldy + d], yb = two ? y[(size_t)(n0 + 1) * ldy + d] : 0.0;
+            if (wa == 0.0 && wb == 0.0 && ya == 0.0 && yb == 0.0) {
+                if (t < 2 * Q) {
+                    const int l = t / Q, q = t - l * Q, nn = n0 + l;
+                    if (nn < nend) {
+                        dmu_part[((size_t)d * N + nn) * Q + q] = 0.0;
+                        ds_part[((size_t)d * N + nn) * Q + q] = 0.0;
+                    }
+                }
+                continue;
+            }
+            wn = (TC)(nl ? wb : wa);
+        }
         // per-observation factors, one thread per (observation, q): a2 = gamma / den2, a1 = gamma / den1, ...
         if (t < 2 * Q) {
             const int l = t / Q, q = t - l * Q, nn = n0 + l;
@@ -380,6 +403,11 @@ __global__ __launch_bounds__(256, 2) void psi_grad_kernel(int D, int N, int M, i
                 R += w;
 #pragma unroll
                 for (int q = 0; q < QP; ++q) T[q] += w * zm[q];
+            }
+            if constexpr (WEIGHTED) {
+                R *= wn;
+#pragma unroll
+                for (int q = 0; q < QP; ++q) T[q] *= wn;
             }
             TC e1 = dpgp_log(al) - (TC)0.5 * l1;
 #pragma unroll
@@ -915,7 +943,8 @@ size_t psi_grad_ws_bytes_kuu(int D, int M, int Q) {
 template <typename TC>
 int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu, const double *s,
                     const double *gamma, const double *alpha, const double *GP, const double *WK, const double *Gv,
-                    double *ws, double *dmu, double *ds, double *dz, double *dgamma, int do_psi2, hipStream_t st) {
+                    double *ws, double *dmu, double *ds, double *dz, double *dgamma, int do_psi2, hipStream_t st,
+                    const double *wts) {
     const int Mp = dpgp_round_up(M, 16);
     if (Mp > 128) return -30;                                  // first version: one thread per row of the M x M statistics
     int ns = 1;
@@ -928,8 +957,17 @@ int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const 
     const int QPr = 4 * dpgp_ceil_div(Q, 4);
     const size_t lds = sizeof(TC) * ((size_t)(Mp * Mp > 2 * Q * 128 ? Mp * Mp : 2 * Q * 128) + (size_t)Mp * QPr + PG_RED_ELEMS(Q) + (size_t)12 * Q + 256 + 32 + (size_t)2 * (7 * Q + 2));
     void (*kern)(int, int, int, int, int, const double *, int, const double *, const double *, const double *, const double *,
-                 const double *, const double *, const double *, const double *, int, int, double *, double *, double *, double *) = nullptr;
-    switch (QPr / 4) {
+                 const double *, const double *, const double *, const double *, int, int, double *, double *, double *, double *,
+                 const double *) = nullptr;
+    if (wts && (!do_psi2 || !std::is_same<TC, double>::value)) return -15;     // the weighted form is the fp64 one with all three terms
+    if constexpr (std::is_same<TC, double>::value) {
+        if (wts) switch (QPr / 4) {
+#define CASE(k) case k: kern = psi_grad_kernel<TC, 4 * k, true>; break;
+            CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+        }
+    }
+    if (!wts) switch (QPr / 4) {
 #define CASE(k) case k: kern = psi_grad_kernel<TC, 4 * k>; break;
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
@@ -940,7 +978,7 @@ int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const 
             hipSuccess)
         return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, dim3(D, ns), dim3(256), lds, st, D, N, M, Mp, Q, y, ldy, z, mu, s, gamma, alpha, GP, WK, Gv,
-                       nper, do_psi2, dmu_part, ds_part, dz_part, dg_part);
+                       nper, do_psi2, dmu_part, ds_part, dz_part, dg_part, wts);
     DPGP_LAUNCH_CHECK();
     const size_t nq = (size_t)N * Q, mq = (size_t)M * Q, dq = (size_t)D * Q;
     if (do_psi2) {
@@ -964,7 +1002,7 @@ int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const 
 }
 template int launch_psi_grad<float>(int, int, int, int, const double *, int, const double *, const double *, const double *,
                                     const double *, const double *, const double *, const double *, const double *, double *,
-                                    double *, double *, double *, double *, int, hipStream_t);
+                                    double *, double *, double *, double *, int, hipStream_t, const double *);
 template int launch_psi_grad<double>(int, int, int, int, const double *, int, const double *, const double *, const double *,
                                      const double *, const double *, const double *, const double *, const double *,
-                                     double *, double *, double *, double *, double *, int, hipStream_t);
+                                     double *, double *, double *, double *, double *, int, hipStream_t, const double *);

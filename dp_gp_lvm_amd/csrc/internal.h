@@ -116,7 +116,9 @@ size_t psi_grad_ws_bytes_kuu(int D, int M, int Q);     // (K_uu term only: do_ps
 template <typename TC>
 int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu, const double *s,
                     const double *gamma, const double *alpha, const double *GP, const double *WK, const double *Gv,
-                    double *ws, double *dmu, double *ds, double *dz, double *dgamma, int do_psi2, hipStream_t st);
+                    double *ws, double *dmu, double *ds, double *dz, double *dgamma, int do_psi2, hipStream_t st,
+                    const double *wts = nullptr);
+// wts != nullptr (TC = double, do_psi2 = 1): per-(output dim, observation) weights [D][N] on the Psi2 term
 // do_psi2 = 0: only the K_uu term (dz, dgamma written; dmu, ds untouched) -- the other two terms then come from:
 // grad.hip: the Psi1 term (mixed precision): dmu, ds overwritten; dz, dgamma added to.  ws: psi1_grad_ws_elems doubles,
 // stage: reduce_rows_stage_elems(max(N Q, M Q, D Q)) doubles, consts as below

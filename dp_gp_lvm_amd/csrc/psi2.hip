@@ -74,12 +74,18 @@ template <typename T, int KS, int PT> struct Psi2Lds {
 // a private LDS region; for every chunk of NR of its rows it (A) computes the per-(n,q) factors, (B) the P[n, .] rows
 // of both column blocks, (C) runs the MFMA + exp2 accumulation.  No workgroup barrier separates the phases, so the
 // waves drift apart and one wave's VALU phases overlap another wave's matrix-core phase on the same SIMD.
-template <typename TIN, typename T, int KS, int PT, bool DIAG>
+//
+// WEIGHTED (compile time; dpgp_psi2_weighted_f64): row n of batch entry b enters the sum with the weight wts[b][n] >= 0.  The
+// exponent of row n is P[n,m] + P[n,m'] + ..., and every P row carries the row constant C_n once, so 1/2 log2 w added to C_n
+// is the weight; a row with w = 0 is given the constants of a row past the end of the split (exp2(-huge) = 0 exactly).  All
+// of it sits in phase A: the MFMA / exp2 sequences of phase C are the same straight-line code.  A chunk none of whose NR rows
+// carries weight skips phases A to C behind one wave-uniform branch (the cost follows the observed entries).
+template <typename TIN, typename T, int KS, int PT, bool DIAG, bool WEIGHTED = false>
 __device__ __forceinline__ void psi2_patch(int N, int M, int Q, int B, const TIN *__restrict__ z,
                                            const TIN *__restrict__ mu, const TIN *__restrict__ s,
                                            const TIN *__restrict__ gamma, const TIN *__restrict__ alpha,
                                            T *__restrict__ part, int Mp, int n_per_split, int b, int sp, int pi, int pj,
-                                           unsigned char *smem_raw) {
+                                           unsigned char *smem_raw, const TIN *__restrict__ wts = nullptr) {
     typedef Psi2Lds<T, KS, PT> G;
     constexpr int PS = G::PS, KP = G::KP, ZLD = G::ZLD, PLD = G::PLD, NR = G::NR;
     typedef typename Mfma<T>::acc_t acc_t;
@@ -136,6 +142,14 @@ __device__ __forceinline__ void psi2_patch(int N, int M, int Q, int B, const TIN
     constexpr int CPL = (NCOL + 63) / 64;            // ... per lane
 
     for (int nc = nbeg + wv; nc < nend; nc += 4 * NR) {     // this wave's chunk: rows nc, nc+4, ..., nc+4(NR-1)
+        if constexpr (WEIGHTED) {
+            bool any = false;
+            if (lane < NR) {
+                const int n = nc + 4 * lane;
+                any = (n < nend) && (wts[(size_t)b * N + n] > (TIN)0);
+            }
+            if (__ballot(any) == 0) continue;               // wave-uniform: nothing of this chunk has been read or written yet
+        }
         // ---- phase A: per-(row,k) factors ----
 #pragma unroll
         for (int e0 = 0; e0 < NR * KP; e0 += 64) {
@@ -144,7 +158,16 @@ __device__ __forceinline__ void psi2_patch(int N, int M, int Q, int B, const TIN
                 const int r = e / KP, k = e - r * KP, n = nc + 4 * r;
                 T vx = 0, vw = 0, vt = 0, vc = 0;
                 if (k < Q) {
-                    if (n < nend) {
+                    bool in_split = n < nend;
+                    T hlw = 0;                       // 1/2 log2 w_n
+                    if constexpr (WEIGHTED) {
+                        if (in_split) {
+                            const T wn = (T)wts[(size_t)b * N + n];
+                            in_split = wn > (T)0;
+                            hlw = (T)(0.5 * DPGP_LOG2E) * dpgp_log(in_split ? wn : (T)1);
+                        }
+                    }
+                    if (in_split) {
                         const T g = gq[k];
                         const T sv = (T)s[(size_t)n * Q + k];
                         const T mc = (T)mu[(size_t)n * Q + k] - zc[k];
@@ -154,6 +177,7 @@ __device__ __forceinline__ void psi2_patch(int N, int M, int Q, int B, const TIN
                         vw = (T)(0.25 * DPGP_LOG2E) * w;
                         vt = (T)2 * mc;
                         vc = (T)DPGP_LOG2E * ((T)0.5 * w * mc * mc - (T)0.25 * dpgp_log(den));
+                        if constexpr (WEIGHTED) vc += (k == 0) ? hlw : (T)0;
                     } else {
                         vc = (T)-1.0e30;             // rows past the end of this split contribute exp2(-huge) = 0
                     }
@@ -1071,14 +1095,14 @@ __global__ __launch_bounds__(256, PSI2_F16_WAVES) void psi2_f16_kernel(int N, in
 #endif
 }
 
-template <typename TIN, typename T, int KS, int PT>
+template <typename TIN, typename T, int KS, int PT, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void psi2_mfma_kernel(int N, int M, int Q, int B, const TIN *__restrict__ z,
                                                         const TIN *__restrict__ mu, const TIN *__restrict__ s,
                                                         const TIN *__restrict__ gamma, const TIN *__restrict__ alpha,
                                                         T *__restrict__ part, int Mp, int n_per_split,
-                                                        ChainKTask task) {
+                                                        ChainKTask task, const TIN *__restrict__ wts) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int zoff = task.ws ? 1 : 0;
+    const int zoff = (!WEIGHTED && task.ws) ? 1 : 0;             // (the weighted launch carries no K_uu task)
     if (zoff && blockIdx.z == 0) {
         if (blockIdx.y == 0) chain_k_task<1>(task, blockIdx.x, smem_raw);
         return;
@@ -1086,19 +1110,23 @@ __global__ __launch_bounds__(256) void psi2_mfma_kernel(int N, int M, int Q, int
     int b, sp, pi, pj;
     psi2_block_coords((Mp + 16 * PT - 1) / (16 * PT), zoff, b, sp, pi, pj);
     if (pi == pj)
-        psi2_patch<TIN, T, KS, PT, true>(N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, n_per_split, b, sp, pi, pj, smem_raw);
+        psi2_patch<TIN, T, KS, PT, true, WEIGHTED>(N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, n_per_split, b, sp, pi, pj, smem_raw,
+                                                   wts);
     else
-        psi2_patch<TIN, T, KS, PT, false>(N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, n_per_split, b, sp, pi, pj, smem_raw);
+        psi2_patch<TIN, T, KS, PT, false, WEIGHTED>(N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, n_per_split, b, sp, pi, pj, smem_raw,
+                                                    wts);
 }
 
 // Plain-VALU variant (cross-check of the matrix-core kernel): thread per (m, m') of the lower block-triangle, literal
 // reference formula rbf_kernel.py:189-199 with the per-(n,q) factors staged through LDS.  Writes slab 0 only.
-template <typename TIN, typename T>
+// WEIGHTED: row n enters with the factor wts[b][n] >= 0; rows with weight 0 are skipped (the branch is uniform for the workgroup).
+template <typename TIN, typename T, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void psi2_plain_kernel(int N, int M, int Q, const TIN *__restrict__ z,
                                                          const TIN *__restrict__ mu, const TIN *__restrict__ s,
                                                          const TIN *__restrict__ gamma, const TIN *__restrict__ alpha,
-                                                         T *__restrict__ part, int Mp) {
+                                                         T *__restrict__ part, int Mp, const TIN *__restrict__ wts) {
     __shared__ T w[PSI2_NT][DPGP_MAX_Q], mm[PSI2_NT][DPGP_MAX_Q], hl[PSI2_NT];
+    __shared__ T wr[WEIGHTED ? PSI2_NT : 1];
     const int b = blockIdx.y, t = threadIdx.x;
     const int e = blockIdx.x * 256 + t;
     const int m = e / Mp, mp = e - m * Mp;
@@ -1125,6 +1153,7 @@ __global__ __launch_bounds__(256) void psi2_plain_kernel(int N, int M, int Q, co
             T a = 0;
             for (int q = 0; q < Q; ++q) a += dpgp_log((T)2 * (T)g[q] * (n < N ? (T)s[(size_t)n * Q + q] : (T)1) + (T)1);
             hl[t] = (T)0.5 * a;
+            if constexpr (WEIGHTED) wr[t] = n < N ? (T)wts[(size_t)b * N + n] : (T)0;
         }
         __syncthreads();
         const int nn = min(PSI2_NT, N - n0);
@@ -1134,7 +1163,11 @@ __global__ __launch_bounds__(256) void psi2_plain_kernel(int N, int M, int Q, co
                 T d = mm[r][q] - zb[q];
                 ex += w[r][q] * d * d;
             }
-            acc += dpgp_exp2((T)(-DPGP_LOG2E) * ex);
+            if constexpr (WEIGHTED) {
+                if (wr[r] > (T)0) acc += wr[r] * dpgp_exp2((T)(-DPGP_LOG2E) * ex);
+            } else {
+                acc += dpgp_exp2((T)(-DPGP_LOG2E) * ex);
+            }
         }
     }
     if (active) {
@@ -1820,9 +1853,55 @@ static int launch_psi2_ks(int B, int N, int M, int Q, const TIN *z, const TIN *m
                                 (int)lds) != hipSuccess)
             return DPGP_ERR_LAUNCH;
     }
-    DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, nper, task);
+    DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, nper, task,
+                       (const TIN *)nullptr);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;
+}
+
+// the weighted fp64 instantiations (dpgp_psi2_weighted_f64): same grid, splits and LDS as the unweighted launch, no K_uu task
+template <int KS>
+static int launch_psi2_weighted_ks(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                   const double *gamma, const double *alpha, const double *wts, double *part, int ns,
+                                   hipStream_t st) {
+    constexpr int PT = Psi2Cfg<double>::PT, PS = 16 * PT;
+    const int Mp = dpgp_round_up(M, 16);
+    const int nps = dpgp_ceil_div(Mp, PS);
+    const int nper = dpgp_round_up(dpgp_ceil_div(N, ns), PSI2_NT);
+    dim3 grid(B, ns, nps * (nps + 1) / 2);
+    const size_t lds = psi2_lds_bytes<double, KS>();
+    auto kern = psi2_mfma_kernel<double, double, KS, PT, true>;
+    if (lds > 48 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds) != hipSuccess)
+            return DPGP_ERR_LAUNCH;
+    }
+    const ChainKTask task = {nullptr, 0, nullptr, nullptr, M, Mp, 0, 0};
+    DPGP_PRELAUNCH(); hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, N, M, Q, B, z, mu, s, gamma, alpha, part, Mp, nper, task, wts);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
+static int launch_psi2_weighted(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                const double *gamma, const double *alpha, const double *wts, double *part, int ns, int algo,
+                                hipStream_t st) {
+    const int Mp = dpgp_round_up(M, 16);
+    if (algo == DPGP_ALGO_PLAIN) {
+        if (ns > 1 && hipMemsetAsync(part + (size_t)B * Mp * Mp, 0, sizeof(double) * (size_t)(ns - 1) * B * Mp * Mp, st) !=
+                          hipSuccess)
+            return DPGP_ERR_LAUNCH;
+        dim3 grid(dpgp_ceil_div(Mp * Mp, 256), B);
+        DPGP_PRELAUNCH(); hipLaunchKernelGGL((psi2_plain_kernel<double, double, true>), grid, dim3(256), 0, st, N, M, Q, z, mu, s, gamma,
+                           alpha, part, Mp, wts);
+        DPGP_LAUNCH_CHECK();
+        return DPGP_OK;
+    }
+    switch (dpgp_ceil_div(Q + 2, 4)) {
+#define CASE(k) \
+    case k: return launch_psi2_weighted_ks<k>(B, N, M, Q, z, mu, s, gamma, alpha, wts, part, ns, st);
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    }
+    return -4;
 }
 
 template <typename TIN>
@@ -1938,7 +2017,7 @@ int launch_psi2_partial(int B, int N, int M, int Q, const TIN *z, const TIN *mu,
             return DPGP_ERR_LAUNCH;
         dim3 grid(dpgp_ceil_div(Mp * Mp, 256), B);
         DPGP_PRELAUNCH(); hipLaunchKernelGGL((psi2_plain_kernel<TIN, T>), grid, dim3(256), 0, st, N, M, Q, z, mu, s, gamma, alpha, part,
-                           Mp);
+                           Mp, (const TIN *)nullptr);
         DPGP_LAUNCH_CHECK();
         return DPGP_OK;
     }
@@ -1979,9 +2058,11 @@ extern "C" size_t dpgp_psi2_workspace_bytes(int B, int N, int M, int Q, int elem
            psi2_pairs_scale_bytes(B, M);
 }
 
+// weighted_entry: the call came through dpgp_psi2_weighted_f64 (algo AUTO or PLAIN only; w may be NULL = unweighted)
 template <typename T>
 static int psi2_api(int B, int N, int M, int Q, const T *z, const T *mu, const T *s, const T *gamma, const T *alpha,
-                    T *out, void *ws, size_t ws_bytes, int algo, void *stream) {
+                    T *out, void *ws, size_t ws_bytes, int algo, void *stream, const T *w = nullptr,
+                    bool weighted_entry = false) {
     if (B <= 0) return -1;
     if (N <= 0) return -2;
     if (M <= 0) return -3;
@@ -1995,11 +2076,19 @@ static int psi2_api(int B, int N, int M, int Q, const T *z, const T *mu, const T
     if (!ws) return -11;
     if (ws_bytes < dpgp_psi2_workspace_bytes(B, N, M, Q, sizeof(T))) return -12;
     if (algo < 0 || algo > DPGP_ALGO_PATCH_F16) return -13;
+    if (weighted_entry && algo != DPGP_ALGO_AUTO && algo != DPGP_ALGO_PLAIN) return -13;
     const int ns = psi2_nsplit(B, N, M), Mp = dpgp_round_up(M, 16);
     unsigned char *consts = (unsigned char *)ws + dpgp_align256(sizeof(T) * (size_t)ns * B * Mp * Mp);
-    int rc = launch_psi2_partial<T, T>(B, N, M, Q, z, mu, s, gamma, alpha, (T *)ws, ns, algo, (hipStream_t)stream,
+    int rc = DPGP_OK;
+    if constexpr (std::is_same<T, double>::value) {
+        if (w) rc = launch_psi2_weighted(B, N, M, Q, z, mu, s, gamma, alpha, w, (T *)ws, ns, algo, (hipStream_t)stream);
+    }
+    if (!w)
+        rc = launch_psi2_partial<T, T>(B, N, M, Q, z, mu, s, gamma, alpha, (T *)ws, ns, algo, (hipStream_t)stream,
                                        nullptr, 0, nullptr, nullptr, consts, 0,
                                        reinterpret_cast<float *>(consts + psi2_consts_bytes(M, Q)));
+    else if (!std::is_same<T, double>::value)
+        return -13;
     if (rc) return rc;
     size_t tot = (size_t)B * M * M;
     DPGP_PRELAUNCH(); hipLaunchKernelGGL((psi2_finish_kernel<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -2016,4 +2105,9 @@ extern "C" int dpgp_psi2_f64(int B, int N, int M, int Q, const double *z, const 
                              const double *gamma, const double *alpha, double *out, void *ws, size_t ws_bytes, int algo,
                              void *stream) {
     return psi2_api<double>(B, N, M, Q, z, mu, s, gamma, alpha, out, ws, ws_bytes, algo, stream);
+}
+extern "C" int dpgp_psi2_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                      const double *gamma, const double *alpha, const double *w, double *out, void *ws,
+                                      size_t ws_bytes, int algo, void *stream) {
+    return psi2_api<double>(B, N, M, Q, z, mu, s, gamma, alpha, out, ws, ws_bytes, algo, stream, w, true);
 }

@@ -28,6 +28,7 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
+from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .test_bound import _TestBound
 from .test_bound_t import _MomentsT, _TestBoundT
@@ -59,7 +60,7 @@ def dp_gp_lvm(y_train,
               alpha_prior_params=DP_DEFAULT_ALPHA_PRIOR_PARAMS,
               mask_size=1,
               device=None, precision=None, process_group=None, initial_values=None, backward_precision=None,
-              psi_algo='auto', _shard_of=None):
+              psi_algo='auto', _shard_of=None, observed=None):
     """
     :param y_train: [N x D] numpy array, columns normalised to zero mean / unit variance (dp_gp_lvm.py:30-32).
     :param num_latent_dims: Q.  :param num_inducing_points: M.  :param truncation_level: T.
@@ -76,8 +77,26 @@ def dp_gp_lvm(y_train,
     :param initial_values: dict of post-initialisation parameter VALUES (x_mean, x_var, x_u, phi_logits, gamma_atoms,
            alpha_atoms, beta_atoms, gamma_1, gamma_2, w_1, w_2) that replace the random/PCA initialisation — used by the
            parity tests and the benchmark, which must not depend on PCA sign conventions or NumPy's global RNG.
+    :param observed: (extension) a boolean [N x D] mask of the entries of y_train that were measured, any pattern with at least one
+           True (entries where it is False are ignored and may be NaN; utils.missing.observed_mask makes the mask of a NaN-filled
+           array).  f_hat is then the sum over the columns d observed somewhere of the unmasked model's five terms on the rows R_d
+           at which d was measured (N -> N_d, Psi2_d and y_d^T y_d over R_d, Psi1_d^T y_d on the zero-filled column): the fp64
+           operators of the unmasked precision='f64' model with a 0 / 1 weight per (column, row) on the Psi2 sum and its adjoint
+           (models/masked_bound_d.py), evaluated eagerly on one GPU — precision and backward_precision None or 'f64',
+           process_group None.  KL(q(X)) runs over all N rows, the DP objective over all D columns, the hyper-prior over the T
+           atoms; a column never observed contributes its DP terms only, a row never observed its KL only.  x_mean defaults to the
+           PCA of the column-mean-filled data.  impute_training_data() fills the gaps with the posterior mean.
     """
     num_samples, num_dimensions = np.shape(y_train)
+    train_obs = None
+    if observed is not None:
+        assert precision in (None, 'f64'), "with observed, precision must be None or 'f64' (the masked model is fp64)"
+        assert backward_precision in (None, 'f64'), "with observed, backward_precision must be None or 'f64' (the masked model is fp64)"
+        assert process_group is None and _shard_of is None, 'with observed, process_group must be None (the masked model is not sharded)'
+        train_obs = _missing.check_observed(observed, (num_samples, num_dimensions))
+        assert train_obs.any(), 'observed must hold at least one True entry'
+        y_train = _missing.zero_filled(y_train, train_obs)
+        precision = backward_precision = 'f64'
     assert 0 < num_latent_dims <= num_dimensions, \
         'Number of latent dimensions must be postive and less than the dimensionality of the observed data.'
     assert 0 < num_inducing_points <= num_samples, \
@@ -118,7 +137,8 @@ def dp_gp_lvm(y_train,
     if 'x_mean' in iv:
         x_init = np.asarray(iv['x_mean'], dtype=np.float64)
     else:
-        x_init = pca(np.asarray(y_train), num_latent_dimensions=num_latent_dims)
+        x_init = pca(np.asarray(y_train) if train_obs is None else _missing.column_mean_filled(y_train, train_obs),
+                     num_latent_dimensions=num_latent_dims)
     x_mean = _t(x_init)                                                        # [N x Q]
     x_var_raw = _raw_pos('x_var', 1.0, (num_samples, num_latent_dims))         # softplus(raw) = diag of q(X) covariance
     if 'x_u' in iv:
@@ -169,7 +189,10 @@ def dp_gp_lvm(y_train,
                phi=torch.empty((d_local, truncation_level), **f64),
                scal=torch.zeros(_lib.lib().dpgp_model_scal_count(d_local), **f64),
                red=torch.zeros(2, **f64), out=torch.zeros(5, **f64))
-    workspace = ops.ElboWorkspace(d_local, num_samples, num_inducing_points, num_latent_dims, precision, device)
+    # observed=: f_hat and its derivatives come from models/masked_bound_d.py; nothing of the fused pipeline is used (no workspace)
+    masked = _MaskedBoundD(np.asarray(y_train, dtype=np.float64), train_obs, device) if train_obs is not None else None
+    workspace = ops.ElboWorkspace(d_local, num_samples, num_inducing_points, num_latent_dims, precision, device) \
+        if masked is None else None
     s_1, s_2 = dp_model.prior
 
     # one training step through dpgp_elbo_step (mixed precision, M <= 128, Q <= 20: DESIGN.md section 7.1): the forward's psi2 dispatch is
@@ -200,6 +223,8 @@ def dp_gp_lvm(y_train,
         lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
         r = dp_model.raw
         out = buf['out'] if out is None else out
+        if masked is not None:
+            return _evaluate_masked(out)[0]
         _lib.check(lib.dpgp_model_prepare(
             d_local, truncation_level, num_latent_dims, num_samples, d_lo, mask_size, r['logits'].data_ptr(),
             gamma_atoms_raw.data_ptr(), sig_var_atoms_raw.data_ptr(), beta_atoms_raw.data_ptr(), x_var_raw.data_ptr(),
@@ -227,6 +252,29 @@ def dp_gp_lvm(y_train,
             _exchange_and_finalise(out, ws_)
         return out
 
+    def _evaluate_masked(out, grad=False):
+        """observed=: prepare (the mixed gamma_d, alpha_d, beta_d, S, phi, scal as in the unmasked evaluation), the masked f_hat of the
+        columns observed somewhere (models/masked_bound_d.py), KL over all rows, then pack and finalize: out[5] as evaluate().
+        Launched eagerly, no host synchronisation.  Returns (out, stage-A/B derivatives or None)."""
+        lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+        r = dp_model.raw
+        _lib.check(lib.dpgp_model_prepare(
+            d_local, truncation_level, num_latent_dims, num_samples, d_lo, mask_size, r['logits'].data_ptr(),
+            gamma_atoms_raw.data_ptr(), sig_var_atoms_raw.data_ptr(), beta_atoms_raw.data_ptr(), x_var_raw.data_ptr(),
+            r['gamma_1'].data_ptr(), r['gamma_2'].data_ptr(), r['w'].data_ptr(), s_1, s_2, 1, buf['gamma'].data_ptr(),
+            buf['alpha'].data_ptr(), buf['beta'].data_ptr(), buf['s'].data_ptr(), buf['phi'].data_ptr(), buf['scal'].data_ptr(), st),
+            'dpgp_model_prepare')
+        with torch.no_grad():
+            gam = masked.take(buf['gamma']).contiguous()
+            al, be = masked.take(buf['alpha']).reshape(-1).contiguous(), masked.take(buf['beta']).reshape(-1).contiguous()
+            res = masked.evaluate(x_u.detach(), x_mean.detach(), buf['s'], gam, al, be, grad=grad)
+            f, grads = res if grad else (res, None)
+            kl = ops.kl_qx(x_mean.detach(), buf['s']).reshape(1)
+        _lib.check(lib.dpgp_model_pack(d_local, f.data_ptr(), buf['scal'].data_ptr(), buf['red'].data_ptr(), st), 'dpgp_model_pack')
+        _lib.check(lib.dpgp_model_finalize(buf['red'].data_ptr(), kl.data_ptr(), buf['scal'][1:2].data_ptr(), out.data_ptr(), st),
+                   'dpgp_model_finalize')
+        return out, grads
+
     def _exchange_and_finalise(out, ws_=None):
         lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
         dist.all_reduce(buf['red'], op=dist.ReduceOp.SUM, group=process_group)    # the only exchange: 2 fp64 scalars
@@ -242,6 +290,11 @@ def dp_gp_lvm(y_train,
         process group the graph holds this rank's part (prepare ... pack); the 2-scalar all-reduce and the finalising kernel
         follow as ordinary calls (a collective inside a captured graph is transport-specific; this form works with any).
         Returns the same device tensor as evaluate(); `out` (optional, [5]) receives a copy on the stream."""
+        if masked is not None:                           # (the masked path is launched eagerly: no capture)
+            res = evaluate()
+            if out is not None:
+                out.copy_(res, non_blocking=True)
+            return res
         if 'graph' not in graph_state:
             evaluate()                                   # (first call outside the capture: function attributes, warm-up)
             torch.cuda.synchronize()
@@ -270,10 +323,18 @@ def dp_gp_lvm(y_train,
         events: optional list of 4 torch.cuda.Event(enable_timing=True), recorded after the forward evaluation, stage A,
         stage B and the chain rule to the raw variables (bench.py's breakdown)."""
         lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
-        gws = grad_workspace()
+        gws = grad_workspace() if masked is None else None
         mark = (lambda i: events[i].record()) if events is not None else (lambda i: None)
         r = dp_model.raw
-        if fused_step and events is None:
+        info = gws.info if masked is None else None
+        if masked is not None:
+            # observed=: forward, dense adjoints and the weighted stage B of the columns observed somewhere; a never-observed
+            # column's rows of d_gamma and d_alpha_beta are zero (its DP terms reach the logits through dpgp_model_backward)
+            _, (dmu, ds, dz, dg, dab) = _evaluate_masked(buf['out'], grad=True)
+            mark(0), mark(1)
+            dg, dab, info = masked.scatter(dg), masked.scatter(dab), masked.info
+            mark(2)
+        elif fused_step and events is None:
             evaluate(_step=True)
             dmu, ds, dz, dg, dab, _ = step_state['grads']
         elif split_step and events is None:
@@ -318,7 +379,7 @@ def dp_gp_lvm(y_train,
         mark(3)
         # trouble flag of the LOCAL output dims (a Cholesky / conditioning flag of the forward evaluation or a non-finite
         # partial gradient), reduced with the gradients: every rank sees the same decision (optimise() branches on it)
-        _lib.check(lib.dpgp_trouble_flag(flat.numel() - 1, flat.data_ptr(), d_local, gws.info.data_ptr(),
+        _lib.check(lib.dpgp_trouble_flag(flat.numel() - 1, flat.data_ptr(), info.numel(), info.data_ptr(),
                                          flat[-1:].data_ptr(), st), 'dpgp_trouble_flag')
         if sharded:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=process_group)      # one packed exchange (N Q x 2 + M Q + ...)
@@ -352,7 +413,7 @@ def dp_gp_lvm(y_train,
                     'precision=%r (info codes of this rank: %s).  The fp32 psi-statistics of precision="mixed" stop being a '
                     'substitute for the reference\'s fp64 once K_uu is nearly singular: build the model with '
                     'precision="f64", backward_precision="mixed".'
-                    % (it, precision, sorted(set(workspace.info.unique().tolist()) - {0})))
+                    % (it, precision, sorted(set((workspace.info if masked is None else masked.info).unique().tolist()) - {0})))
             for k, p_ in params.items():
                 p_.grad = g[k].reshape(p_.shape)                                 # (views of this step's own packed buffer: no copy)
             opt.step()
@@ -416,7 +477,10 @@ def dp_gp_lvm(y_train,
         return bound, out
 
     def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
-        if x_test_mean is None and not use_pca:
+        if x_test_mean is None and not use_pca and train_obs is not None:
+            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(np.asarray(y_train), train_obs, y0, obs,
+                                                                           x_mean.detach().cpu().numpy())
+        elif x_test_mean is None and not use_pca:
             x_test_mean = _missing.masked_nearest_neighbour_init(np.asarray(y_train), y0, obs, x_mean.detach().cpu().numpy())
         return _init_test_latents(y0, None, use_pca, x_test_mean, x_test_var)
 
@@ -462,6 +526,8 @@ def dp_gp_lvm(y_train,
         The trace term enters with the derived sign, - tr((K_d^-1 - P_d) Psi2*(n)).  _predictive_moments' tr_term is the same
         quantity, + tr((K_d^-1 - P_d) Psi2*) summed over the test points, and is ADDED there (following the reference), so
             sum_n var(n,d) = predicted_covar[d,0,0] + (N* - 1)/beta_d - 2 tr_term_d."""
+        if masked is not None:
+            return _marginals_at_masked(cols, xt, st_)
         m_ = num_inducing_points
         idx = torch.as_tensor(np.asarray(cols), device=device)
         f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
@@ -483,6 +549,34 @@ def dp_gp_lvm(y_train,
         mean, var = ops.qx_psi_point_moments(z[None].expand(len(cols), -1, -1).contiguous(), f64(xt), f64(st_), gu, au, c.contiguous(),
                                              r.contiguous(), gidx, bu)
         return mean[:, :, 0].transpose(0, 1).contiguous(), var[:, :, 0].transpose(0, 1).contiguous()
+
+    def _marginals_at_masked(cols, xt, st_):
+        """_marginals_at on a model trained with observed=: Psi2_d is the weighted sum over the rows at which column d was measured and
+        Psi1_d^T y_d comes from ops.psi1T_y on the zero-filled data (no [K, N, M] array); a column never observed has no posterior:
+        mean 0, variance alpha_d + 1/beta_d."""
+        cols = np.asarray(cols)
+        pos = np.searchsorted(masked.cols_np, cols)
+        seen = (pos < masked.cols_np.size) & (masked.cols_np[np.minimum(pos, masked.cols_np.size - 1)] == cols)
+        idx = torch.as_tensor(cols, device=device)
+        au, bu = buf['alpha'][:, 0][idx].contiguous(), buf['beta'][:, 0][idx].contiguous()
+        prior_var = (au + 1.0 / bu)[None, :].expand(xt.shape[0], -1)
+        mean, var = torch.zeros((xt.shape[0], cols.size), dtype=TORCH_DTYPE, device=device), prior_var.clone()
+        if seen.any():
+            here = torch.as_tensor(np.flatnonzero(seen), device=device)
+            sel = torch.as_tensor(pos[seen], dtype=torch.long, device=device)
+            gu, a_, b_ = buf['gamma'][idx[here]].contiguous(), au[here].contiguous(), bu[here].contiguous()
+            z = x_u.detach()
+            c, rhs = masked.posterior(z, x_mean.detach(), F.softplus(x_var_raw).detach(), gu, a_, b_, sel=sel)
+            k_ = int(sel.numel())
+            gidx = torch.zeros((k_, 1), dtype=torch.int32, device=device)
+            mn, vr = ops.qx_psi_point_moments(z[None].expand(k_, -1, -1).contiguous(), xt.contiguous(), st_.contiguous(), gu, a_,
+                                              c[:, None].contiguous(), rhs[:, :, None].contiguous(), gidx, b_)
+            mean[:, here], var[:, here] = mn[:, :, 0].transpose(0, 1), vr[:, :, 0].transpose(0, 1)
+        return mean, var
+
+    def _not_built(name):
+        raise NotImplementedError('%s is not built for a model trained with observed=: use impute_training_data for the gaps of the '
+                                  'training data' % name)
 
     class DP_GP_LVM(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508)."""
@@ -540,14 +634,20 @@ def dp_gp_lvm(y_train,
         @property
         def per_dimension_terms(self):
             """[D_local x 5] f_hat terms and the info flags of the last evaluation (0 fine, > 0 failed factorisation,
-            DPGP_INFO_ILL_CONDITIONED = -2: fp32 Psi2 no longer trustworthy for this output dim)."""
+            DPGP_INFO_ILL_CONDITIONED = -2: fp32 Psi2 no longer trustworthy for this output dim).  A model trained with observed=:
+            [D x 5] and [D], zero rows for the columns never observed."""
+            if masked is not None:
+                if masked.terms is None:
+                    evaluate()
+                return masked.scatter(masked.terms), masked.scatter(masked.info)
             return workspace.terms, workspace.info
 
         @property
         def conditioning_guard(self):
             """[D_local] bound on what the rounding of an fp32 Psi2 can move each output dim's f_hat terms by (last
-            evaluation; computed in every precision mode; flagged in info when > DPGP_GUARD_REL * N in mixed / f32)."""
-            return workspace.guard
+            evaluation; computed in every precision mode; flagged in info when > DPGP_GUARD_REL * N in mixed / f32); None for a model
+            trained with observed= (fp64 throughout, no fused evaluation)."""
+            return None if masked is not None else workspace.guard
 
         @property
         def last_stage_b_form(self):
@@ -601,6 +701,8 @@ def dp_gp_lvm(y_train,
             (one more dpgp_elbo_fhat call).  Returns (prediction_lower_bound, x_test_mean [N* x Q], x_test_covar [N* x Q x Q],
             test_log_likelihood) at the initial q(X*): nearest training neighbour + N(0, 0.01^2) noise, or PCA of y_test
             (`use_pca`), or the given x_test_mean / x_test_var (values; what a caller's optimiser of q(X*) passes back in)."""
+            if masked is not None:
+                _not_built('predict_new_latent_variables')
             assert not sharded and world == 1, 'prediction paths run on one GPU'
             y_test = np.asarray(y_test, dtype=np.float64)
             num_test_points, test_dims = np.shape(y_test)
@@ -707,7 +809,12 @@ def dp_gp_lvm(y_train,
             reference_compat=True.
 
             marginal_variance=True (extension): the last entry is the per-entry variance [N* x Du] of predictive_marginals on
-            the predicted dims in place of the [Du x N* x N*] array."""
+            the predicted dims in place of the [Du x N* x N*] array.
+
+            On a model trained with observed= this method and predict_new_latent_variables are not built: NotImplementedError
+            (predictive_marginals gives the moments at test points, impute_training_data fills the training data's own gaps)."""
+            if masked is not None:
+                _not_built('predict_missing_data')
             if observed is not None:
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
@@ -740,6 +847,21 @@ def dp_gp_lvm(y_train,
                 with torch.no_grad():
                     predicted_covar = _marginals_at(pred_state['missing_columns'], xt, st_)[1]
             return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
+
+        @staticmethod
+        def impute_training_data(return_variance=False):
+            """A model trained with observed=: y_train [N x D] with every unobserved entry (n, d) replaced by the posterior mean
+            beta_d Psi1_d[n,:] (K_d + beta_d Psi2_d)^-1 Psi1_d^T y_d (Psi2_d and y_d over the rows at which d was observed); observed
+            entries as given, a never-observed column 0.  fp64 device tensor.  return_variance=True: (filled, var), var [N x D] the
+            per-entry variance of predictive_marginals at the training q(X) at the unobserved entries and 0 at the observed ones;
+            filled is the same tensor either way."""
+            assert masked is not None, 'impute_training_data needs a model trained with observed='
+            evaluate()
+            with torch.no_grad():
+                mean, var = _marginals_at_masked(np.arange(num_dimensions), x_mean.detach(), F.softplus(x_var_raw).detach())
+                obs = torch.as_tensor(train_obs, device=device)
+                filled = torch.where(obs, y_local, mean)
+                return (filled, torch.where(obs, torch.zeros_like(var), var)) if return_variance else filled
 
     return DP_GP_LVM()
 

@@ -444,13 +444,22 @@ def psi1T_y(z, mu, s, gamma, alpha, y):
     return out
 
 
-def psi2(z, mu, s, gamma, alpha, algo='auto'):
-    """Kernel.psi_2 -> [B,M,M]  (rbf_kernel.py:164-199), streamed over n on the matrix cores."""
+def psi2(z, mu, s, gamma, alpha, algo='auto', weights=None):
+    """Kernel.psi_2 -> [B,M,M]  (rbf_kernel.py:164-199), streamed over n on the matrix cores.
+    weights [B,N] (fp64 only; algo 'auto' or 'plain'): out[b] = sum_n weights[b,n] psi2_bn (dpgp_psi2_weighted_f64).  The weights
+    must be >= 0 and finite — behaviour for negative weights is unspecified; a weight of 0 contributes exactly 0.0."""
     dt, z, mu, s, gamma, alpha, b, n, m, q = _zms(z, mu, s, gamma, alpha)
     out = torch.empty((b, m, m), dtype=dt, device=mu.device)
     l = _lib.lib()
     wsb = l.dpgp_psi2_workspace_bytes(b, n, m, q, out.element_size())
     ws = _ws(wsb, mu.device)
+    if weights is not None:
+        assert dt == torch.float64, 'weighted Psi2 is an fp64 operator'
+        weights = _qx_weights(weights, b, n, mu)
+        _lib.check(l.dpgp_psi2_weighted_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                            alpha.data_ptr(), weights.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb,
+                                            _lib.ALGO[algo], _stream()), 'dpgp_psi2_weighted_f64')
+        return out
     name = 'dpgp_psi2_' + _SUFFIX[dt]
     _lib.check(getattr(l, name)(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
                                 alpha.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb, _lib.ALGO[algo], _stream()), name)
@@ -903,10 +912,14 @@ def _elbo_grad_chain_large_composed(alpha, beta, workspace, jitter, z, gamma, ps
     return gp, wk, gv, dab, torch.maximum(info_k, info_b)
 
 
-def elbo_grad_psi(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, prec='mixed', g_psi1=None):
+def elbo_grad_psi(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, prec='mixed', g_psi1=None, weights=None):
     """Backward pass, stage B: d f_hat / d (mu [N,Q], s [N,Q], z [M,Q], gamma [D,Q]) from the stage-A adjoints
     (rbf_kernel.py:58-199 differentiated).  g_psi1 [D,N,Mp] (mixed precision only): a full adjoint of Psi1 in place of the
-    rank-1 form g_v[d,a] y[n,d] — then y and g_v may be None."""
+    rank-1 form g_v[d,a] y[n,d] — then y and g_v may be None.
+    weights [D,N] (prec='f64' only, AssertionError otherwise): the Psi2 term becomes <g_psi2_d, sum_n weights[d,n] psi2_dn>
+    (dpgp_elbo_grad_psi_weighted_f64); the Psi1 term is governed by y alone (zero-fill it), the K_uu term is unweighted.  The
+    weights must be >= 0 and finite — behaviour for negative weights is unspecified; a weight of 0 contributes exactly 0.0."""
+    assert weights is None or (prec == 'f64' and g_psi1 is None), 'weights are taken by the fp64 stage B only'
     f64 = torch.float64
     z, mu, s = _prep(z, f64, 'z'), _prep(mu, f64, 'mu'), _prep(s, f64, 's')
     gamma, alpha, _, d = _hyp(gamma, alpha, None, f64)
@@ -920,12 +933,20 @@ def elbo_grad_psi(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, prec='mixed', g
     if prec == 'f64' and m > 128:
         if g_psi1 is not None:
             raise ValueError('a full Psi1 adjoint is taken in mixed precision only')
-        return _elbo_grad_psi_f64_blocks(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v)
+        return _elbo_grad_psi_f64_blocks(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, weights)
     l = _lib.lib()
     wsb = l.dpgp_elbo_grad_psi_workspace_bytes_ex(d, n, m, q, _lib.PREC[prec])
     ws = _ws(wsb, dev)
     dmu, ds = torch.empty((n, q), dtype=f64, device=dev), torch.empty((n, q), dtype=f64, device=dev)
     dz, dg = torch.empty((m, q), dtype=f64, device=dev), torch.empty((d, q), dtype=f64, device=dev)
+    if weights is not None:
+        weights = _qx_weights(weights, d, n, mu)
+        _lib.check(l.dpgp_elbo_grad_psi_weighted_f64(d, n, m, q, y.data_ptr(), y.stride(0), z.data_ptr(), mu.data_ptr(),
+                                                     s.data_ptr(), gamma.data_ptr(), alpha.data_ptr(), weights.data_ptr(),
+                                                     g_psi2.data_ptr(), w_kuu.data_ptr(), g_v.data_ptr(), ws.data_ptr(), wsb,
+                                                     dmu.data_ptr(), ds.data_ptr(), dz.data_ptr(), dg.data_ptr(), _stream()),
+                   'dpgp_elbo_grad_psi_weighted_f64')
+        return dmu, ds, dz, dg
     _lib.check(l.dpgp_elbo_grad_psi_ex(d, n, m, q, y.data_ptr() if y is not None else None, y.stride(0) if y is not None else 0,
                                        z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
                                        g_psi2.data_ptr(), w_kuu.data_ptr(), g_v.data_ptr() if g_v is not None else None,
@@ -935,7 +956,7 @@ def elbo_grad_psi(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, prec='mixed', g
     return dmu, ds, dz, dg
 
 
-def _elbo_grad_psi_f64_blocks(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v):
+def _elbo_grad_psi_f64_blocks(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, weights=None):
     """Stage B in fp64 for M > 128.  The fp64 kernel keeps the M x M adjoint of one output dim in LDS (M <= 128); every term
     of stage B is a sum over PAIRS of inducing points (Psi2 and K_uu terms) or over single ones (Psi1 term), so the sum is
     split over the nb (nb - 1) / 2 unordered pairs {I, J} of blocks of <= 64 inducing points: pair {I, J} runs the same
@@ -963,7 +984,7 @@ def _elbo_grad_psi_f64_blocks(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v):
             gs = torch.nn.functional.pad(g_psi2[:, idx][:, :, idx] * scale, pad2).contiguous()
             ws_ = torch.nn.functional.pad(w_kuu[:, idx][:, :, idx] * scale, pad2).contiguous()
             gvs = torch.nn.functional.pad(g_v[:, idx] * wd, (0, mps - ms)).contiguous() if g_v is not None else None
-            a, b, c, e = elbo_grad_psi(y, z[idx].contiguous(), mu, s, gamma, alpha, gs, ws_, gvs, prec='f64')
+            a, b, c, e = elbo_grad_psi(y, z[idx].contiguous(), mu, s, gamma, alpha, gs, ws_, gvs, prec='f64', weights=weights)
             dmu += a
             ds += b
             dz.index_add_(0, idx, c)

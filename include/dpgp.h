@@ -283,6 +283,15 @@ int dpgp_psi2_f32(int B, int N, int M, int Q, const float *z, const float *mu, c
                   const float *alpha, float *out, void *ws, size_t ws_bytes, int algo, void *stream);
 int dpgp_psi2_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s, const double *gamma,
                   const double *alpha, double *out, void *ws, size_t ws_bytes, int algo, void *stream);
+/* ---- Psi2 with a weight per (batch entry, observation): out[b] = sum_n w[b][n] psi2_bn, where psi2_bn is row n's term of the
+ *      sum dpgp_psi2_f64 forms; exactly symmetric.  fp64.  w[B][N] >= 0 and finite (behaviour for negative weights is
+ *      unspecified); a weight of 0 contributes exactly 0.0 and a run of rows with weight 0 is not evaluated at all (missing
+ *      entries of a data matrix: w = 0 / 1).  w == NULL: the unweighted kernels of dpgp_psi2_f64, bit for bit.  w adds no
+ *      bad-argument code: codes, their order and ws (dpgp_psi2_workspace_bytes(B,N,M,Q,8)) are those of dpgp_psi2_f64.
+ *      algo: DPGP_ALGO_AUTO (matrix cores) or DPGP_ALGO_PLAIN, anything else -13.  No atomics: the same bits on every run. */
+int dpgp_psi2_weighted_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                           const double *gamma, const double *alpha, const double *w /* [B][N], nullable */, double *out,
+                           void *ws, size_t ws_bytes, int algo, void *stream);
 
 /* ---- tf.cholesky (dp_gp_lvm.py:116,127): in-place lower Cholesky of a[B,M,M] (upper triangle zeroed), info[B].
  *      ws: dpgp_potrf_workspace_bytes(B,M,elem_size).                                                              */
@@ -400,6 +409,18 @@ int dpgp_elbo_grad_psi(int D, int N, int M, int Q, const double *y, int ldy, con
                        const double *s, const double *gamma, const double *alpha, const double *g_psi2,
                        const double *w_kuu, const double *g_v, int prec, void *ws, size_t ws_bytes, double *d_mu,
                        double *d_s, double *d_z, double *d_gamma, void *stream);
+/* dpgp_elbo_grad_psi(prec = DPGP_PREC_F64) with a weight per (output dim, observation) on the Psi2 term: the derivatives, with
+ * respect to mu, s, z and gamma_d, of  sum_d <g_psi2_d, sum_n w[d][n] psi2_dn> + <g_v_d, Psi1_d^T y_d> + the K_uu term.  The Psi1
+ * term is governed by y alone (the caller zero-fills it where an entry is missing), the K_uu term is unweighted, alpha stays a
+ * constant factor.  w[D][N] >= 0 and finite (behaviour for negative weights is unspecified); a weight of 0 contributes exactly 0.0,
+ * and a pair of observations (2k, 2k+1 of an n-split) with w = 0 and y = 0 is not evaluated.  w == NULL: the unweighted kernel, bit
+ * for bit.  w adds no bad-argument code: codes, their order and ws (dpgp_elbo_grad_psi_workspace_bytes_ex(D,N,M,Q,DPGP_PREC_F64))
+ * are those of dpgp_elbo_grad_psi; M <= 128 (-30 otherwise).  No atomics: the same bits on every run. */
+int dpgp_elbo_grad_psi_weighted_f64(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu,
+                                    const double *s, const double *gamma, const double *alpha,
+                                    const double *w /* [D][N], nullable */, const double *g_psi2, const double *w_kuu,
+                                    const double *g_v, void *ws, size_t ws_bytes, double *d_mu, double *d_s, double *d_z,
+                                    double *d_gamma, void *stream);
 /* as dpgp_elbo_grad_psi with a full adjoint g_psi1[D][N][Mp] of Psi1 (may be NULL) in place of the rank-1 form
  * g_v[d][a] y[n][d]: then y and g_v may be NULL.  Mixed precision only.  (The over-T model, reference dp_gp_lvm.py:513-676,
  * couples every atom with all columns of y.) */
