@@ -31,6 +31,7 @@ from .interfaces.trainable import Trainable
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .test_bound import _TestBound
+from .test_bound_d import _TestBoundD
 from .test_bound_t import _MomentsT, _TestBoundT
 
 
@@ -465,12 +466,18 @@ def dp_gp_lvm(y_train,
         assert not sharded and world == 1, 'prediction paths run on one GPU'
         return _missing.masked_arguments(y_test, observed, num_dimensions, predict, reference_compat)
 
-    def _masked_bound(y0, obs):
+    def _masked_bound(y0, obs, form='slots'):
         """The fp64 test bound with one slot per output dim that has an observed entry: that dim's mixed (gamma, alpha, beta) of
-        this evaluate() and the shared inducing inputs.  Returns (bound, the training-side evaluation out[5])."""
+        this evaluate() and the shared inducing inputs.  Returns (bound, the training-side evaluation out[5]).
+        form='shared': the same bound on ONE copy of the inducing inputs (models/test_bound_d.py), no slots."""
         out = evaluate().clone()
         cols = np.flatnonzero(obs.any(axis=0))
         idx = torch.as_tensor(cols, device=device)
+        if form == 'shared':
+            bound = _TestBoundD(x_u.detach(), buf['gamma'][idx], buf['alpha'][idx, 0], buf['beta'][idx, 0], _t(y0[:, cols]),
+                                _t(obs[:, cols].T), device)
+            pred_state['missing_columns'] = _missing.missing_columns(obs)
+            return bound, out
         bound = _TestBound.slots(x_u.detach(), buf['gamma'][idx], buf['alpha'][idx, 0], buf['beta'][idx, 0],
                                  _t(y0[:, cols].T[:, :, None]), np.ones(cols.size), _t(obs[:, cols].T), device)
         pred_state['missing_columns'] = _missing.missing_columns(obs)
@@ -574,9 +581,13 @@ def dp_gp_lvm(y_train,
             mean[:, here], var[:, here] = mn[:, :, 0].transpose(0, 1), vr[:, :, 0].transpose(0, 1)
         return mean, var
 
-    def _not_built(name):
-        raise NotImplementedError('%s is not built for a model trained with observed=: use impute_training_data for the gaps of the '
-                                  'training data' % name)
+    def _reference_form_not_built(name, how):
+        raise NotImplementedError("%s: the reference's form of this call is not built for a model trained with observed=: %s"
+                                  % (name, how))
+
+    def _form_arg(form, observed):
+        assert form in ('slots', 'shared'), "form must be 'slots' or 'shared'"
+        assert form == 'slots' or observed is not None, "form='shared' is the masked test bound: it needs observed="
 
     class DP_GP_LVM(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508)."""
@@ -692,7 +703,8 @@ def dp_gp_lvm(y_train,
             return 0.5 * torch.sum(be[:, None] * (tr[None, :] - psi0[:, None])) - 0.5 * torch.sum(be * (tr - psi0))
 
         @staticmethod
-        def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
+        def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
+                                         observed=None):
             """Mirror of dp_gp_lvm.py:233-309: q(X*) for fully observed test data y_test [N* x D] and the prediction lower bound
                 f_hat + f_hat_test - KL(q(X)) - KL(q(X*)),    test log-likelihood = f_hat_test - KL(q(X*)),
             (without the reference's broadcasting defect in its beta (trace - psi_0) term, dp_gp_lvm.py:292 — see
@@ -700,9 +712,27 @@ def dp_gp_lvm(y_train,
             where f_hat_test is the SAME fused ELBO evaluated on (y_test, q(X*)) with the trained kernel and inducing inputs
             (one more dpgp_elbo_fhat call).  Returns (prediction_lower_bound, x_test_mean [N* x Q], x_test_covar [N* x Q x Q],
             test_log_likelihood) at the initial q(X*): nearest training neighbour + N(0, 0.01^2) noise, or PCA of y_test
-            (`use_pca`), or the given x_test_mean / x_test_var (values; what a caller's optimiser of q(X*) passes back in)."""
+            (`use_pca`), or the given x_test_mean / x_test_var (values; what a caller's optimiser of q(X*) passes back in).
+
+            On a model trained with observed=: the call takes observed=, a boolean [N* x D] mask as in predict_missing_data
+            (utils.missing.observed_mask(y_test) for gaps marked by NaN, all True for complete rows); f_hat_test is the
+            shared-inducing masked test bound (models/test_bound_d.py) with every measured entry counting, the training-side f_hat
+            the model's own masked one, q(X*) starts at the nearest training neighbour over the jointly observed columns.
+            Without observed= it is the reference's call, which such a model does not take: NotImplementedError.  AssertionError
+            for reference_compat=True; observed= is taken by such a model only."""
             if masked is not None:
-                _not_built('predict_new_latent_variables')
+                if observed is None:
+                    _reference_form_not_built('predict_new_latent_variables', 'pass observed=, the mask of the measured entries of '
+                                              'y_test [N* x D] (utils.missing.observed_mask(y_test) reads it off the NaNs)')
+                y0, obs = _masked(y_test, observed, reference_compat=reference_compat)
+                xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+                bound, out = _masked_bound(y0, obs, 'shared')
+                with torch.no_grad():
+                    f_hat_test, _, _ = bound.evaluate(xt, st_)
+                    pred_state['terms'] = bound.terms
+                    test_ll = f_hat_test - ops.kl_qx(xt, st_)
+                    return out[1] - out[2] + test_ll, xt, torch.diag_embed(st_), test_ll
+            assert observed is None, 'observed= is taken by a model trained with observed='
             assert not sharded and world == 1, 'prediction paths run on one GPU'
             y_test = np.asarray(y_test, dtype=np.float64)
             num_test_points, test_dims = np.shape(y_test)
@@ -719,14 +749,17 @@ def dp_gp_lvm(y_train,
             return lower_bound, xt, torch.diag_embed(st_), test_ll
 
         @staticmethod
-        def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
+        def test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None, form='slots'):
             """d (f_hat_test - KL(q(X*))) / d (x_test_mean, x_test_var) with the trained model fixed — what TensorFlow's autograd
             gives a caller of the reference who optimises q(X*) on the bounds returned by predict_*; y_test [N* x Do], Do <= D
             (the first Do output dims).  Uses the backward pass of the fused ELBO (stages A and B) on the test points.
             observed: as predict_missing_data (y_test [N* x D]; True everywhere is allowed here): the gradient of the masked
-            bound, fp64, by the weighted test-point operators."""
+            bound, fp64, by the weighted test-point operators.  form (with observed only, AssertionError otherwise): 'slots', one
+            slot with its own copy of Z, Psi1* and adjoint per output dim, or 'shared', the same bound on one copy of Z with no
+            [D x N* x M] array (models/test_bound_d.py, ops.psi_latent_adjoint)."""
+            _form_arg(form, observed)
             if observed is not None:
-                bound, _ = _masked_bound(*_masked(y_test, observed))
+                bound, _ = _masked_bound(*_masked(y_test, observed), form)
                 xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
                     _t(x_test_var.detach().cpu().numpy() if torch.is_tensor(x_test_var) else x_test_var)
                 with torch.no_grad():
@@ -748,14 +781,16 @@ def dp_gp_lvm(y_train,
 
         @staticmethod
         def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
-                                  x_test_var=None, observed=None):
+                                  x_test_var=None, observed=None, form='slots'):
             """Adam on q(X*) (mean and softplus-parametrised variances) maximising f_hat_test - KL(q(X*)) for test points
             observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*.  observed: as
-            predict_missing_data; the slots' factors are formed once, no host synchronisation inside the loop."""
+            predict_missing_data; the slots' factors are formed once, no host synchronisation inside the loop.  form: as
+            test_latent_gradients."""
+            _form_arg(form, observed)
             if observed is not None:
                 y0, obs = _masked(y_test, observed)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
-                bound, _ = _masked_bound(y0, obs)
+                bound, _ = _masked_bound(y0, obs, form)
                 raw = torch.log(torch.expm1(st_))
                 opt = torch.optim.Adam([xt, raw], lr=learning_rate)
                 with torch.no_grad():
@@ -793,7 +828,7 @@ def dp_gp_lvm(y_train,
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
-                                 observed=None, marginal_variance=False):
+                                 observed=None, marginal_variance=False, form='slots'):
             """Mirror of dp_gp_lvm.py:311-500: y_test [N* x Do] holds the FIRST Do output dims of the test points; returns
             (missing_data_lower_bound, x_test_mean, x_test_covar, predicted_mean [N* x Du], predicted_covar [Du x N* x N*])
             for the remaining Du = D - Do dims at the initial q(X*) (see predict_new_latent_variables).  Composed of the
@@ -811,14 +846,32 @@ def dp_gp_lvm(y_train,
             marginal_variance=True (extension): the last entry is the per-entry variance [N* x Du] of predictive_marginals on
             the predicted dims in place of the [Du x N* x N*] array.
 
-            On a model trained with observed= this method and predict_new_latent_variables are not built: NotImplementedError
-            (predictive_marginals gives the moments at test points, impute_training_data fills the training data's own gaps)."""
+            form (with observed only, AssertionError otherwise): 'slots' or 'shared', as test_latent_gradients: how f_hat* is evaluated.
+
+            On a model trained with observed=: y_test is [N* x D] (the reference's first-Do-columns form, a narrower y_test without
+            observed=, is not built for such a model: NotImplementedError), observed defaults to utils.missing.observed_mask(y_test)
+            (NaN = missing); f_hat* is always the shared-inducing bound, the training-side f_hat the model's own masked one, and the
+            last two entries are the per-entry moments of predictive_marginals on missing_columns, predicted_mean [N* x Du] and
+            predicted_var [N* x Du] — per entry whatever marginal_variance says (no [Du x N* x N*] array is built for such a
+            model).  AssertionError for reference_compat=True."""
+            _form_arg(form, observed if masked is None else True)
             if masked is not None:
-                _not_built('predict_missing_data')
+                if observed is None and np.ndim(y_test) == 2 and np.shape(y_test)[1] != num_dimensions:
+                    _reference_form_not_built('predict_missing_data', 'pass y_test [N* x D] with NaN at the missing entries, or with observed=')
+                y0, obs = _masked(y_test, _missing.observed_mask(y_test) if observed is None else observed, predict=True,
+                                  reference_compat=reference_compat)
+                xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
+                bound, out = _masked_bound(y0, obs, 'shared')
+                with torch.no_grad():
+                    f_hat_test, _, _ = bound.evaluate(xt, st_)
+                    pred_state['terms'] = bound.terms
+                    lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                    predicted_mean, predicted_var = _marginals_at_masked(pred_state['missing_columns'], xt, st_)
+                return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_var
             if observed is not None:
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
-                bound, out = _masked_bound(y0, obs)
+                bound, out = _masked_bound(y0, obs, form)
                 with torch.no_grad():
                     f_hat_test, _, _ = bound.evaluate(xt, st_)
                     pred_state['terms'] = bound.terms

@@ -383,6 +383,44 @@ def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
     return tr, quad
 
 
+def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
+    """(d_mu, d_s) [N*,Q] of  L = sum_b <g_psi2_b, sum_n weights[b,n] psi2_bn> + sum_b g_v_b . (Psi1_b^T y_b)  for B kernels
+    (gamma [B,Q], alpha [B]) that share the inducing inputs z [M,Q] and q(X*) = (mu, s) [N*,Q] (dpgp_psi_latent_adjoint_f64, fp64):
+    y [N*,B] zero-filled data (column b for kernel b; row stride free), g_v [B,M], g_psi2 [B,M,M] (any matrices), weights None
+    (all ones) or [B,N*] fp64 contiguous.  Derivatives with respect to the variances s.  Nothing of size B N* M or N* M M is
+    formed; fixed summation order, the same bits on every run."""
+    f64 = torch.float64
+    z, mu, s = _prep(z, f64, 'z'), _prep(mu, f64, 'mu'), _prep(s, f64, 's')
+    assert z.dim() == 2, 'z must be [M x Q]'
+    m, q = z.shape
+    assert mu.dim() == 2 and mu.shape[1] == q and s.shape == mu.shape, 'mu and s must be [N* x Q]'
+    n = mu.shape[0]
+    gamma = _prep(gamma, f64, 'gamma')
+    assert gamma.dim() == 2 and gamma.shape[1] == q, 'gamma must be [B x Q]'
+    b = gamma.shape[0]
+    alpha = _prep(alpha, f64, 'alpha').reshape(-1)
+    assert alpha.numel() == b, 'alpha must be [B]'
+    if not isinstance(y, torch.Tensor):
+        raise TypeError('y must be a torch.Tensor')
+    if y.dtype != f64 or not y.is_cuda or y.dim() != 2 or y.stride(1) != 1 or y.stride(0) < b:
+        y = _prep(y, f64, 'y')
+    assert tuple(y.shape) == (n, b), 'y must be [N* x B]'
+    g_v, g_psi2 = _prep(g_v, f64, 'g_v'), _prep(g_psi2, f64, 'g_psi2')
+    assert tuple(g_v.shape) == (b, m) and tuple(g_psi2.shape) == (b, m, m), 'g_v must be [B x M], g_psi2 [B x M x M]'
+    if weights is not None:
+        weights = _qx_weights(weights, b, n, mu)
+    d_mu = torch.empty((n, q), dtype=f64, device=mu.device)
+    d_s = torch.empty_like(d_mu)
+    l = _lib.lib()
+    wsb = l.dpgp_psi_latent_adjoint_workspace_bytes(b, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_psi_latent_adjoint_f64(b, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                             alpha.data_ptr(), y.data_ptr(), y.stride(0), None if weights is None else weights.data_ptr(),
+                                             g_v.data_ptr(), g_psi2.data_ptr(), d_mu.data_ptr(), d_s.data_ptr(), ws.data_ptr(), wsb,
+                                             _stream()), 'dpgp_psi_latent_adjoint_f64')
+    return d_mu, d_s
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

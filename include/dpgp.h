@@ -250,6 +250,28 @@ int dpgp_qx_psi_point_moments_f64(int K, int G, int J, int N, int M, int Q, cons
                                   const int *gidx, const double *beta, double *mean, double *var, void *ws, size_t ws_bytes,
                                   void *stream);
 
+/* ---- Latent adjoint of B kernels that share inducing inputs AND q(X*) (csrc/psi_latent_adjoint.hip): the frozen over-D model at
+ *      test time.  z[M][Q], q(X*) = (mu[N][Q], s[N][Q]: variances), gamma[B][Q], alpha[B]; y[N][ldy]: zero-filled data, column b
+ *      for kernel b; w[B][N]: weights of the test points (NULL = all ones; any finite reals); stage-A adjoints g_v[B][M] and
+ *      g_psi2[B][M][M] (any matrices: symmetry not assumed).  With psi1_bn[m], psi2_bn[m,m'] test point n's own terms of kernel b:
+ *        L = sum_b <g_psi2_b, sum_n w[b][n] psi2_bn> + sum_b g_v_b . (Psi1_b^T y_b)
+ *        d_mu[N][Q] = dL/dmu,   d_s[N][Q] = dL/ds           (no z, gamma or alpha outputs: the model is frozen)
+ *      Per kernel one product E[N x pairs] W[pairs x (1 + 2Q)] on the fp64 matrix pipe: a pair m <= m' is visited once, E is
+ *      made on the fly (one exponential per (b, n, pair); per chunk of 128 moment columns, i.e. twice at Q = 64), W is formed in
+ *      LDS from g_psi2 and z; the Psi1 term is the same product over single inducing points.  Nothing of size B (1 + 2Q) M M,
+ *      N M M or B N M is written to memory.  A workgroup owns 64 test points and a slab of kernels b, walked in ascending order;
+ *      the workspace holds the slabs' partial (d_mu, d_s) only and a second launch adds them in slab order: no atomics, the
+ *      same bits on every run.  A weight of 0 and a y of 0 contribute exactly 0.0.  1 <= B, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q;
+ *      ldy >= B.
+ *   Bad arguments, checked in this order before anything is launched:  B -1, N -2, M -3, Q -4, z -5, mu -6, s -7, gamma -8,
+ *      alpha -9, y -10, ldy -11, (w: nullable, no code), g_v -13, g_psi2 -14, d_mu -15, d_s -16, ws -17, ws_bytes too small -18.
+ *   ws: dpgp_psi_latent_adjoint_workspace_bytes(B,N,M,Q) (a host function; 0 for a shape out of range). */
+size_t dpgp_psi_latent_adjoint_workspace_bytes(int B, int N, int M, int Q);
+int dpgp_psi_latent_adjoint_f64(int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                const double *gamma, const double *alpha, const double *y, int ldy, const double *w,
+                                const double *g_v, const double *g_psi2, double *d_mu, double *d_s, void *ws, size_t ws_bytes,
+                                void *stream);
+
 /* ---- Kernel.covariance_diag (rbf_kernel.py:96-116): out[B,N] = alpha_b (+1/beta_b) (+jitter) */
 int dpgp_ard_rbf_diag_f32(int B, int N, const float *alpha, const float *beta, int flags, double jitter, float *out,
                           void *stream);

@@ -1,0 +1,218 @@
+"""GPU tests of the shared-inducing test bound of dp_gp_lvm (models/test_bound_d.py on ops.psi_latent_adjoint) and of what the model
+builds on it: form='shared' of test_latent_gradients / optimise_test_latents / predict_missing_data, and predict_missing_data /
+predict_new_latent_variables on a model trained with observed=.
+
+_TestBoundD against _TestBound.slots (one slot, with its own copy of Z, per column), the route the model took before: the bound to
+1e-10 relative, the [B x 5] terms to 1e-10, the gradients to 1e-8 of their largest entry (the adjoint measure of
+test_gpu_psi_latent_adjoint.py).  Kernels and inducing inputs of the fixtures dpgplvm_50_10_25_3_T8 and grad_ref_60_10_15_4_T5, test
+points near training rows, two masks each (30 % missing at random; the same with a column never observed, a row never observed and a
+column observed once), and an odd shape (M = 140 inducing points, N* = 7, random kernels)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import golden
+from test_gpu_train_masked_d import build_fixture, masks, points_near_training, softplus, trained_with_a_mask
+
+pytestmark = pytest.mark.gpu
+F64 = torch.float64
+MODEL_FIXTURE = 'grad_ref_60_10_15_4_T5'
+
+
+def kernels_of(name):
+    """(z, training latent means, y, gamma [D,Q], alpha [D], beta [D]) of a fixture or of the odd shape."""
+    if name == 'odd_140_7':
+        rs = np.random.default_rng(140)
+        q, d, m = 5, 6, 140
+        z = rs.standard_normal((m, q))
+        return z, z[:40], rs.standard_normal((40, d)), rs.uniform(0.5, 2.0, (d, q)), rs.uniform(0.5, 2.0, d), rs.uniform(2.0, 20.0, d)
+    g = golden(name)
+    if 'gamma' in g:
+        return g['z'], g['mu'], g['y'], g['gamma'], g['alpha'][:, 0], g['beta'][:, 0]
+    e = np.exp(g['dp_logits'] - g['dp_logits'].max(axis=1, keepdims=True))
+    phi = e / e.sum(axis=1, keepdims=True)
+    mix = lambda k: phi @ softplus(g[k])
+    return g['x_u'], g['x_mean'], g['y'], mix('gamma_atoms_raw'), mix('alpha_atoms_raw')[:, 0], mix('beta_atoms_raw')[:, 0]
+
+
+def points_for(name, kind):
+    z, x, y, gamma, alpha, beta = kernels_of(name)
+    n_t = 7 if name == 'odd_140_7' else 13
+    rs = np.random.default_rng(len(name) + n_t)
+    rows = rs.permutation(x.shape[0])[:n_t]
+    obs = masks(n_t, y.shape[1])[kind]
+    y0 = np.where(obs, y[rows] + 0.05 * rs.standard_normal((n_t, y.shape[1])), 0.0)
+    return z, gamma, alpha, beta, y0, obs, x[rows] + 0.05 * rs.standard_normal((n_t, x.shape[1])), rs.uniform(0.3, 1.0, (n_t, x.shape[1]))
+
+
+def adjoint_close(got, want, tol, what):
+    got, want = got.cpu().numpy(), want.cpu().numpy()
+    top = np.abs(want).max()
+    print('%s: max |err| %.3e of %.3e (bound %.0e of that)' % (what, np.abs(got - want).max(), top, tol))
+    np.testing.assert_allclose(got, want, rtol=0, atol=tol * top, err_msg=what)
+
+
+@pytest.mark.parametrize('kind', ['rand30', 'edge'])
+@pytest.mark.parametrize('name', ['dpgplvm_50_10_25_3_T8', 'grad_ref_60_10_15_4_T5', 'odd_140_7'])
+def test_the_shared_bound_equals_the_slots(dev, name, kind):
+    from dp_gp_lvm_amd.models.test_bound import _TestBound
+    from dp_gp_lvm_amd.models.test_bound_d import _TestBoundD
+    z, gamma, alpha, beta, y0, obs, xm, xv = points_for(name, kind)
+    cols = np.flatnonzero(obs.any(axis=0))
+    assert kind != 'edge' or cols.size == obs.shape[1] - 1
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=dev)
+    mu, s = t(xm), t(xv)
+    slots = _TestBound.slots(t(z), t(gamma[cols]), t(alpha[cols]), t(beta[cols]), t(y0[:, cols].T[:, :, None]), np.ones(cols.size),
+                             t(obs[:, cols].T.astype(np.float64)), dev)
+    shared = _TestBoundD(t(z), t(gamma[cols]), t(alpha[cols]), t(beta[cols]), t(y0[:, cols]), t(obs[:, cols].T.astype(np.float64)), dev)
+    f_want, dmu_want, ds_want = slots.evaluate(mu, s, grad=True)
+    f_got, dmu_got, ds_got = shared.evaluate(mu, s, grad=True)
+    assert not shared.info.any() and not shared.info_uu.any()
+    print('%s %s: bound %.15g (slots %.15g)' % (name, kind, float(f_got), float(f_want)))
+    np.testing.assert_allclose(float(f_got), float(f_want), rtol=1e-10)
+    assert tuple(shared.terms.shape) == (cols.size, 5) == tuple(slots.terms.shape)
+    want = slots.terms.cpu().numpy()
+    np.testing.assert_allclose(shared.terms.cpu().numpy(), want, rtol=1e-10, atol=1e-10 * max(1.0, np.abs(want).max()), err_msg='terms')
+    adjoint_close(dmu_got, dmu_want, 1e-8, 'd mean')
+    adjoint_close(ds_got, ds_want, 1e-8, 'd var')
+    # without grad: the same bound and the statistics it was made of
+    f_again, v, psi_2 = shared.evaluate(mu, s)
+    assert float(f_again) == float(f_got) and tuple(v.shape) == (cols.size, z.shape[0]) and tuple(psi_2.shape) == (cols.size,) + 2 * z.shape[:1]
+
+
+MODELS = {}
+
+
+def model_of(dev, which):
+    """'complete': the fixture trained on complete data (fp64); 'masked': on the 'edge' mask; 'all_true': on an all-True mask."""
+    if which not in MODELS:
+        g = golden(MODEL_FIXTURE)
+        if which == 'complete':
+            MODELS[which] = build_fixture(g, dev, None, precision='f64', backward_precision='f64')
+        elif which == 'masked':
+            MODELS[which] = trained_with_a_mask(dev, MODEL_FIXTURE, 'edge')[2]
+        else:
+            MODELS[which] = build_fixture(g, dev, np.ones(g['y'].shape, dtype=bool))
+    return golden(MODEL_FIXTURE), MODELS[which]
+
+
+@pytest.mark.parametrize('which', ['complete', 'masked'])
+def test_model_gradients_shared_against_slots(dev, which):
+    g, model = model_of(dev, which)
+    y_t, o_t, xm, xv = points_near_training(g, 21, n_t=9)
+    y_nan = np.where(o_t, y_t, np.nan)
+    want = model.test_latent_gradients(y_nan, xm, xv, observed=o_t)
+    terms_slots = model.prediction_terms.clone()
+    got = model.test_latent_gradients(y_nan, xm, xv, observed=o_t, form='shared')
+    for name, a, b in zip(('d mean', 'd var'), got, want):
+        assert tuple(a.shape) == xm.shape
+        adjoint_close(a, b, 1e-8, '%s model, %s' % (which, name))
+    np.testing.assert_allclose(model.prediction_terms.cpu().numpy(), terms_slots.cpu().numpy(), rtol=1e-10,
+                               atol=1e-10 * max(1.0, float(terms_slots.abs().max())))
+
+
+@pytest.mark.parametrize('which', ['complete', 'masked'])
+def test_twenty_adam_iterations_agree(dev, which):
+    g, model = model_of(dev, which)
+    y_t, o_t, xm, xv = points_near_training(g, 22, n_t=9)
+    y_nan = np.where(o_t, y_t, np.nan)
+    fits = [model.optimise_test_latents(y_nan, num_iterations=20, learning_rate=0.01, x_test_mean=xm, x_test_var=xv, observed=o_t, **kw)
+            for kw in (dict(), dict(form='shared'))]
+    for name, a, b in zip(('mean', 'var'), fits[1], fits[0]):
+        moved = float((b.cpu() - torch.as_tensor(xm if name == 'mean' else xv)).abs().max())
+        print('%s model, %s after 20 iterations: max |shared - slots| %.3e (moved by %.3e)' % (which, name, float((a - b).abs().max()), moved))
+        assert moved > 1e-3
+        np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), rtol=0, atol=1e-6)
+
+
+def test_prediction_on_a_mask_trained_model(dev):
+    from dp_gp_lvm_amd import ops
+    g, model = model_of(dev, 'masked')
+    y_t, o_t, xm, xv = points_near_training(g, 23, n_t=8)
+    o_t[:, 5] = True                                           # a column with nothing missing: not among the predicted ones
+    y_nan = np.where(o_t, y_t, np.nan)
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=F64, device=dev)
+    for observed in (o_t, None):                               # None: the mask is read off the NaNs
+        out = model.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=observed)
+        assert len(out) == 5
+        bound, x_m, x_c, mean, var = out
+        cols = np.flatnonzero(~o_t.all(axis=0))
+        assert np.array_equal(model.missing_columns, cols) and 5 not in cols and 2 in cols
+        assert tuple(mean.shape) == (8, cols.size) == tuple(var.shape) and tuple(x_c.shape) == (8, xm.shape[1], xm.shape[1])
+        np.testing.assert_array_equal(x_m.cpu().numpy(), xm)
+        np.testing.assert_array_equal(torch.diagonal(x_c, dim1=-2, dim2=-1).cpu().numpy(), xv)
+        f_star = float(model.prediction_terms.sum())
+        assert tuple(model.prediction_terms.shape) == (int(o_t.any(axis=0).sum()), 5)
+        kl_star = float(ops.kl_qx(t(xm), t(xv)))
+        terms = model.objective_terms
+        print('bound %.15g = f_hat %.15g + f_hat* %.15g - KL %.15g - KL* %.15g' % (float(bound), float(terms[1]), f_star, float(terms[2]), kl_star))
+        np.testing.assert_allclose(float(bound), float(terms[1]) + f_star - float(terms[2]) - kl_star, rtol=1e-10)
+        m_want, v_want = model.predictive_marginals(xm, xv, columns=cols)
+        np.testing.assert_allclose(mean.cpu().numpy(), m_want.cpu().numpy(), rtol=1e-12, atol=1e-12)
+        np.testing.assert_allclose(var.cpu().numpy(), v_want.cpu().numpy(), rtol=1e-12, atol=1e-12)
+        assert bool((var > 0).all())
+        # marginal_variance changes nothing for such a model
+        out_v = model.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=observed, marginal_variance=True, form='shared')
+        assert torch.equal(out_v[4], var) and torch.equal(out_v[3], mean) and float(out_v[0]) == float(bound)
+    # every measured entry counts in predict_new_latent_variables; gaps are allowed
+    from dp_gp_lvm_amd.utils import missing
+    for y_in, o_in in ((y_nan, missing.observed_mask(y_nan)), (y_nan, o_t), (y_t, np.ones(o_t.shape, dtype=bool))):
+        out = model.predict_new_latent_variables(y_in, x_test_mean=xm, x_test_var=xv, observed=o_in)
+        assert len(out) == 4
+        bound, x_m, x_c, test_ll = out
+        f_star = float(model.prediction_terms.sum())
+        np.testing.assert_allclose(float(test_ll), f_star - kl_star, rtol=1e-10)
+        np.testing.assert_allclose(float(bound), float(terms[1]) - float(terms[2]) + f_star - kl_star, rtol=1e-10)
+        np.testing.assert_array_equal(x_m.cpu().numpy(), xm)
+    assert tuple(model.prediction_terms.shape) == (g['y'].shape[1], 5)              # (the last call: complete test rows)
+    # the default start: the nearest training row over the jointly observed columns
+    out = model.predict_missing_data(y_nan)
+    assert tuple(out[1].shape) == xm.shape and bool(torch.isfinite(out[0])) and bool(torch.isfinite(out[3]).all())
+    out = model.predict_new_latent_variables(y_nan, observed=o_t)
+    assert tuple(out[1].shape) == xm.shape and bool(torch.isfinite(out[0]))
+
+
+def test_all_true_training_mask_equals_the_unmasked_model(dev):
+    g, masked_model = model_of(dev, 'all_true')
+    _, plain = model_of(dev, 'complete')
+    y_t, o_t, xm, xv = points_near_training(g, 24, n_t=8)
+    y_nan = np.where(o_t, y_t, np.nan)
+    got = masked_model.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=o_t)
+    for form in ('slots', 'shared'):
+        want = plain.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=o_t, marginal_variance=True, form=form)
+        assert np.array_equal(masked_model.missing_columns, plain.missing_columns)
+        print('form %s: bound %.15g (unmasked model %.15g)' % (form, float(got[0]), float(want[0])))
+        np.testing.assert_allclose(float(got[0]), float(want[0]), rtol=1e-9)
+        for name, a, b in zip(('mean', 'var'), got[3:], want[3:]):
+            b = b.cpu().numpy()
+            print('form %s, %s: max |err| %.3e of %.3e' % (form, name, np.abs(a.cpu().numpy() - b).max(), np.abs(b).max()))
+            np.testing.assert_allclose(a.cpu().numpy(), b, rtol=1e-9, atol=1e-9 * max(1.0, np.abs(b).max()), err_msg=name)
+
+
+def test_argument_checks(dev):
+    g, model = model_of(dev, 'complete')
+    _, masked_model = model_of(dev, 'masked')
+    y_t, o_t, xm, xv = points_near_training(g, 25)
+    y_nan = np.where(o_t, y_t, np.nan)
+    for m in (model, masked_model):
+        with pytest.raises(AssertionError):
+            m.test_latent_gradients(y_t[:, :4], xm, xv, form='shared')
+        with pytest.raises(AssertionError):
+            m.optimise_test_latents(y_t[:, :4], num_iterations=1, x_test_mean=xm, x_test_var=xv, form='shared')
+        with pytest.raises(AssertionError):
+            m.test_latent_gradients(y_nan, xm, xv, observed=o_t, form='blocks')
+    with pytest.raises(AssertionError):
+        model.predict_missing_data(y_t[:, :4], x_test_mean=xm, x_test_var=xv, form='shared')
+    with pytest.raises(AssertionError):
+        model.predict_new_latent_variables(y_t, x_test_mean=xm, x_test_var=xv, observed=o_t)     # a mask-trained model's argument
+    with pytest.raises(AssertionError):
+        masked_model.predict_missing_data(y_nan, x_test_mean=xm, x_test_var=xv, observed=o_t, reference_compat=True)
+    with pytest.raises(AssertionError):
+        masked_model.predict_new_latent_variables(y_nan, x_test_mean=xm, x_test_var=xv, observed=o_t, reference_compat=True)
+    with pytest.raises(AssertionError):
+        masked_model.predict_missing_data(y_t, x_test_mean=xm, x_test_var=xv)                    # nothing is missing
+    # the reference's forms of the two calls (no mask; the first Do columns) stay what they were on such a model
+    with pytest.raises(NotImplementedError):
+        masked_model.predict_new_latent_variables(y_t, x_test_mean=xm, x_test_var=xv)
+    with pytest.raises(NotImplementedError):
+        masked_model.predict_missing_data(y_t[:, :4], x_test_mean=xm, x_test_var=xv)
