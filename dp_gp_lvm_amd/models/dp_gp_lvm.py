@@ -28,11 +28,12 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
+from . import collapsed, marginals as _marginals
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
-from .test_bound import _TestBound
-from .test_bound_d import _TestBoundD
-from .test_bound_t import _MomentsT, _TestBoundT
+from .frozen_bound import _TestBound
+from .frozen_bound_d import _TestBoundD
+from .frozen_bound_t import _MomentsT, _TestBoundT
 
 
 def shard_bounds(num_dimensions, rank, world_size):
@@ -469,7 +470,7 @@ def dp_gp_lvm(y_train,
     def _masked_bound(y0, obs, form='slots'):
         """The fp64 test bound with one slot per output dim that has an observed entry: that dim's mixed (gamma, alpha, beta) of
         this evaluate() and the shared inducing inputs.  Returns (bound, the training-side evaluation out[5]).
-        form='shared': the same bound on ONE copy of the inducing inputs (models/test_bound_d.py), no slots."""
+        form='shared': the same bound on ONE copy of the inducing inputs (models/frozen_bound_d.py), no slots."""
         out = evaluate().clone()
         cols = np.flatnonzero(obs.any(axis=0))
         idx = torch.as_tensor(cols, device=device)
@@ -535,7 +536,6 @@ def dp_gp_lvm(y_train,
             sum_n var(n,d) = predicted_covar[d,0,0] + (N* - 1)/beta_d - 2 tr_term_d."""
         if masked is not None:
             return _marginals_at_masked(cols, xt, st_)
-        m_ = num_inducing_points
         idx = torch.as_tensor(np.asarray(cols), device=device)
         f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
         gu, au, bu = f64(buf['gamma'][idx]), f64(buf['alpha'][:, 0][idx]), f64(buf['beta'][:, 0][idx])
@@ -543,18 +543,13 @@ def dp_gp_lvm(y_train,
         psi_1 = ops.psi1(z, mu, s_train, gu, au)                                 # [K x N x M] (training)
         psi_2 = ops.psi2(z, mu, s_train, gu, au)
         k_uu = ops.ard_rbf_gram(z, None, gu, au, bu, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)
-        l_uu, _ = ops.potrf_batched(k_uu)
-        li = ops.tril_inverse_batched(l_uu)
-        tm = ops.matmul(ops.matmul(li, psi_2), li.transpose(1, 2))
-        l_a, _ = ops.potrf_batched((bu[:, None, None] * tm + torch.eye(m_, dtype=TORCH_DTYPE, device=device)).contiguous())
-        r0 = ops.matmul(ops.tril_inverse_batched(l_a), li)
-        pm = ops.matmul(r0.transpose(1, 2), r0)                                  # P_d
+        li, _ = collapsed.factors(k_uu)
+        r0 = collapsed.Chain(li, psi_2, bu).r0
         y_u = _t(np.asarray(y_train)[:, np.asarray(cols)]).to(TORCH_DTYPE).transpose(0, 1).contiguous()[:, :, None]
-        r = bu[:, None, None] * ops.matmul(pm, ops.matmul(psi_1.transpose(1, 2), y_u))           # [K x M x 1]
-        c = (ops.matmul(li.transpose(1, 2), li) - pm)[:, None]
+        r, c = collapsed.posterior(r0, collapsed.k_inverse(li), bu, ops.matmul(psi_1.transpose(1, 2), y_u))      # r [K x M x 1]
         gidx = torch.zeros((len(cols), 1), dtype=torch.int32, device=device)
-        mean, var = ops.qx_psi_point_moments(z[None].expand(len(cols), -1, -1).contiguous(), f64(xt), f64(st_), gu, au, c.contiguous(),
-                                             r.contiguous(), gidx, bu)
+        mean, var = ops.qx_psi_point_moments(z[None].expand(len(cols), -1, -1).contiguous(), f64(xt), f64(st_), gu, au,
+                                             c[:, None].contiguous(), r.contiguous(), gidx, bu)
         return mean[:, :, 0].transpose(0, 1).contiguous(), var[:, :, 0].transpose(0, 1).contiguous()
 
     def _marginals_at_masked(cols, xt, st_):
@@ -716,7 +711,7 @@ def dp_gp_lvm(y_train,
 
             On a model trained with observed=: the call takes observed=, a boolean [N* x D] mask as in predict_missing_data
             (utils.missing.observed_mask(y_test) for gaps marked by NaN, all True for complete rows); f_hat_test is the
-            shared-inducing masked test bound (models/test_bound_d.py) with every measured entry counting, the training-side f_hat
+            shared-inducing masked test bound (models/frozen_bound_d.py) with every measured entry counting, the training-side f_hat
             the model's own masked one, q(X*) starts at the nearest training neighbour over the jointly observed columns.
             Without observed= it is the reference's call, which such a model does not take: NotImplementedError.  AssertionError
             for reference_compat=True; observed= is taken by such a model only."""
@@ -756,7 +751,7 @@ def dp_gp_lvm(y_train,
             observed: as predict_missing_data (y_test [N* x D]; True everywhere is allowed here): the gradient of the masked
             bound, fp64, by the weighted test-point operators.  form (with observed only, AssertionError otherwise): 'slots', one
             slot with its own copy of Z, Psi1* and adjoint per output dim, or 'shared', the same bound on one copy of Z with no
-            [D x N* x M] array (models/test_bound_d.py, ops.psi_latent_adjoint)."""
+            [D x N* x M] array (models/frozen_bound_d.py, ops.psi_latent_adjoint)."""
             _form_arg(form, observed)
             if observed is not None:
                 bound, _ = _masked_bound(*_masked(y_test, observed), form)
@@ -1378,7 +1373,7 @@ def dp_gp_lvm_t(y_train,
             means = masked.posterior_means(x_u, x_mean, F.softplus(x_var_raw), gat, aat, bat, phi.transpose(0, 1).contiguous())
             return torch.where(torch.as_tensor(train_obs, device=device), y_dev, means)
 
-    # ---- prediction (models/test_bound_t.py): fp64, one GPU; the reference's own over-T predict_* raise NameError, so there is
+    # ---- prediction (models/frozen_bound_t.py): fp64, one GPU; the reference's own over-T predict_* raise NameError, so there is
     # nothing to mirror: the bound is the model's own masked bound on the test rows with everything trained held fixed
     pred_state = {}
 
@@ -1435,7 +1430,7 @@ def dp_gp_lvm_t(y_train,
         return init, var
 
     def _moments():
-        """The training side of the predictive moments (test_bound_t._MomentsT), formed once per call."""
+        """The training side of the predictive moments (frozen_bound_t._MomentsT), formed once per call."""
         gat, aat, bat, phit, s = _frozen()
         train = masked if masked is not None else \
             _MaskedBoundT(np.asarray(y_train, dtype=np.float64), np.ones((num_samples, num_dimensions), dtype=bool),
@@ -1444,9 +1439,7 @@ def dp_gp_lvm_t(y_train,
             return _MomentsT(train, x_u.detach(), x_mean.detach(), s, gat, aat, bat, phit)
 
     def _columns_arg(columns):
-        cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
-        assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
-        return torch.as_tensor(cols, dtype=torch.long, device=device)
+        return _marginals.columns_arg(columns, num_dimensions, device)
 
     class DP_GP_LVM_T(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
@@ -1514,7 +1507,7 @@ def dp_gp_lvm_t(y_train,
         def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None):
             """q(X*) for fully observed test data y_test [N* x D] and the prediction lower bound
                 f_hat + f_hat* - KL(q(X)) - KL(q(X*)),    test log-likelihood = f_hat* - KL(q(X*)),
-            f_hat* the model's own bound on (y_test, q(X*)) with everything trained held fixed (models/test_bound_t.py).  Returns
+            f_hat* the model's own bound on (y_test, q(X*)) with everything trained held fixed (models/frozen_bound_t.py).  Returns
             (prediction_lower_bound, x_test_mean [N* x Q], x_test_covar [N* x Q x Q], test_log_likelihood) at the initial q(X*):
             nearest training neighbour + N(0, 0.01^2) noise, or PCA of y_test (`use_pca`), or the given values; variances 1.
             fp64 and one GPU (AssertionError for a 'mixed' or sharded model)."""
@@ -1566,7 +1559,7 @@ def dp_gp_lvm_t(y_train,
         def predictive_marginals(x_test_mean, x_test_var, columns=None):
             """(mean, var), each [N* x len(columns)]: the per-entry moments of the mixture sum_t phi_td N(mean_t, var_t) of the
             output dims `columns` (default: all D) at q(X*) = (x_test_mean, x_test_var [N* x Q]); formulas in
-            models/test_bound_t._MomentsT, the Psi2 parts by ops.qx_psi_pointwise.  A column never observed in training has mean
+            models/frozen_bound_t._MomentsT, the Psi2 parts by ops.qx_psi_pointwise.  A column never observed in training has mean
             0 and variance sum_t phi_td (alpha_t + 1 / beta_t)."""
             cols = _columns_arg(columns)
             with torch.no_grad():

@@ -12,6 +12,7 @@ import torch
 from .. import ops
 from ..utils.constants import GP_DEFAULT_JITTER
 from ..utils.types import TORCH_DTYPE
+from . import collapsed
 
 
 class _TestBoundD:
@@ -19,12 +20,12 @@ class _TestBoundD:
     beta [B], y [N*,B] zero where unobserved, weights [B,N*] (1 where column b was measured at test point n).  fp64 on the device.
 
     Once per object (the trained model is frozen): K_b = K_uu(gamma_b, alpha_b) + jitter I = L L^T, L^-1, K_b^-1 on [B,M,M].
-    Per evaluation, with N_b = sum_n w_bn:  Psi2*_b = sum_n w_bn psi2_bn,  v_b = Psi1*_b^T y_b,
-        T = L^-1 Psi2* L^-T,  A = beta T + I = L_A L_A^T,  R0 = L_A^-1 L^-1,  u = R0 v,
+    Per evaluation, with N_b = sum_n w_bn:  Psi2*_b = sum_n w_bn psi2_bn,  v_b = Psi1*_b^T y_b, then models/collapsed.py with D = 1,
+    N_w = N_b, J = 1:
         f_hat*_b = 1/2 N_b (log beta - log 2 pi) - log|L_A| + 1/2 beta (tr T - alpha N_b) + 1/2 beta^2 |u|^2 - 1/2 beta |y_b|^2
     (the five terms of _TestBound.evaluate with D_b = 1 and N* -> N_b, in that order in self.terms [B x 5]) and, for the gradient,
-        G2 = 1/2 beta (K_b^-1 - P) - 1/2 beta^3 r r^T,   g_v = beta^2 r        (P = R0^T R0, r = R0^T u)
-    contracted with dPsi/d(mu, s) by ops.psi_latent_adjoint.  No host synchronisation.  self.info: failed factorisations of A."""
+    G2 in the difference form and g_v = beta^2 r, contracted with dPsi/d(mu, s) by ops.psi_latent_adjoint.  No host
+    synchronisation.  self.info: failed factorisations of A."""
 
     def __init__(self, z, gamma, alpha, beta, y, weights, device):
         f64 = TORCH_DTYPE
@@ -42,11 +43,9 @@ class _TestBoundD:
         self.n_w = torch.sum(self.weights, dim=1)
         self.yy = torch.sum(self.y * self.y, dim=0)
         ones = torch.ones(b, dtype=f64, device=device)
-        k_uu = ops.ard_rbf_gram(self.z, None, self.gamma, self.alpha, ones, include_noise=False, include_jitter=True,
-                                jitter=GP_DEFAULT_JITTER)
-        self.l_uu, self.info_uu = ops.potrf_batched(k_uu)
-        self.li = ops.tril_inverse_batched(self.l_uu)
-        self.kinv = ops.matmul(self.li.transpose(1, 2), self.li)
+        self.li, self.info_uu = collapsed.factors(ops.ard_rbf_gram(self.z, None, self.gamma, self.alpha, ones, include_noise=False,
+                                                                   include_jitter=True, jitter=GP_DEFAULT_JITTER))
+        self.kinv = collapsed.k_inverse(self.li)
         self.eye = torch.eye(m, dtype=f64, device=device)
         self.terms = self.info = None
 
@@ -56,21 +55,15 @@ class _TestBoundD:
         mu, s = mu.contiguous(), s.contiguous()
         psi_2 = ops.psi2(self.z, mu, s, self.gamma, self.alpha, weights=self.weights)
         v = ops.psi1T_y(self.z, mu, s, self.gamma, self.alpha, self.y)                       # [B, M]
-        tm = ops.matmul(ops.matmul(self.li, psi_2), self.li.transpose(1, 2))
-        l_a, self.info = ops.potrf_batched(be[:, None, None] * tm + self.eye)
-        r0 = ops.matmul(ops.tril_inverse_batched(l_a), self.li)
-        u = ops.matmul(r0, v[:, :, None])                                                    # [B, M, 1]
-        logdet = torch.sum(torch.log(torch.diagonal(l_a, dim1=-2, dim2=-1)), dim=-1)
-        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
-        self.terms = torch.stack([0.5 * n_w * (torch.log(be) - math.log(2.0 * math.pi)), -logdet, 0.5 * be * (tr - self.alpha * n_w),
-                                  0.5 * be * be * torch.sum(u * u, dim=(1, 2)), -0.5 * be * self.yy], dim=1)
+        ch = collapsed.Chain(self.li, psi_2, be, self.eye).project(v[:, :, None])             # u [B, M, 1]
+        self.info = ch.info
+        self.terms = torch.stack([0.5 * n_w * (torch.log(be) - math.log(2.0 * math.pi)), -ch.logdet, 0.5 * be * (ch.tr - self.alpha * n_w),
+                                  0.5 * be * be * torch.sum(ch.u * ch.u, dim=(1, 2)), -0.5 * be * self.yy], dim=1)
         f = torch.sum(self.terms)
         if not grad:
             return f, v, psi_2
-        r = ops.matmul(r0.transpose(1, 2), u)                                                # [B, M, 1]
-        p = ops.matmul(r0.transpose(1, 2), r0)
-        g2 = (0.5 * be)[:, None, None] * (self.kinv - p) - (0.5 * be ** 3)[:, None, None] * ops.matmul(r, r.transpose(1, 2))
-        g_v = (be * be)[:, None] * r[:, :, 0]
-        d_mu, d_s = ops.psi_latent_adjoint(self.z, mu, s, self.gamma, self.alpha, self.y, g_v.contiguous(), g2.contiguous(),
-                                           weights=self.weights)
+        adj = collapsed.Adjoint(ch)
+        g_v = (be * be)[:, None] * adj.r[:, :, 0]
+        d_mu, d_s = ops.psi_latent_adjoint(self.z, mu, s, self.gamma, self.alpha, self.y, g_v.contiguous(),
+                                           adj.g2_difference(self.kinv).contiguous(), weights=self.weights)
         return f, d_mu, d_s

@@ -30,10 +30,9 @@ from ..utils import missing as _missing
 from .dp_gp_lvm import dp_gp_lvm_t
 from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
-from .test_bound import _TestBound, _as_device
-from .slot_bound import kernel_slots
+from .frozen_bound import _TestBound, _as_device, kernel_slots
 from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
-from . import marginals as _marginals
+from . import collapsed, marginals as _marginals
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -231,15 +230,13 @@ def _predictive_moments(bound_u, c_index, x_mean, s_train, y_train_u, xt, st_):
     whose training C = L_A^-1 L^-1 Psi1^T enters kernel b's mean (b itself; the reference's MRD uses the last training view's C
     for every view, gaussian_process.py:938)."""
     psi_1, psi_2 = bound_u.psi(x_mean, s_train)
-    tm = ops.matmul(ops.matmul(bound_u.li, psi_2), bound_u.li.transpose(1, 2))
-    l_a, _ = ops.potrf_batched(bound_u.beta[:, None, None] * tm + bound_u.eye)
+    r0 = collapsed.Chain(bound_u.li, psi_2, bound_u.beta, bound_u.eye).r0                      # L_A^-1 L^-1 (training)
     psi_1t, psi_2t = bound_u.psi(xt, st_)
     n_t = xt.shape[0]
-    r0 = ops.matmul(ops.tril_inverse_batched(l_a), bound_u.li)                                 # L_A^-1 L^-1 (training)
     c_tr = ops.matmul(r0, psi_1.transpose(1, 2))                                             # [B, M, N]
     c_pred = ops.matmul(r0, psi_1t.transpose(1, 2))                                          # [B, M, N*]
     means, covars = [], []
-    p = ops.matmul(r0.transpose(1, 2), r0)                                                   # (K_uu + beta Psi2)^-1
+    p = collapsed.precision(r0)                                                              # (K_uu + beta Psi2)^-1
     gmat = psi_2t - ops.matmul(psi_1t.transpose(1, 2), psi_1t)
     tr = torch.diagonal(ops.matmul(bound_u.kinv - p, psi_2t), dim1=-2, dim2=-1).sum(-1)
     for b, y_u in enumerate(y_train_u):
@@ -412,7 +409,7 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
 
     def _test_bound(y_test):
         z, g, a, b = _frozen()
-        bound = _TestBound(z, g, a, b, [_as_device(y_test, dev_)], dev_)
+        bound = _TestBound.kernels(z, g, a, b, [_as_device(y_test, dev_)], dev_)
         pred_state['bound'] = bound
         return bound
 
@@ -578,7 +575,7 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
                     f_hat, kl = _train_terms()
                     kl_t = ops.kl_qx(xt, st_)
                     z, g, a, b = _frozen()
-                    plain = _TestBound(z, g, a, b, [torch.zeros((y0.shape[0], 1), dtype=TORCH_DTYPE, device=dev_)], dev_)
+                    plain = _TestBound.kernels(z, g, a, b, [torch.zeros((y0.shape[0], 1), dtype=TORCH_DTYPE, device=dev_)], dev_)
                     means, covars = _predictive_moments(plain, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
                                                         [_as_device(y_np[:, mc], dev_)], xt, st_)
                 covar = _marginals_at(xt, st_, mc)[1] if marginal_variance else covars[0]
@@ -837,7 +834,7 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
     def _test_bound(views_test):
         """Test bound of the first len(views_test) kernels (the observed views)."""
         with torch.no_grad():
-            bound = _TestBound(*_frozen(inner[:len(views_test)]), [_as_device(v, dev_) for v in views_test], dev_)
+            bound = _TestBound.kernels(*_frozen(inner[:len(views_test)]), [_as_device(v, dev_) for v in views_test], dev_)
         pred_state['bound'] = bound
         return bound
 
@@ -901,9 +898,8 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         for i, (v, cols, _) in enumerate(slots):
             y[i, :, :len(cols)] = y0s[v][:, cols]
         with torch.no_grad():
-            bound = kernel_slots(*_frozen(inner), [v for v, _, _ in slots], _as_device(y, dev_),
-                                            [len(c) for _, c, _ in slots], _as_device(np.stack([w for _, _, w in slots]), dev_),
-                                            dev_)
+            bound = kernel_slots(*_frozen(inner), [v for v, _, _ in slots], _as_device(y, dev_), [len(c) for _, c, _ in slots],
+                                 _as_device(np.stack([w for _, _, w in slots]), dev_), dev_)
         pred_state['bound'] = bound
         pred_state['missing_views'] = [v for v in range(num_views) if not obs[v].all()]
         pred_state['missing_columns'] = [_missing.missing_columns(obs[v]) for v in pred_state['missing_views']]
@@ -1040,8 +1036,8 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                     f_test, _, _ = bound.evaluate(xt, st_)
                     f_hat, kl = _train_terms()
                     kl_t = ops.kl_qx(xt, st_)
-                    bound_u = _TestBound(*_frozen([inner[v] for v in mv_]),
-                                         [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(mv_), dev_)
+                    bound_u = _TestBound.kernels(*_frozen([inner[v] for v in mv_]),
+                                                 [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(mv_), dev_)
                     means, covars = _predictive_moments(bound_u, list(range(len(mv_))), x_mean_t.detach(),
                                                         F.softplus(x_var_raw).detach(),
                                                         [_as_device(views_np[v][:, c], dev_) for v, c in zip(mv_, mc)], xt, st_)
@@ -1056,7 +1052,7 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             lb = _bound_at(views_test, xt, st_)
             ku = inner[vo:]
             with torch.no_grad():
-                bound_u = _TestBound(*_frozen(ku), [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(ku), dev_)
+                bound_u = _TestBound.kernels(*_frozen(ku), [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(ku), dev_)
                 c_index = [len(ku) - 1] * len(ku) if reference_compat else list(range(len(ku)))
                 means, covars = _predictive_moments(bound_u, c_index, x_mean_t.detach(), F.softplus(x_var_raw).detach(),
                                                     [_as_device(v, dev_) for v in views_np[vo:]], xt, st_)

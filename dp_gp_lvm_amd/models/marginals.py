@@ -16,6 +16,7 @@ import torch
 
 from .. import ops
 from ..utils.types import TORCH_DTYPE
+from . import collapsed
 
 
 class _Marginals:
@@ -49,11 +50,9 @@ def one_kernel(c, y, beta, slots, columns, d):
     device, m = y.device, c['r0'].shape[1]
     sel = torch.as_tensor(slots, dtype=torch.long, device=device)
     take = lambda t: t.index_select(0, sel).contiguous()
-    r0 = take(c['r0'])
-    pm = ops.matmul(r0.transpose(1, 2).contiguous(), r0)                                         # P_p [P, M, M]
     v = ops.matmul(take(c['psi_1']).transpose(1, 2).contiguous(), take(y))                      # Psi1^T Y_p [P, M, Dmax]
     be = beta.reshape(1)
-    rb = be[:, None, None] * ops.matmul(pm, v)
+    rb, cm = collapsed.posterior(take(c['r0']), take(c['kinv']), be, v)                      # per pattern [P, ...]
     r = torch.zeros((m, d), dtype=TORCH_DTYPE, device=device)
     gidx = torch.full((d,), -1, dtype=torch.int32, device=device)
     for p, cols in enumerate(columns):
@@ -62,7 +61,7 @@ def one_kernel(c, y, beta, slots, columns, d):
         gidx[ct] = p
     i0 = slots[0]
     return _Marginals(c['z'][i0:i0 + 1], c['gamma'][i0:i0 + 1], c['alpha'][i0:i0 + 1].reshape(1), be, c['zfac'][i0:i0 + 1],
-                      (take(c['kinv']) - pm)[None], r[None], gidx[None])
+                      cm[None], r[None], gidx[None])
 
 
 def of_masked_bound(bound, z, mu, s, gamma, alpha, beta, d):

@@ -3,7 +3,7 @@ The collapsed bound of bayesian_gp_lvm for TRAINING data with missing entries (o
 fp64 on the device.  With a boolean mask [N x D] the bound is a sum over output dims, dim d seeing only the rows R_d at which
 it was measured; columns that share one row pattern share a "slot" b (D_b columns, 0 / 1 row weights w_b, N_b = sum_n w_b[n]),
 and all slots share the one kernel (Z, gamma, alpha, beta).  The forward pass is the sum _TestBound.slots(...).evaluate computes
-(test_bound.py), evaluated at the training q(X); here Z and the hyper-parameters move, so K_uu and its factors are formed per
+(frozen_bound.py), evaluated at the training q(X); here Z and the hyper-parameters move, so K_uu and its factors are formed per
 evaluation and the bound is also differentiated with respect to them.
 """
 import math
@@ -14,103 +14,101 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..utils import missing as _missing
-from ..utils.constants import GP_DEFAULT_JITTER
 from ..utils.types import TORCH_DTYPE
+from . import collapsed
 
 
-class _MaskedBound:
-    """f = sum_b f_b with (T_b = L^-1 Psi2_b L^-T, A_b = beta T_b + I = L_A L_A^T, R0 = L_A^-1 L^-1, U = R0 Psi1^T Y_b)
-        f_b = 1/2 N_b D_b (log beta - log 2 pi) - D_b log|L_A| + 1/2 D_b beta (tr T_b - alpha N_b) + 1/2 beta^2 |U|^2 - 1/2 beta |Y_b|^2
-    Psi2_b the weighted sum over the rows of slot b (ops.qx_psi_stats_batched(weights=)), Y_b zero where unobserved.
+class _SlotBound:
+    """What _MaskedBound and _MaskedViewsBound share: B slots (column groups of one row pattern) as ONE batch of the weighted
+    operators.  slots: a list of (columns' data [N, D_b], row weights w_b [N]).  Per slot, in the symbols of models/collapsed.py
+    (D = D_b the slot's column count, N_w = N_b = sum_n w_b[n], no phi):
+        terms[b] = 1/2 N_b D_b (log beta - log 2 pi), -D_b log|L_A|, 1/2 D_b beta (tr T_b - alpha N_b), 1/2 beta^2 |U|^2, -1/2 beta |Y_b|^2
+    Psi2_b the weighted sum over the rows of slot b (ops.qx_psi_stats_batched(weights=)), Y_b zero where unobserved; G2 in the
+    product form and G1_b = beta^2 Y_b R^T go to ops.qx_psi_adjoint(weights=) for (mu, S) and to ops.qx_psi_param_adjoint for the
+    Psi part of (Z, gamma, alpha), per slot.  A subclass forms the kernels of the slots (chain) and adds the slots' parameter
+    adjoints and GK_b within their kernel (evaluate).  No host synchronisation."""
 
-    Backward pass (P = (K_uu + beta Psi2_b)^-1 = R0^T R0, R = P Psi1^T Y_b, KP = K_uu^-1 Psi2_b):
-        G2_b = 1/2 D_b beta^2 sym(KP P) - 1/2 beta^3 R R^T         (= 1/2 D_b beta (K_uu^-1 - P) - .., written as a product:
-        G1_b = beta^2 Y_b R^T                                         the difference cancels for a small beta |Psi2| / |K_uu|)
-        GK_b = -1/2 D_b beta^2 KP P KP^T - 1/2 beta^2 R R^T         (= 1/2 D_b (K_uu^-1 - P) - 1/2 D_b beta K_uu^-1 Psi2_b K_uu^-1 - ..)
-    (mu, S) through ops.qx_psi_adjoint(weights=), (Z, gamma, alpha) through Psi by ops.qx_psi_param_adjoint with the same G1, G2
-    (per slot, added here: the slots share the kernel), through K_uu by ONE ops.ard_rbf_gram_grad with GK = sum_b GK_b; beta and
-    alpha's explicit -1/2 D_b beta N_b are closed forms on the [B, M, M] arrays.  No host synchronisation."""
-
-    def __init__(self, y0, observed, device):
+    def __init__(self, slots, device):
         f64 = TORCH_DTYPE
-        groups = _missing.group_columns_by_pattern(observed)
-        assert groups, 'observed must hold at least one True entry'
-        n, dmax = y0.shape[0], max(len(c) for c, _ in groups)
-        y = np.zeros((len(groups), n, dmax))
-        for i, (cols, _) in enumerate(groups):
-            y[i, :, :len(cols)] = y0[:, cols]
-        self.groups = groups
-        self.b, self.n, self.device = len(groups), n, device
+        n, dmax = slots[0][0].shape[0], max(y.shape[1] for y, _ in slots)
+        y = np.zeros((len(slots), n, dmax))
+        for i, (ys, _) in enumerate(slots):
+            y[i, :, :ys.shape[1]] = ys
+        self.b, self.n, self.device = len(slots), n, device
         self.y = torch.as_tensor(y, dtype=f64, device=device).contiguous()                           # [B, N, Dmax]
         self.yy = torch.sum(self.y * self.y, dim=(1, 2))
-        self.dims = torch.tensor([float(len(c)) for c, _ in groups], dtype=f64, device=device)
-        self.weights = torch.as_tensor(np.stack([w for _, w in groups]), dtype=f64, device=device).contiguous()
+        self.dims = torch.tensor([float(ys.shape[1]) for ys, _ in slots], dtype=f64, device=device)
+        self.weights = torch.as_tensor(np.stack([w for _, w in slots]), dtype=f64, device=device).contiguous()
         self.n_w = torch.sum(self.weights, dim=1)
-        self.one = torch.ones(1, dtype=f64, device=device)
         self.terms = self.info = None
 
-    def chain(self, z, mu, s, gamma, alpha, beta):
-        """Everything up to the factor of A_b (shared by evaluate and the imputation)."""
-        b, m = self.b, z.shape[0]
-        gamma, alpha = gamma.reshape(1, -1), alpha.reshape(1)
-        k_uu = ops.ard_rbf_gram(z, None, gamma, alpha, self.one, include_noise=False, include_jitter=True,
-                                jitter=GP_DEFAULT_JITTER)
-        l_uu, info_uu = ops.potrf_batched(k_uu)
-        li = ops.tril_inverse_batched(l_uu)
-        kinv = ops.matmul(li.transpose(1, 2), li)
-        zfac = ops.ard_rbf_gram(z, None, 0.5 * gamma, alpha * alpha, self.one)
-        rep = lambda t: t.expand(b, *t.shape[1:]).contiguous()
-        c = dict(z=rep(z[None]), gamma=rep(gamma), alpha=rep(alpha), zfac=rep(zfac), li=rep(li), kinv=rep(kinv))
+    def _chain(self, c, mu, s, info_uu):
+        """c: the kernels gathered to the slots (z, gamma, alpha, beta, zfac, li, kinv); adds the statistics and the factors of
+        A_b (psi_1, psi_2, chain, and tm, l_a, r0 of it: what marginals.py reads)."""
         c['psi_1'], c['psi_2'] = ops.qx_psi_stats_batched(c['z'], mu, s, c['gamma'], c['alpha'], c['zfac'], weights=self.weights)
-        c['tm'] = ops.matmul(ops.matmul(c['li'], c['psi_2']), c['li'].transpose(1, 2))
-        eye = torch.eye(m, dtype=TORCH_DTYPE, device=self.device)
-        c['l_a'], info_a = ops.potrf_batched(beta.reshape(1, 1, 1) * c['tm'] + eye)
-        c['r0'] = ops.matmul(ops.tril_inverse_batched(c['l_a']), c['li'])
-        self.info = torch.maximum(info_uu.abs().max(), info_a.abs().max())
+        ch = c['chain'] = collapsed.Chain(c['li'], c['psi_2'], c['beta'])
+        c['tm'], c['l_a'], c['r0'] = ch.tm, ch.l_a, ch.r0
+        self.info = torch.maximum(info_uu.abs().max(), ch.info.abs().max())
         return c
+
+    def _forward(self, c):
+        """f, the projected chain and |U|^2 per slot; sets self.terms [B x 5]."""
+        be, al, dd, n_w = c['beta'], c['alpha'], self.dims, self.n_w
+        ch = c['chain'].project(ops.matmul(c['psi_1'].transpose(1, 2), self.y))                  # u [B, M, Dmax]
+        uu = torch.sum(ch.u * ch.u, dim=(1, 2))
+        self.terms = torch.stack([0.5 * n_w * dd * (torch.log(be) - math.log(2.0 * math.pi)), -dd * ch.logdet,
+                                  0.5 * dd * be * (ch.tr - al * n_w), 0.5 * be * be * uu, -0.5 * be * self.yy], dim=1)
+        return torch.sum(self.terms), ch, uu
+
+    def _backward(self, c, ch, uu, mu, s):
+        """(d_mu, d_s, the per-slot (d_z, d_gamma, d_alpha) through Psi, GK_b [B,M,M], the beta summand [B])."""
+        adj = collapsed.Adjoint(ch, self.dims)
+        g2 = adj.g2_product(c['kinv'])
+        g1 = (adj.b3 * adj.b3) * ops.matmul(self.y, adj.r.transpose(1, 2))                       # [B, N, M]
+        gk = adj.gk()
+        args = (c['z'], mu, s, c['gamma'], c['alpha'], g1, g2, c['zfac'])
+        d_mu, d_s = ops.qx_psi_adjoint(*args, weights=self.weights)
+        return d_mu, d_s, ops.qx_psi_param_adjoint(*args, weights=self.weights), gk, adj.d_beta(self.n_w, c['alpha'], uu, self.yy)
+
+    def posterior_means(self, z, mu, s, gamma, alpha, beta):
+        """[B, N, Dmax]: beta Psi1 (K_uu + beta Psi2_b)^-1 Psi1^T Y_b at every row, per slot, with the slot's kernel (Psi1 is not
+        weighted)."""
+        c = self.chain(z, mu, s, gamma, alpha, beta)
+        v = ops.matmul(c['psi_1'].transpose(1, 2), self.y)
+        return c['chain'].beta[:, None, None] * ops.matmul(c['psi_1'], ops.matmul(collapsed.precision(c['r0']), v))
+
+
+class _MaskedBound(_SlotBound):
+    """f = sum_b f_b over the column groups of ONE kernel (z [M,Q], gamma, alpha, beta): K_uu, its factors and the pair factor
+    are formed once and expanded to the slots; the slots' (Z, gamma, alpha, beta) adjoints are added with torch.sum, the K_uu
+    term is ONE ops.ard_rbf_gram_grad with GK = sum_b GK_b; alpha's explicit part is -1/2 beta sum_b D_b N_b."""
+
+    def __init__(self, y0, observed, device):
+        self.groups = _missing.group_columns_by_pattern(observed)
+        assert self.groups, 'observed must hold at least one True entry'
+        super().__init__([(y0[:, cols], w) for cols, w in self.groups], device)
+
+    def chain(self, z, mu, s, gamma, alpha, beta):
+        """Everything up to the factor of A_b (shared by evaluate, the imputation and marginals.py)."""
+        gamma, alpha = gamma.reshape(1, -1), alpha.reshape(1)
+        li, kinv, info_uu, zfac = collapsed.shared_z_kernels(z, gamma, alpha)
+        rep = lambda t: t.expand(self.b, *t.shape[1:]).contiguous()
+        c = dict(z=rep(z[None]), gamma=rep(gamma), alpha=rep(alpha), zfac=rep(zfac), li=rep(li), kinv=rep(kinv), beta=beta.reshape(1))
+        return self._chain(c, mu, s, info_uu)
 
     def evaluate(self, z, mu, s, gamma, alpha, beta, grad=False):
         """f (0-d); with grad also a dict of df/d(mu, s, z, gamma [Q], alpha, beta) (the values, not the raw variables).
         self.terms: [B x 5], self.info: 0 when K_uu and every A_b factorised."""
-        be, al, dd, n_w = beta.reshape(()), alpha.reshape(()), self.dims, self.n_w
         c = self.chain(z, mu, s, gamma, alpha, beta)
-        psi_1, psi_2, tm, r0 = c['psi_1'], c['psi_2'], c['tm'], c['r0']
-        u = ops.matmul(r0, ops.matmul(psi_1.transpose(1, 2), self.y))                            # [B, M, Dmax]
-        logdet = torch.sum(torch.log(torch.diagonal(c['l_a'], dim1=-2, dim2=-1)), dim=-1)
-        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
-        uu = torch.sum(u * u, dim=(1, 2))
-        self.terms = torch.stack([0.5 * n_w * dd * (torch.log(be) - math.log(2.0 * math.pi)), -dd * logdet,
-                                  0.5 * dd * be * (tr - al * n_w), 0.5 * be * be * uu, -0.5 * be * self.yy], dim=1)
-        f = torch.sum(self.terms)
+        f, ch, uu = self._forward(c)
         if not grad:
             return f
-        sym = lambda a: 0.5 * (a + a.transpose(1, 2))
-        d3 = dd[:, None, None]
-        r = ops.matmul(r0.transpose(1, 2), u)                                                     # [B, M, Dmax]
-        p = ops.matmul(r0.transpose(1, 2), r0)
-        rrt = ops.matmul(r, r.transpose(1, 2))
-        kp = ops.matmul(c['kinv'], psi_2)                                                         # K_uu^-1 Psi2_b
-        kpp = ops.matmul(kp, p)
-        g2 = (0.5 * be * be) * d3 * sym(kpp) - (0.5 * be ** 3) * rrt
-        g1 = (be * be) * ops.matmul(self.y, r.transpose(1, 2))                                   # [B, N, M]
-        gk = torch.sum((-0.5 * be * be) * d3 * sym(ops.matmul(kpp, kp.transpose(1, 2))) - (0.5 * be * be) * rrt, dim=0)
-        args = (c['z'], mu, s, c['gamma'], c['alpha'], g1, g2, c['zfac'])
-        d_mu, d_s = ops.qx_psi_adjoint(*args, weights=self.weights)
-        dz_b, dg_b, da_b = ops.qx_psi_param_adjoint(*args, weights=self.weights)
-        rk, sx, sq = ops.ard_rbf_gram_grad(z, gamma.reshape(1, -1), alpha.reshape(1), gk)
+        d_mu, d_s, (dz_b, dg_b, da_b), gk, db_b = self._backward(c, ch, uu, mu, s)
+        rk, sx, sq = ops.ard_rbf_gram_grad(z, gamma.reshape(1, -1), alpha.reshape(1), torch.sum(gk, dim=0))
         d_z = torch.sum(dz_b, dim=0) - 2.0 * gamma.reshape(1, -1) * sx
         d_gamma = torch.sum(dg_b, dim=0) - 0.5 * torch.sum(sq, dim=0)
-        d_alpha = torch.sum(da_b) + torch.sum(rk) / al - 0.5 * be * torch.sum(dd * n_w)
-        d_beta = torch.sum(0.5 * n_w * dd / be - 0.5 * dd * torch.sum(p * psi_2, dim=(1, 2)) + 0.5 * dd * (tr - al * n_w)
-                           + be * uu - (0.5 * be * be) * torch.sum(rrt * psi_2, dim=(1, 2)) - 0.5 * self.yy)
-        return f, dict(mu=d_mu, s=d_s, z=d_z, gamma=d_gamma, alpha=d_alpha, beta=d_beta)
-
-    def posterior_means(self, z, mu, s, gamma, alpha, beta):
-        """[B, N, Dmax]: beta Psi1 (K_uu + beta Psi2_b)^-1 Psi1^T Y_b at every row, per slot (Psi1 is not weighted)."""
-        c = self.chain(z, mu, s, gamma, alpha, beta)
-        p = ops.matmul(c['r0'].transpose(1, 2), c['r0'])
-        v = ops.matmul(c['psi_1'].transpose(1, 2), self.y)
-        return beta.reshape(()) * ops.matmul(c['psi_1'], ops.matmul(p, v))
+        d_alpha = torch.sum(da_b) + torch.sum(rk) / alpha.reshape(()) - 0.5 * beta.reshape(()) * torch.sum(self.dims * self.n_w)
+        return f, dict(mu=d_mu, s=d_s, z=d_z, gamma=d_gamma, alpha=d_alpha, beta=torch.sum(db_b))
 
 
 def _log_normal_prior(x):
@@ -176,34 +174,20 @@ class MaskedBayesianGPLVM:
             return torch.where(obs, torch.as_tensor(self.y0, dtype=TORCH_DTYPE, device=self.device), out)
 
 
-class _MaskedViewsBound:
-    """_MaskedBound for V views with their own kernels (Z_v, gamma_v, alpha_v, beta_v) sharing q(X): the slots of view v (the
-    column groups of its mask that share one row pattern) use kernel v, kern[b] = v.  The slots of all views are ONE batch,
-    ordered by view and then by first column: one weighted stats call, one adjoint and one parameter adjoint serve them all,
-    and the per-slot d_z, d_gamma, d_alpha, d_beta and GK_b are added within their view (index_add).  K_uu_v, L_v, L_v^-1,
-    K_uu_v^-1 and the pair factor are formed once per kernel per evaluation and gathered to the slots; the K_uu term of all V
-    kernels is ONE ops.ard_rbf_gram_grad_batched with GK_v = sum_{b in v} GK_b.  The formulas per slot are _MaskedBound's with
-    (alpha, beta) of the slot's kernel.  No host synchronisation."""
+class _MaskedViewsBound(_SlotBound):
+    """_MaskedBound for V views with their own kernels (Z_v, gamma_v, alpha_v, beta_v) sharing q(X): the slots of view v use
+    kernel v, kern[b] = v.  The slots of all views are ONE batch, ordered by view and then by first column; K_uu_v, its factors
+    and the pair factor are formed once per kernel per evaluation and gathered to the slots; the per-slot d_z, d_gamma,
+    d_alpha, d_beta and GK_b are added within their view (index_add), and the K_uu term of all V kernels is ONE
+    ops.ard_rbf_gram_grad_batched with GK_v = sum_{b in v} GK_b."""
 
     def __init__(self, y0s, observeds, device):
-        f64 = TORCH_DTYPE
         self.view_groups = [_missing.group_columns_by_pattern(o) for o in observeds]
         assert all(self.view_groups), 'every view must hold at least one True entry'
-        slots = [(v, cols, w) for v, gs in enumerate(self.view_groups) for cols, w in gs]
-        n, dmax = y0s[0].shape[0], max(len(c) for _, c, _ in slots)
-        y = np.zeros((len(slots), n, dmax))
-        for i, (v, cols, _) in enumerate(slots):
-            y[i, :, :len(cols)] = y0s[v][:, cols]
-        self.slots = slots
-        self.b, self.v, self.n, self.device = len(slots), len(y0s), n, device
-        self.kern = torch.tensor([v for v, _, _ in slots], dtype=torch.long, device=device)
-        self.y = torch.as_tensor(y, dtype=f64, device=device).contiguous()                           # [B, N, Dmax]
-        self.yy = torch.sum(self.y * self.y, dim=(1, 2))
-        self.dims = torch.tensor([float(len(c)) for _, c, _ in slots], dtype=f64, device=device)
-        self.weights = torch.as_tensor(np.stack([w for _, _, w in slots]), dtype=f64, device=device).contiguous()
-        self.n_w = torch.sum(self.weights, dim=1)
-        self.one = torch.ones(1, dtype=f64, device=device)
-        self.terms = self.info = None
+        self.slots = [(v, cols, w) for v, gs in enumerate(self.view_groups) for cols, w in gs]
+        super().__init__([(y0s[v][:, cols], w) for v, cols, w in self.slots], device)
+        self.v = len(y0s)
+        self.kern = torch.tensor([v for v, _, _ in self.slots], dtype=torch.long, device=device)
 
     def per_view(self, t):
         """[B, ...] per slot -> [V, ...]: the slots of a view added."""
@@ -211,66 +195,24 @@ class _MaskedViewsBound:
 
     def chain(self, z, mu, s, gamma, alpha, beta):
         """z [V,M,Q], gamma [V,Q], alpha [V], beta [V]: everything up to the factor of A_b."""
-        m = z.shape[1]
-        k_uu = torch.cat([ops.ard_rbf_gram(z[v], None, gamma[v:v + 1], alpha[v:v + 1], self.one, include_noise=False,
-                                           include_jitter=True, jitter=GP_DEFAULT_JITTER) for v in range(self.v)])
-        l_uu, info_uu = ops.potrf_batched(k_uu)
-        li = ops.tril_inverse_batched(l_uu)
-        kinv = ops.matmul(li.transpose(1, 2), li)
-        zfac = ops.qx_pair_factor(z, gamma, alpha)
+        li, kinv, info_uu, zfac = collapsed.own_z_kernels(z, gamma, alpha)
         take = lambda t: t.index_select(0, self.kern).contiguous()
         c = dict(z=take(z), gamma=take(gamma), alpha=take(alpha), beta=take(beta), zfac=take(zfac), li=take(li), kinv=take(kinv))
-        c['psi_1'], c['psi_2'] = ops.qx_psi_stats_batched(c['z'], mu, s, c['gamma'], c['alpha'], c['zfac'], weights=self.weights)
-        c['tm'] = ops.matmul(ops.matmul(c['li'], c['psi_2']), c['li'].transpose(1, 2))
-        eye = torch.eye(m, dtype=TORCH_DTYPE, device=self.device)
-        c['l_a'], info_a = ops.potrf_batched(c['beta'][:, None, None] * c['tm'] + eye)
-        c['r0'] = ops.matmul(ops.tril_inverse_batched(c['l_a']), c['li'])
-        self.info = torch.maximum(info_uu.abs().max(), info_a.abs().max())
-        return c
+        return self._chain(c, mu, s, info_uu)
 
     def evaluate(self, z, mu, s, gamma, alpha, beta, grad=False):
         """f (0-d); with grad also a dict of df/d(mu, s, z [V,M,Q], gamma [V,Q], alpha [V], beta [V]) (the values, not the raw
         variables).  self.terms: [B x 5], self.info: 0 when every K_uu_v and every A_b factorised."""
-        dd, n_w = self.dims, self.n_w
         c = self.chain(z, mu, s, gamma, alpha, beta)
-        be, al = c['beta'], c['alpha']                                                            # [B]: the slots' kernels'
-        psi_1, psi_2, tm, r0 = c['psi_1'], c['psi_2'], c['tm'], c['r0']
-        u = ops.matmul(r0, ops.matmul(psi_1.transpose(1, 2), self.y))                            # [B, M, Dmax]
-        logdet = torch.sum(torch.log(torch.diagonal(c['l_a'], dim1=-2, dim2=-1)), dim=-1)
-        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
-        uu = torch.sum(u * u, dim=(1, 2))
-        self.terms = torch.stack([0.5 * n_w * dd * (torch.log(be) - math.log(2.0 * math.pi)), -dd * logdet,
-                                  0.5 * dd * be * (tr - al * n_w), 0.5 * be * be * uu, -0.5 * be * self.yy], dim=1)
-        f = torch.sum(self.terms)
+        f, ch, uu = self._forward(c)
         if not grad:
             return f
-        sym = lambda a: 0.5 * (a + a.transpose(1, 2))
-        d3, b3 = dd[:, None, None], be[:, None, None]
-        r = ops.matmul(r0.transpose(1, 2), u)                                                     # [B, M, Dmax]
-        p = ops.matmul(r0.transpose(1, 2), r0)
-        rrt = ops.matmul(r, r.transpose(1, 2))
-        kp = ops.matmul(c['kinv'], psi_2)                                                         # K_uu^-1 Psi2_b
-        kpp = ops.matmul(kp, p)
-        g2 = (0.5 * b3 * b3) * d3 * sym(kpp) - (0.5 * b3 ** 3) * rrt
-        g1 = (b3 * b3) * ops.matmul(self.y, r.transpose(1, 2))                                   # [B, N, M]
-        gk = self.per_view((-0.5 * b3 * b3) * d3 * sym(ops.matmul(kpp, kp.transpose(1, 2))) - (0.5 * b3 * b3) * rrt)
-        args = (c['z'], mu, s, c['gamma'], c['alpha'], g1, g2, c['zfac'])
-        d_mu, d_s = ops.qx_psi_adjoint(*args, weights=self.weights)
-        dz_b, dg_b, da_b = ops.qx_psi_param_adjoint(*args, weights=self.weights)
-        rk, sx, sq = ops.ard_rbf_gram_grad_batched(z, gamma, alpha, gk)                           # [V,M], [V,M,Q], [V,M,Q]
+        d_mu, d_s, (dz_b, dg_b, da_b), gk, db_b = self._backward(c, ch, uu, mu, s)
+        rk, sx, sq = ops.ard_rbf_gram_grad_batched(z, gamma, alpha, self.per_view(gk))            # [V,M], [V,M,Q], [V,M,Q]
         d_z = self.per_view(dz_b) - 2.0 * gamma[:, None, :] * sx
         d_gamma = self.per_view(dg_b) - 0.5 * torch.sum(sq, dim=1)
-        d_alpha = self.per_view(da_b.reshape(-1) - 0.5 * be * dd * n_w) + torch.sum(rk, dim=1) / alpha
-        d_beta = self.per_view(0.5 * n_w * dd / be - 0.5 * dd * torch.sum(p * psi_2, dim=(1, 2)) + 0.5 * dd * (tr - al * n_w)
-                               + be * uu - (0.5 * be * be) * torch.sum(rrt * psi_2, dim=(1, 2)) - 0.5 * self.yy)
-        return f, dict(mu=d_mu, s=d_s, z=d_z, gamma=d_gamma, alpha=d_alpha, beta=d_beta)
-
-    def posterior_means(self, z, mu, s, gamma, alpha, beta):
-        """[B, N, Dmax]: beta_v Psi1_v (K_uu_v + beta_v Psi2_b)^-1 Psi1_v^T Y_b at every row, per slot (Psi1 is not weighted)."""
-        c = self.chain(z, mu, s, gamma, alpha, beta)
-        p = ops.matmul(c['r0'].transpose(1, 2), c['r0'])
-        v = ops.matmul(c['psi_1'].transpose(1, 2), self.y)
-        return c['beta'][:, None, None] * ops.matmul(c['psi_1'], ops.matmul(p, v))
+        d_alpha = self.per_view(da_b.reshape(-1) - 0.5 * c['beta'] * self.dims * self.n_w) + torch.sum(rk, dim=1) / alpha
+        return f, dict(mu=d_mu, s=d_s, z=d_z, gamma=d_gamma, alpha=d_alpha, beta=self.per_view(db_b))
 
 
 class MaskedMRD:

@@ -21,21 +21,18 @@ import torch.nn.functional as F
 from .. import ops
 from ..utils.constants import GP_DEFAULT_JITTER
 from ..utils.types import TORCH_DTYPE
+from . import collapsed
 
 
 class _MaskedBoundD:
-    """With K_d = K_uu(gamma_d, alpha_d) + jitter I = L L^T, T_d = L^-1 Psi2_d L^-T, A_d = beta_d T_d + I = L_A L_A^T,
-    R0 = L_A^-1 L^-1 (so P_d = (K_d + beta_d Psi2_d)^-1 = R0^T R0), u_d = R0 v_d:
+    """One slot per column d observed somewhere, in the symbols of models/collapsed.py with K_d = K_uu(gamma_d, alpha_d) +
+    jitter I, D = 1, N_w = N_d, J = 1 and no phi:
         terms[d] = 1/2 N_d (log beta_d - log 2 pi), -log|L_A|, 1/2 beta_d (tr T_d - alpha_d N_d), -1/2 beta_d y_d^T y_d,
                    1/2 beta_d^2 |u_d|^2
-    Adjoints (r_d = P_d v_d, KP = K_d^-1 Psi2_d; the product forms of masked_bound._MaskedViewsBound with one column per slot —
-    no K^-1 - P differences):
-        g_psi2_d = 1/2 beta_d^2 sym(KP P) - 1/2 beta_d^3 r r^T,   g_v_d = beta_d^2 r_d,
-        GK_d     = -1/2 beta_d^2 sym(KP P KP^T) - 1/2 beta_d^2 r r^T,   w_kuu_d = GK_d .* (K_d - jitter I)
+    Adjoints: g_psi2_d = G2 in the product form, g_v_d = beta_d^2 r_d, w_kuu_d = GK_d .* (K_d - jitter I),
         d alpha_d = -1/2 beta_d N_d + (sum w_kuu_d + 2 <g_psi2_d, Psi2_d> + g_v_d . v_d) / alpha_d
-        d beta_d  = 1/2 N_d / beta_d - 1/2 <P, Psi2_d> + 1/2 (tr T_d - alpha_d N_d) + beta_d |u_d|^2
-                    - 1/2 beta_d^2 r^T Psi2_d r - 1/2 y_d^T y_d
-    and (mu, S, z, gamma_d) by the weighted stage B on the adjoints padded to Mp.  No host synchronisation."""
+    d beta_d the core's summand, and (mu, S, z, gamma_d) by the weighted stage B on the adjoints padded to Mp.  No host
+    synchronisation."""
 
     def __init__(self, y0, observed, device):
         f64 = TORCH_DTYPE
@@ -68,20 +65,15 @@ class _MaskedBoundD:
         """gamma [Dc,Q], alpha [Dc], beta [Dc] of the batch columns: statistics and factors shared by the bound, its backward
         pass, the imputation and the predictive moments.  sel (long tensor): only these columns of the batch (gamma, alpha, beta
         are then theirs)."""
-        m = z.shape[0]
         y = self.y if sel is None else self.y.index_select(1, sel).contiguous()
         w = self.weights if sel is None else self.weights.index_select(0, sel).contiguous()
         c = dict(k_uu=ops.ard_rbf_gram(z, None, gamma, alpha, beta, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER))
-        l_k, info_k = ops.potrf_batched(c['k_uu'])
-        c['li'] = ops.tril_inverse_batched(l_k)
-        c['psi_2'] = ops.psi2(z, mu, s, gamma, alpha, weights=w)
+        c['li'], info_k = collapsed.factors(c['k_uu'])
+        psi_2 = ops.psi2(z, mu, s, gamma, alpha, weights=w)
         c['v'] = ops.psi1T_y(z, mu, s, gamma, alpha, y)                                     # [Dc, M]
-        c['tm'] = ops.matmul(ops.matmul(c['li'], c['psi_2']), c['li'].transpose(1, 2))
-        eye = torch.eye(m, dtype=TORCH_DTYPE, device=self.device)
-        c['l_a'], info_a = ops.potrf_batched((beta[:, None, None] * c['tm'] + eye).contiguous())
-        c['r0'] = ops.matmul(ops.tril_inverse_batched(c['l_a']), c['li'])
+        c['chain'] = collapsed.Chain(c['li'], psi_2, beta)
         if sel is None:
-            self.info = torch.maximum(info_k.abs(), info_a.abs()).to(torch.int32)
+            self.info = torch.maximum(info_k.abs(), c['chain'].info.abs()).to(torch.int32)
         return c
 
     def evaluate(self, z, mu, s, gamma, alpha, beta, grad=False):
@@ -89,33 +81,21 @@ class _MaskedBoundD:
         self.terms: [Dc x 5]; self.info [Dc]: 0 where K_d and A_d factorised."""
         n_d = self.n_d
         c = self.chain(z, mu, s, gamma, alpha, beta)
-        psi_2, v, tm, r0 = c['psi_2'], c['v'], c['tm'], c['r0']
-        u = ops.matmul(r0, v[:, :, None])                                                         # [Dc, M, 1]
-        logdet = torch.sum(torch.log(torch.diagonal(c['l_a'], dim1=-2, dim2=-1)), dim=-1)
-        tr = torch.diagonal(tm, dim1=-2, dim2=-1).sum(-1)
-        uu = torch.sum(u * u, dim=(1, 2))
-        self.terms = torch.stack([0.5 * n_d * (torch.log(beta) - math.log(2.0 * math.pi)), -logdet, 0.5 * beta * (tr - alpha * n_d),
-                                  -0.5 * beta * self.yy, 0.5 * beta * beta * uu], dim=1)
+        v, ch = c['v'], c['chain'].project(c['v'][:, :, None])                                    # u [Dc, M, 1]
+        uu = torch.sum(ch.u * ch.u, dim=(1, 2))
+        self.terms = torch.stack([0.5 * n_d * (torch.log(beta) - math.log(2.0 * math.pi)), -ch.logdet,
+                                  0.5 * beta * (ch.tr - alpha * n_d), -0.5 * beta * self.yy, 0.5 * beta * beta * uu], dim=1)
         f = torch.sum(self.terms).reshape(1)
         if not grad:
             return f
         m = z.shape[0]
         mp = 16 * ((m + 15) // 16)
-        sym = lambda a: 0.5 * (a + a.transpose(1, 2))
-        b3 = beta[:, None, None]
-        r = ops.matmul(r0.transpose(1, 2), u)                                                     # [Dc, M, 1]: P v
-        p = ops.matmul(r0.transpose(1, 2), r0)
-        rrt = r * r.transpose(1, 2)
-        kinv = ops.matmul(c['li'].transpose(1, 2), c['li'])
-        kp = ops.matmul(kinv, psi_2)
-        kpp = ops.matmul(kp, p)
-        g2 = (0.5 * b3 * b3) * sym(kpp) - (0.5 * b3 ** 3) * rrt
-        gk = (-0.5 * b3 * b3) * sym(ops.matmul(kpp, kp.transpose(1, 2))) - (0.5 * b3 * b3) * rrt
-        wk = gk * (c['k_uu'] - GP_DEFAULT_JITTER * torch.eye(m, dtype=TORCH_DTYPE, device=self.device))
-        gv = beta[:, None] ** 2 * r[:, :, 0]
-        d_alpha = -0.5 * beta * n_d + (wk.sum(dim=(1, 2)) + 2.0 * (g2 * psi_2).sum(dim=(1, 2)) + torch.sum(gv * v, dim=1)) / alpha
-        d_beta = 0.5 * n_d / beta - 0.5 * torch.sum(p * psi_2, dim=(1, 2)) + 0.5 * (tr - alpha * n_d) + beta * uu \
-            - (0.5 * beta * beta) * torch.sum(rrt * psi_2, dim=(1, 2)) - 0.5 * self.yy
+        adj = collapsed.Adjoint(ch, outer=torch.mul)
+        g2 = adj.g2_product(collapsed.k_inverse(c['li']))
+        wk = adj.gk() * (c['k_uu'] - GP_DEFAULT_JITTER * torch.eye(m, dtype=TORCH_DTYPE, device=self.device))
+        gv = beta[:, None] ** 2 * adj.r[:, :, 0]
+        d_alpha = -0.5 * beta * n_d + (wk.sum(dim=(1, 2)) + 2.0 * (g2 * ch.psi_2).sum(dim=(1, 2)) + torch.sum(gv * v, dim=1)) / alpha
+        d_beta = adj.d_beta(n_d, alpha, uu, self.yy)
         pad2 = (0, mp - m, 0, mp - m)
         d_mu, d_s, d_z, d_gamma = ops.elbo_grad_psi(self.y, z, mu, s, gamma, alpha, F.pad(g2, pad2).contiguous(),
                                                     F.pad(wk, pad2).contiguous(), F.pad(gv, (0, mp - m)).contiguous(), prec='f64',
@@ -125,6 +105,5 @@ class _MaskedBoundD:
     def posterior(self, z, mu, s, gamma, alpha, beta, sel=None):
         """(c_d = K_d^-1 - P_d [K,M,M], rhs_d = beta_d P_d v_d [K,M]): what the predictive moments of the batch columns `sel` need."""
         c = self.chain(z, mu, s, gamma, alpha, beta, sel=sel)
-        p = ops.matmul(c['r0'].transpose(1, 2), c['r0'])
-        rhs = beta[:, None] * ops.matmul(p, c['v'][:, :, None])[:, :, 0]
-        return ops.matmul(c['li'].transpose(1, 2), c['li']) - p, rhs
+        rhs, cm = collapsed.posterior(c['chain'].r0, collapsed.k_inverse(c['li']), beta, c['v'][:, :, None])
+        return cm, rhs[:, :, 0]

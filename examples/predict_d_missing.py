@@ -3,7 +3,7 @@
 Synthetic data: D = 8 phase-shifted sines of one latent coordinate.  The DP-GP-LVM (T = 3 atoms, every column its own mixed kernel)
 is trained on 60 rows with 30 % of their entries removed (observed=mask); 20 further rows arrive with 30 % of their entries missing.
 optimise_test_latents(..., form='shared') fits q(X*) to what was measured on one copy of the inducing inputs
-(models/test_bound_d.py) and predict_missing_data() returns the mean and variance of every entry of the columns that have gaps.
+(models/frozen_bound_d.py) and predict_missing_data() returns the mean and variance of every entry of the columns that have gaps.
 
     python examples/predict_d_missing.py [--iterations 300] [--test-iterations 100] [--seed 5]
 """

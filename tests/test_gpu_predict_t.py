@@ -1,4 +1,4 @@
-"""GPU tests of the over-T model's prediction paths (models/test_bound_t.py, DP_GP_LVM_T.predict_* / test_latent_gradients /
+"""GPU tests of the over-T model's prediction paths (models/frozen_bound_t.py, DP_GP_LVM_T.predict_* / test_latent_gradients /
 optimise_test_latents / predictive_marginals): the frozen test bound and its gradient against the committed fp64 oracle composed per
 column on its observed test rows (phi and every trained value constants), the per-entry moments against a NumPy restatement of
 their four formulas, T = 1 against bayesian_gp_lvm, one-hot phi against the over-D dp_gp_lvm, and fitting q(X*) end to end.

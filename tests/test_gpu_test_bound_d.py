@@ -1,4 +1,4 @@
-"""GPU tests of the shared-inducing test bound of dp_gp_lvm (models/test_bound_d.py on ops.psi_latent_adjoint) and of what the model
+"""GPU tests of the shared-inducing test bound of dp_gp_lvm (models/frozen_bound_d.py on ops.psi_latent_adjoint) and of what the model
 builds on it: form='shared' of test_latent_gradients / optimise_test_latents / predict_missing_data, and predict_missing_data /
 predict_new_latent_variables on a model trained with observed=.
 
@@ -55,8 +55,8 @@ def adjoint_close(got, want, tol, what):
 @pytest.mark.parametrize('kind', ['rand30', 'edge'])
 @pytest.mark.parametrize('name', ['dpgplvm_50_10_25_3_T8', 'grad_ref_60_10_15_4_T5', 'odd_140_7'])
 def test_the_shared_bound_equals_the_slots(dev, name, kind):
-    from dp_gp_lvm_amd.models.test_bound import _TestBound
-    from dp_gp_lvm_amd.models.test_bound_d import _TestBoundD
+    from dp_gp_lvm_amd.models.frozen_bound import _TestBound
+    from dp_gp_lvm_amd.models.frozen_bound_d import _TestBoundD
     z, gamma, alpha, beta, y0, obs, xm, xv = points_for(name, kind)
     cols = np.flatnonzero(obs.any(axis=0))
     assert kind != 'edge' or cols.size == obs.shape[1] - 1

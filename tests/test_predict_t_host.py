@@ -1,9 +1,9 @@
-"""CPU tests (no GPU) of mixture_moments (models/test_bound_t.py): the per-entry mean and variance of the over-T model's
+"""CPU tests (no GPU) of mixture_moments (models/frozen_bound_t.py): the per-entry mean and variance of the over-T model's
 mixture over the atoms, sum_t phi_td N(mean_t(n,d), var_t(n,d))."""
 import numpy as np
 import torch
 
-from dp_gp_lvm_amd.models.test_bound_t import mixture_moments
+from dp_gp_lvm_amd.models.frozen_bound_t import mixture_moments
 
 
 def random_case(t, n, j, seed):

@@ -2,7 +2,7 @@
 # medians of 15 timings; the spread of a form is min to max of 7 repeats of that median; the two forms of (a) take turns within
 # every repeat.
 #   python tools/time_point_moments.py [ops] [model]
-# (a) ops:   ops.qx_psi_point_moments against the composition of the operators that existed before it, as test_bound_t._MomentsT.at
+# (a) ops:   ops.qx_psi_point_moments against the composition of the operators that existed before it, as frozen_bound_t._MomentsT.at
 #            composes them: ops.qx_psi_pointwise, ops.psi1 (Psi1* [K,N,M] in memory), ops.matmul, two gathers, element-wise work.
 #            The condition of 7.12: the fused median is no greater than the largest of the composition's 7 repeats.
 # (b) model: predictive_marginals and impute_training_data(return_variance=True) of a mask-trained bayesian_gp_lvm at the three

@@ -18,8 +18,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dp_gp_lvm_amd import _lib, ops                                     # noqa: E402
-from dp_gp_lvm_amd.models.test_bound import _TestBound                  # noqa: E402
-from dp_gp_lvm_amd.models.test_bound_d import _TestBoundD               # noqa: E402
+from dp_gp_lvm_amd.models.frozen_bound import _TestBound                # noqa: E402
+from dp_gp_lvm_amd.models.frozen_bound_d import _TestBoundD           # noqa: E402
 
 dev = torch.device('cuda', 0)
 f64 = dict(dtype=torch.float64, device=dev)
