@@ -266,7 +266,7 @@ extern "C" int dpgp_elbo_grad_chain_big(int D, int N, int M, int Q, const double
 // factors are used as they are, and part 1 of the pair-tile form (images of the observations, pass 1) has already run on this
 // workspace (elbo_run with pgws).
 struct GradPsiWs { unsigned char *consts; double *part, *ws1, *stage; unsigned char *pgws; };
-// patch-form partials of the Psi2 term: only where that form can run (asked for, or no pair-tile form: Q > 20)
+// patch-form partials of the Psi2 term: only where that form can run (asked for, or no pair-tile form: Q > 21, psi2_pgrad_supported)
 static bool grad_psi_needs_patch(int M, int Q, bool patch_form) {
     return patch_form || !psi2_pgrad_supported(M, Q) || getenv("DPGP_GRAD_PATCH");
 }
@@ -326,7 +326,7 @@ extern "C" size_t dpgp_elbo_grad_psi_workspace_bytes_ex(int D, int N, int M, int
     if (prec == DPGP_PREC_F64 || !psi2_grad_supported(M, Q) || getenv("DPGP_GRAD_PLAIN"))
         return dpgp_align256(psi_grad_ws_bytes(D, N, M, Q, nullptr));        // the plain kernel only (with its [D][N][Q] partials)
     // mixed precisions: the plain kernel carries the K_uu term only; then the psi2 constants, the patch-form partials (where that form
-    // can run), the Psi1 term's partials, the reduction stage and the pair-tile form (Q <= 20: its images and the two passes' results —
+    // can run), the Psi1 term's partials, the reduction stage and the pair-tile form (Q <= 21: its images and the two passes' results —
     // not when the patch form is asked for)
     const bool patch = (prec == DPGP_PREC_MIXED_PATCH);
     const size_t mx = (size_t)Q * (N > D ? (N > M ? N : M) : (D > M ? D : M));
@@ -453,7 +453,8 @@ extern "C" int dpgp_elbo_fhat(int D, int N, int M, int Q, const double *y, int l
                              ws_bytes, stream, nullptr);
 }
 
-// ---- training step (mixed precision, M <= 128, Q <= 20): f_hat terms AND the stage-A / stage-B gradients of one evaluation.
+// ---- training step (mixed precision, M <= 128, Q <= 21 = the pair-tile form's limit; the model offers it up to Q = 20,
+// ops.elbo_step_supported): f_hat terms AND the stage-A / stage-B gradients of one evaluation.
 // What one Adam iteration of the reference needs (forward + tf.gradients, test/synthetic_data_hard_test.py:143-155).  Compared
 // with dpgp_elbo_fhat + dpgp_elbo_grad_chain + dpgp_elbo_grad_psi the exponentials of the Psi2 statistic are evaluated twice
 // instead of three times: pass 1 of stage B (rows = observations, columns = pairs of inducing points) does not depend on the

@@ -258,7 +258,10 @@ template int launch_chain_grad<double>(int, int, int, const double *, int, const
 //   log psi2 = 2 log alpha - sum_q [ 1/2 log den2 + 1/4 gamma (z_a - z_m')^2 + gamma (mu - (z_a + z_m')/2)^2 / den2 ],  den2 = 2 gamma S + 1
 //   log psi1 =   log alpha - 1/2 sum_q [ log den1 + gamma (mu - z_a)^2 / den1 ],                                       den1 = gamma S + 1
 // ---------------------------------------------------------------------------------------------------------------
-#define PG_RED_ELEMS(Q) ((size_t)1024)       // wave sums [4][5 Q + 2] <= 608; 256 doubles of column-mean scratch
+// psi_grad_kernel's `red` area: wave sums [4][5 Q + 2] (<= 648 elements), and 256 doubles (512 floats) of column-mean scratch.  Sized
+// exactly: with a flat 1024 elements the fp64 kernel wanted 166 240 B of LDS at Mp = 128, Q = 17 .. 20 and could not be launched
+// (now 162 144 B at Q = 20; Mp = 128 with Q >= 21 is still beyond the 160 KB)
+#define PG_RED_ELEMS(Q) ((size_t)(4 * (5 * (Q) + 2) > 512 ? 4 * (5 * (Q) + 2) : 512))
 __device__ __forceinline__ float pg_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 __device__ __forceinline__ double pg_exp(double x) { return exp(x); }
 // QP: latent dims padded to a multiple of 4 (compile time, so that the per-thread q-arrays stay in registers)
@@ -973,6 +976,7 @@ int launch_psi_grad(int D, int N, int M, int Q, const double *y, int ldy, const 
 #undef CASE
     }
     if (!kern) return -4;
+    if (lds > 160 * 1024) return -30;                          // (beyond the LDS: fp64 at Mp = 128 with Q >= 21 — unsupported, as Mp > 128 is)
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess)

@@ -143,7 +143,7 @@ int launch_psi2_grad(int B, int N, int M, int Q, const unsigned char *consts, co
 #define DPGP_LB_TILE_ELEMS (16 * 17)   // elements of one tile of the lb_out image (= TSZ of linalg_dev.h)
 #define DPGP_PREP_ROWS 16   // output dims per row-block of dpgp_model_prepare (scal has 2 + ceil(D / 16) entries)
 
-// ---- psi2_pairs_grad.hip: the Psi2 term of stage B in the pair-tile form (Q <= 10) ---------------------------------------
+// ---- psi2_pairs_grad.hip: the Psi2 term of stage B in the pair-tile form (Q <= 21) ---------------------------------------
 bool psi2_pgrad_supported(int M, int Q);
 size_t psi2_pgrad_ws_bytes(int D, int N, int M, int Q);
 // which: 1 = the part that does not depend on the adjoints (observation images, pass 1; psi2_part / scale != nullptr: Psi2 as a

@@ -33,7 +33,7 @@ typedef unsigned pg_u4 __attribute__((ext_vector_type(4)));
 #define PG_FB 32                     // feature rows of one block of the second product (one 32-row matrix instruction)
 
 // Kernel configuration by the K-steps of the exponent product (KS = psi2_pairs_ksteps(Q)):
-//   NFB  feature blocks of 32 rows of the second product (2Q + 1 features: Q <= 15 one block, Q <= 20 two)
+//   NFB  feature blocks of 32 rows of the second product (2Q + 1 features: Q <= 15 one block, Q <= 21 two)
 //   G    resident column tiles per wave;  NW waves per workgroup, ONE workgroup per compute unit (two waves per SIMD, 256
 //        registers per lane, the whole LDS): with G = 4 and four waves (round 3) the new loop spilled its column operands
 //   WPS  waves per SIMD the register allocation allows (workgroups per compute unit = 4 WPS / NW, each with its share of the LDS)
@@ -55,8 +55,8 @@ template <> struct PgCfg<6> { static constexpr int NFB = 1, G = 2, NW = 8, WPS =
 #endif
 template <> struct PgCfg<8> { static constexpr int NFB = 2, G = PG_G8, NW = PG_NW8, WPS = PG_WPS8; };   // (G = 2 at two waves per SIMD spills 130 registers)
 __host__ __device__ inline int pg_nfb(int KS) { return KS >= 8 ? 2 : 1; }
-// 1 KB pieces of the feature image of one row tile.  One block: [hi | lo] x [K-step 0 | 1].  Two blocks (33 .. 41 features, Q = 16 .. 20):
-// the second block holds at most 9 features — its hi words sit in rows 0-15 and its lo words in rows 16-31 of ONE operand, so that
+// 1 KB pieces of the feature image of one row tile.  One block: [hi | lo] x [K-step 0 | 1].  Two blocks (33 .. 43 features, Q = 16 .. 21):
+// the second block holds at most 11 features — its hi words sit in rows 0-15 and its lo words in rows 16-31 of ONE operand, so that
 // (X_hi, W_hi) and (X_lo, W_hi) are one matrix instruction and the block needs no lo plane: 6 pieces, 5 products per K-step half instead
 // of 8 and 6 (the rows r and r + 16 of its result are added in the pass kernel's epilogue)
 __host__ __device__ constexpr int pg_xp(int NFB) { return NFB == 2 ? 6 : 4; }
@@ -1202,6 +1202,11 @@ __global__ void pg_poison_kernel(const int *__restrict__ flag, double *dmu, doub
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
+// The limit is Q <= 21: eight K-steps hold 6 Q + 2 <= 128 slots (psi2_pairs_ksteps) and two feature blocks 2 Q + 1 = 43 <= 48 features.
+// Everything sized by Q in this file holds at 21: pg_obs_row's QM = (16 KS - 2) / 6 = 21, pg_pair_images_kernel's 3 q + 2 < SLP / 2
+// guard (3 * 20 + 2 = 62 < 64), the blocks of four latent dims of pg_finish_pairs_kernel / pg_finish_obs_kernel (grid.z = ceil(Q / 4),
+// each guarded by q < Q) and PG_QP_SWITCH's QP = 24 instance of pg_finish_m1_kernel.  (dpgp_elbo_step is offered up to Q = 20 by
+// ops.elbo_step_supported: the model's choice of path, not a limit of these kernels.)
 bool psi2_pgrad_supported(int M, int Q) {
     const int ks = psi2_pairs_ksteps(Q);
     return ks <= 8 && 2 * Q + 1 <= (pg_nfb(ks) == 2 ? 48 : PG_FB) && M >= 1 && M <= 4096;   // (a second block holds 16 features: pg_xp)
@@ -1216,14 +1221,18 @@ template <int KS> static int pg_ring_tiles() {                   // row tiles pe
     }
     return NTb;
 }
-// finishing kernels: per-thread arrays of QP = 4 ceil(Q / 4) entries (Q <= 20 here; arrays of DPGP_MAX_Q doubles spill)
+// finishing kernels: per-thread arrays of QP = 4 ceil(Q / 4) entries (Q <= 21 here: psi2_pgrad_supported; arrays of DPGP_MAX_Q doubles
+// spill).  A Q beyond the largest instance is an error, never a smaller instance: pg_finish_m1_kernel<NF, 20> at Q = 21 summed 20
+// latent dims and then read red[w][40 .. 41], one row past its [4][2 QP] array, into dz[:, 20].
 #define PG_QP_SWITCH(Q, CALL)                                   \
     switch (((Q) + 3) / 4) {                                    \
         case 1: { constexpr int QP_ = 4; CALL; } break;         \
         case 2: { constexpr int QP_ = 8; CALL; } break;         \
         case 3: { constexpr int QP_ = 12; CALL; } break;        \
         case 4: { constexpr int QP_ = 16; CALL; } break;        \
-        default: { constexpr int QP_ = 20; CALL; } break;       \
+        case 5: { constexpr int QP_ = 20; CALL; } break;        \
+        case 6: { constexpr int QP_ = 24; CALL; } break;        \
+        default: return -4;                                     \
     }
 #define PG_DC_PAIRS 16               // chunks of output dims of the finishing kernels
 #define PG_DC_OBS 64
@@ -1322,7 +1331,9 @@ static int pg_launch_pass(int D, const _Float16 *rimg, int row_per_d, const _Flo
     if constexpr (KS >= 8 && G0 == 1) {
         // two resident column tiles per wave (one register set for the exponent operand: 248 registers) halve the ring fills and the LDS
         // reads per step
-        if (cost(2, 920) <= cost(1, 1000) && !getenv("DPGP_PG_G1"))   // (DPGP_PG_G1: experiments)
+        const char *e = getenv("DPGP_PG_G");                       // (experiments and tests: 1 or 2; DPGP_PG_G1: experiments)
+        const int force = e ? atoi(e) : 0;
+        if (force == 2 || (force != 1 && cost(2, 920) <= cost(1, 1000) && !getenv("DPGP_PG_G1")))
             return pg_launch_pass_g<KS, WLO, 2>(D, rimg, row_per_d, ximg, cimg, col_per_d, out, n_row_tiles, n_col_tiles, po, st);
     }
     return pg_launch_pass_g<KS, WLO, G0>(D, rimg, row_per_d, ximg, cimg, col_per_d, out, n_row_tiles, n_col_tiles, po, st);

@@ -197,7 +197,8 @@ def dp_gp_lvm(y_train,
         if masked is None else None
     s_1, s_2 = dp_model.prior
 
-    # one training step through dpgp_elbo_step (mixed precision, M <= 128, Q <= 20: DESIGN.md section 7.1): the forward's psi2 dispatch is
+    # one training step through dpgp_elbo_step (mixed precision, where ops.elbo_step_supported offers it: M <= 128 and, by choice,
+    # Q <= 20): the forward's psi2 dispatch is
     # replaced by the first pass of stage B (DPGP_FUSED_STEP=0: the three separate calls, e.g. for bench.py's per-stage breakdown)
     # fp64 forward + 'mixed' stage B: pair-tile or patch form by the conditioning of K_uu (see _gradients; DPGP_ADAPTIVE_STAGE_B=0: always
     # the patch form)
@@ -319,7 +320,8 @@ def dp_gp_lvm(y_train,
     def _gradients(events=None):
         """d objective / d (raw trainable variables) — what tf.gradients(objective, trainable variables) gives the
         reference's optimiser (test/synthetic_data_hard_test.py:143-155).  dpgp_elbo_step (one call: forward, stage A, stage B;
-        mixed precision, M <= 128, Q <= 20) or one forward evaluation, then dpgp_elbo_grad_chain and dpgp_elbo_grad_psi; then
+        mixed precision, where ops.elbo_step_supported offers it: M <= 128, Q <= 20) or one forward evaluation, then
+        dpgp_elbo_grad_chain and dpgp_elbo_grad_psi; then
         dpgp_model_backward; sharded over D, the per-GPU
         partial gradients are packed into one buffer and sum-all-reduced.  Returns {name: tensor} keyed like ``raw``.
         events: optional list of 4 torch.cuda.Event(enable_timing=True), recorded after the forward evaluation, stage A,

@@ -750,7 +750,9 @@ def elbo_fhat_t(y, yy, z, mu, s, gamma_atoms, alpha_atoms, beta_atoms, phit, jit
 
 
 def elbo_step_supported(m, q):
-    """dpgp_elbo_step: B_d in LDS (M <= 128) and the pair-tile form of stage B (Q <= 20)."""
+    """Where the models take dpgp_elbo_step: B_d in LDS (M <= 128) and Q <= 20.  The Q bound is this function's choice (the step was
+    tuned and measured up to the BASELINE configs' Q = 20), not the kernels' limit: the pair-tile form of stage B, and with it
+    dpgp_elbo_step, takes Q <= 21 (psi2_pgrad_supported, csrc/psi2_pairs_grad.hip); at Q = 21 the models take the three calls."""
     return 16 * ((int(m) + 15) // 16) <= 128 and int(q) <= 20
 
 

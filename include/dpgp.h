@@ -421,7 +421,7 @@ int dpgp_elbo_grad_chain_big(int D, int N, int M, int Q, const double *z, const 
  *   DPGP_PREC_MIXED: fp32 arithmetic, fp64 sums of the per-workgroup partial results, any M: the Psi2 term on the matrix pipe
  *     (psi2_grad_kernel: the forward's f16-split exponent tiles, a second MFMA product for the z-weighted column sums), the
  *     Psi1 term by two reduction-free kernels, the K_uu term without a pass over the observations;
- *   DPGP_PREC_F64: one plain kernel, M <= 128 (-30 otherwise).
+ *   DPGP_PREC_F64: one plain kernel, M <= 128, and at 113 <= M <= 128 Q <= 20: M x M adjoint and z in 160 KB of LDS (-30 otherwise).
  * M may exceed N (prediction evaluates few test points).  ws: dpgp_elbo_grad_psi_workspace_bytes_ex(D,N,M,Q,prec) — the
  * images and results of the pair-tile form (the bulk: ~1.6 GB at N=2000, D=512, M=128, Q=10) are only part of it for
  * DPGP_PREC_MIXED; dpgp_elbo_grad_psi_workspace_bytes(D,N,M,Q) = the largest of the three (works for every prec).            */
@@ -455,7 +455,7 @@ int dpgp_elbo_grad_psi_ex(int D, int N, int M, int Q, const double *y, int ldy, 
  * one call — what one Adam iteration of every training script of the reference evaluates (objective + tf.gradients,
  * test/synthetic_data_hard_test.py:143-155; forward src/models/dp_gp_lvm.py:108-145, src/kernels/rbf_kernel.py:135-199).
  * Mixed precision (prec = DPGP_PREC_MIXED, as of the three calls it replaces: dpgp_elbo_fhat_ex + dpgp_elbo_grad_chain +
- * dpgp_elbo_grad_psi; or DPGP_PREC_MIXED_FAST for stage B), M <= 128 (-3), Q <= 20 (-4).  Same results as the three calls within the mixed-precision tolerance; the
+ * dpgp_elbo_grad_psi; or DPGP_PREC_MIXED_FAST for stage B), M <= 128 (-3), Q <= 21 (-4: the pair-tile form of stage B).  Same results as the three calls within the mixed-precision tolerance; the
  * Psi2 statistic comes out of the first pass of stage B (same exponentials, constant feature), so its exponentials are
  * evaluated twice per step instead of three times — the minimum: Psi2 is needed before the adjoints exist, the observation-side sums
  * after; Psi1^T y likewise comes out of the Psi1 term's adjoint-free pass (its y-weighted constant feature).  exec (may be NULL): with
