@@ -11,6 +11,9 @@ parameter values, and ``objective`` re-evaluates on every access.
 Multi-GPU: the per-output-dimension terms are independent given (q(X), Z, atoms), so the D outputs are sharded over the
 ranks of ``process_group`` (rank r keeps columns r*D/W .. (r+1)*D/W of Y and the matching rows of phi); q(X), Z and the
 atoms are replicated.  The only exchange per evaluation is a sum all-reduce of the two scalars (f_hat, DP objective).
+The same holds for a model trained with observed= (its bound runs on the local columns observed somewhere, possibly none), for the
+per-entry moments and for the shared-inducing test bound, whose sums over columns are completed by one all-reduce each
+(DESIGN.md section 7.15).
 """
 import os
 import numpy as np
@@ -32,7 +35,7 @@ from . import collapsed, marginals as _marginals
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .frozen_bound import _TestBound
-from .frozen_bound_d import _TestBoundD
+from .frozen_bound_d import _ShardedTestBoundD, _TestBoundD
 from .frozen_bound_t import _MomentsT, _TestBoundT
 
 
@@ -41,6 +44,41 @@ def shard_bounds(num_dimensions, rank, world_size):
     base, rem = divmod(num_dimensions, world_size)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+def weighted_shard_bounds(costs, rank, world_size, align=1):
+    """Contiguous split of the D = len(costs) output dims by cost: rank r owns [lo, hi), every bound a multiple of `align` (or D),
+    and the largest share's cost is the smallest any contiguous aligned split into world_size shares can have.  Exact dynamic
+    programme over the D / align units (prefix sums; O(world_size units^2), host only, deterministic: every rank computes the same
+    bounds).  Among the splits with that largest share it prefers a small sum of squared shares, then late cuts, which for equal
+    costs is shard_bounds.  No share is empty while world_size <= ceil(D / align); beyond that the first units get a rank each."""
+    costs = np.asarray(costs, dtype=np.float64).reshape(-1)
+    d, align = costs.size, int(align)
+    assert align >= 1 and world_size >= 1 and 0 <= rank < world_size and d >= 1 and (costs >= 0).all(), \
+        'weighted_shard_bounds: costs must be non-negative, 0 <= rank < world_size, align >= 1'
+    units = -(-d // align)
+    if world_size >= units:
+        cuts = [min(k, units) for k in range(world_size + 1)]
+    else:
+        prefix = np.concatenate([[0.0], np.cumsum(np.add.reduceat(costs, np.arange(0, d, align)))])
+        # best[k][i]: (largest share, sum of squares, first cut) of the units i.. split into k non-empty shares
+        best = [[None] * (units + 1) for _ in range(world_size + 1)]
+        for i in range(units):
+            c = prefix[units] - prefix[i]
+            best[1][i] = (c, c * c, units)
+        for k in range(2, world_size + 1):
+            for i in range(units - k + 1):
+                pick = None
+                for c in range(i + 1, units - k + 2):
+                    head, rest = prefix[c] - prefix[i], best[k - 1][c]
+                    cand = (max(head, rest[0]), head * head + rest[1], c)
+                    if pick is None or cand[:2] <= pick[:2]:
+                        pick = cand                      # (ties: the later cut)
+                best[k][i] = pick
+        cuts = [0]
+        for k in range(world_size, 0, -1):
+            cuts.append(best[k][cuts[-1]][2])
+    return min(cuts[rank] * align, d), min(cuts[rank + 1] * align, d)
 
 
 def _adam(params, learning_rate):
@@ -62,7 +100,7 @@ def dp_gp_lvm(y_train,
               alpha_prior_params=DP_DEFAULT_ALPHA_PRIOR_PARAMS,
               mask_size=1,
               device=None, precision=None, process_group=None, initial_values=None, backward_precision=None,
-              psi_algo='auto', _shard_of=None, observed=None):
+              psi_algo='auto', _shard_of=None, observed=None, shard_by='count'):
     """
     :param y_train: [N x D] numpy array, columns normalised to zero mean / unit variance (dp_gp_lvm.py:30-32).
     :param num_latent_dims: Q.  :param num_inducing_points: M.  :param truncation_level: T.
@@ -84,17 +122,26 @@ def dp_gp_lvm(y_train,
            array).  f_hat is then the sum over the columns d observed somewhere of the unmasked model's five terms on the rows R_d
            at which d was measured (N -> N_d, Psi2_d and y_d^T y_d over R_d, Psi1_d^T y_d on the zero-filled column): the fp64
            operators of the unmasked precision='f64' model with a 0 / 1 weight per (column, row) on the Psi2 sum and its adjoint
-           (models/masked_bound_d.py), evaluated eagerly on one GPU — precision and backward_precision None or 'f64',
-           process_group None.  KL(q(X)) runs over all N rows, the DP objective over all D columns, the hyper-prior over the T
+           (models/masked_bound_d.py), evaluated eagerly — precision and backward_precision None or 'f64'.
+           KL(q(X)) runs over all N rows, the DP objective over all D columns, the hyper-prior over the T
            atoms; a column never observed contributes its DP terms only, a row never observed its KL only.  x_mean defaults to the
            PCA of the column-mean-filled data.  impute_training_data() fills the gaps with the posterior mean.
+           With process_group every rank is given the full y_train and the full mask and keeps its columns of both; the bound runs
+           on the local columns observed somewhere, which may be none (such a rank contributes f_hat = 0 and zero partial
+           derivatives and still joins every collective); the exchanges are the unmasked model's.
+    :param shard_by: how the D columns are split over the ranks: 'count' (shard_bounds: equal numbers of columns) or, with observed
+           only, 'observed' (weighted_shard_bounds on a cost of 1 + the number of observed rows per column, aligned to mask_size).
     """
     num_samples, num_dimensions = np.shape(y_train)
     train_obs = None
+    assert shard_by in ('count', 'observed'), "shard_by must be 'count' or 'observed'"
+    assert shard_by == 'count' or observed is not None, "shard_by='observed' splits by the mask: it needs observed="
     if observed is not None:
         assert precision in (None, 'f64'), "with observed, precision must be None or 'f64' (the masked model is fp64)"
         assert backward_precision in (None, 'f64'), "with observed, backward_precision must be None or 'f64' (the masked model is fp64)"
-        assert process_group is None and _shard_of is None, 'with observed, process_group must be None (the masked model is not sharded)'
+        if process_group is not None:
+            import torch.distributed as dist_
+            assert isinstance(process_group, dist_.ProcessGroup), 'process_group must be a torch.distributed process group'
         train_obs = _missing.check_observed(observed, (num_samples, num_dimensions))
         assert train_obs.any(), 'observed must hold at least one True entry'
         y_train = _missing.zero_filled(y_train, train_obs)
@@ -179,9 +226,13 @@ def dp_gp_lvm(y_train,
     else:
         dist, rank, world = None, 0, 1
     sharded = process_group is not None          # (a 1-rank group still goes through pack -> all_reduce -> finalize)
-    d_lo, d_hi = shard_bounds(num_dimensions, rank, world)
+    if shard_by == 'observed':
+        d_lo, d_hi = weighted_shard_bounds(train_obs.sum(axis=0) + 1, rank, world, mask_size)
+    else:
+        d_lo, d_hi = shard_bounds(num_dimensions, rank, world)
     d_local = d_hi - d_lo
     assert d_local > 0, 'more ranks than output dimensions'
+    split = sharded or world > 1                 # (this object holds a share of the columns: prediction assembles over the ranks)
     y_local = _t(np.asarray(y_train)[:, d_lo:d_hi])                            # [N x D_local]
 
     # ---- device buffers of one objective evaluation (allocated once) ----
@@ -192,7 +243,9 @@ def dp_gp_lvm(y_train,
                scal=torch.zeros(_lib.lib().dpgp_model_scal_count(d_local), **f64),
                red=torch.zeros(2, **f64), out=torch.zeros(5, **f64))
     # observed=: f_hat and its derivatives come from models/masked_bound_d.py; nothing of the fused pipeline is used (no workspace)
-    masked = _MaskedBoundD(np.asarray(y_train, dtype=np.float64), train_obs, device) if train_obs is not None else None
+    # (sharded: the bound of the local columns; a share with no observed column is an empty batch)
+    masked = _MaskedBoundD(np.asarray(y_train, dtype=np.float64)[:, d_lo:d_hi], train_obs[:, d_lo:d_hi], device) \
+        if train_obs is not None else None
     workspace = ops.ElboWorkspace(d_local, num_samples, num_inducing_points, num_latent_dims, precision, device) \
         if masked is None else None
     s_1, s_2 = dp_model.prior
@@ -264,9 +317,9 @@ def dp_gp_lvm(y_train,
         _lib.check(lib.dpgp_model_prepare(
             d_local, truncation_level, num_latent_dims, num_samples, d_lo, mask_size, r['logits'].data_ptr(),
             gamma_atoms_raw.data_ptr(), sig_var_atoms_raw.data_ptr(), beta_atoms_raw.data_ptr(), x_var_raw.data_ptr(),
-            r['gamma_1'].data_ptr(), r['gamma_2'].data_ptr(), r['w'].data_ptr(), s_1, s_2, 1, buf['gamma'].data_ptr(),
-            buf['alpha'].data_ptr(), buf['beta'].data_ptr(), buf['s'].data_ptr(), buf['phi'].data_ptr(), buf['scal'].data_ptr(), st),
-            'dpgp_model_prepare')
+            r['gamma_1'].data_ptr(), r['gamma_2'].data_ptr(), r['w'].data_ptr(), s_1, s_2, 1 if rank == 0 else 0,
+            buf['gamma'].data_ptr(), buf['alpha'].data_ptr(), buf['beta'].data_ptr(), buf['s'].data_ptr(), buf['phi'].data_ptr(),
+            buf['scal'].data_ptr(), st), 'dpgp_model_prepare')
         with torch.no_grad():
             gam = masked.take(buf['gamma']).contiguous()
             al, be = masked.take(buf['alpha']).reshape(-1).contiguous(), masked.take(buf['beta']).reshape(-1).contiguous()
@@ -274,6 +327,8 @@ def dp_gp_lvm(y_train,
             f, grads = res if grad else (res, None)
             kl = ops.kl_qx(x_mean.detach(), buf['s']).reshape(1)
         _lib.check(lib.dpgp_model_pack(d_local, f.data_ptr(), buf['scal'].data_ptr(), buf['red'].data_ptr(), st), 'dpgp_model_pack')
+        if sharded:                                         # the only exchange: (f_hat, DP objective) of the local columns
+            dist.all_reduce(buf['red'], op=dist.ReduceOp.SUM, group=process_group)
         _lib.check(lib.dpgp_model_finalize(buf['red'].data_ptr(), kl.data_ptr(), buf['scal'][1:2].data_ptr(), out.data_ptr(), st),
                    'dpgp_model_finalize')
         return out, grads
@@ -465,15 +520,28 @@ def dp_gp_lvm(y_train,
         pred_state['terms'] = terms_t.clone()
         return sums[0].clone(), sums[1].clone()
 
-    def _masked(y_test, observed, predict=False, reference_compat=False):
-        assert not sharded and world == 1, 'prediction paths run on one GPU'
+    ONE_GPU = "on a model sharded over a process group the test-time paths run the shared-inducing masked bound only: pass " \
+              "observed= with form='shared' (form='slots' and the reference's own forms of the prediction paths run on one GPU)"
+
+    def _masked(y_test, observed, predict=False, reference_compat=False, form='shared'):
+        assert not split or form == 'shared', ONE_GPU
         return _missing.masked_arguments(y_test, observed, num_dimensions, predict, reference_compat)
 
     def _masked_bound(y0, obs, form='slots'):
         """The fp64 test bound with one slot per output dim that has an observed entry: that dim's mixed (gamma, alpha, beta) of
         this evaluate() and the shared inducing inputs.  Returns (bound, the training-side evaluation out[5]).
-        form='shared': the same bound on ONE copy of the inducing inputs (models/frozen_bound_d.py), no slots."""
+        form='shared': the same bound on ONE copy of the inducing inputs (models/frozen_bound_d.py), no slots.
+        A sharded model ('shared' only): the bound of the local columns that have an observed test entry, wrapped so that one
+        evaluation is one packed all-reduce (frozen_bound_d._ShardedTestBoundD); `out` is the global training-side evaluation."""
         out = evaluate().clone()
+        if split:
+            assert form == 'shared', ONE_GPU
+            here = np.flatnonzero(obs[:, d_lo:d_hi].any(axis=0))                 # local indices
+            idx = torch.as_tensor(here, device=device)
+            local = _TestBoundD(x_u.detach(), buf['gamma'][idx], buf['alpha'][idx, 0], buf['beta'][idx, 0], _t(y0[:, d_lo + here]),
+                                _t(obs[:, d_lo + here].T), device) if here.size else None
+            pred_state['missing_columns'] = _missing.missing_columns(obs)
+            return _ShardedTestBoundD(local, obs.shape[0], num_latent_dims, device, process_group if sharded else None), out
         cols = np.flatnonzero(obs.any(axis=0))
         idx = torch.as_tensor(cols, device=device)
         if form == 'shared':
@@ -487,6 +555,14 @@ def dp_gp_lvm(y_train,
         return bound, out
 
     def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
+        """The start of q(X*) on the full y_train and the full masks (every rank holds them).  A start the caller did not supply
+        draws np.random.normal noise: sharded, rank 0's is broadcast once, so that the replicas of q(X*) start bit-identical."""
+        xt, st_ = _masked_init_local(y0, obs, use_pca, x_test_mean, x_test_var)
+        if sharded and x_test_mean is None:
+            dist.broadcast(xt, src=dist.get_global_rank(process_group, 0), group=process_group)
+        return xt, st_
+
+    def _masked_init_local(y0, obs, use_pca, x_test_mean, x_test_var):
         if x_test_mean is None and not use_pca and train_obs is not None:
             x_test_mean = _missing.jointly_observed_nearest_neighbour_init(np.asarray(y_train), train_obs, y0, obs,
                                                                            x_mean.detach().cpu().numpy())
@@ -538,7 +614,7 @@ def dp_gp_lvm(y_train,
             sum_n var(n,d) = predicted_covar[d,0,0] + (N* - 1)/beta_d - 2 tr_term_d."""
         if masked is not None:
             return _marginals_at_masked(cols, xt, st_)
-        idx = torch.as_tensor(np.asarray(cols), device=device)
+        idx = torch.as_tensor(np.asarray(cols) - d_lo, device=device)           # (cols: global, within this rank's [d_lo, d_hi))
         f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
         gu, au, bu = f64(buf['gamma'][idx]), f64(buf['alpha'][:, 0][idx]), f64(buf['beta'][:, 0][idx])
         z, mu, s_train = f64(x_u.detach()), f64(x_mean.detach()), f64(F.softplus(x_var_raw).detach())
@@ -558,9 +634,9 @@ def dp_gp_lvm(y_train,
         """_marginals_at on a model trained with observed=: Psi2_d is the weighted sum over the rows at which column d was measured and
         Psi1_d^T y_d comes from ops.psi1T_y on the zero-filled data (no [K, N, M] array); a column never observed has no posterior:
         mean 0, variance alpha_d + 1/beta_d."""
-        cols = np.asarray(cols)
+        cols = np.asarray(cols) - d_lo                                     # (given global, within this rank's [d_lo, d_hi))
         pos = np.searchsorted(masked.cols_np, cols)
-        seen = (pos < masked.cols_np.size) & (masked.cols_np[np.minimum(pos, masked.cols_np.size - 1)] == cols)
+        seen = np.isin(cols, masked.cols_np)                               # (masked.cols_np may be empty: a share never observed)
         idx = torch.as_tensor(cols, device=device)
         au, bu = buf['alpha'][:, 0][idx].contiguous(), buf['beta'][:, 0][idx].contiguous()
         prior_var = (au + 1.0 / bu)[None, :].expand(xt.shape[0], -1)
@@ -577,6 +653,22 @@ def dp_gp_lvm(y_train,
                                               c[:, None].contiguous(), rhs[:, :, None].contiguous(), gidx, b_)
             mean[:, here], var[:, here] = mn[:, :, 0].transpose(0, 1), vr[:, :, 0].transpose(0, 1)
         return mean, var
+
+    def _assembled_marginals(cols, xt, st_):
+        """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
+        into a zero-filled [2 x N* x len(cols)] buffer, one sum all-reduce completes it; every rank returns the same (mean, var).
+        Without a communicator (_shard_of) the other ranks' columns stay zero."""
+        cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+        pair = torch.zeros((2, xt.shape[0], cols.size), dtype=TORCH_DTYPE, device=device)
+        own = np.flatnonzero((cols >= d_lo) & (cols < d_hi))
+        if own.size:
+            mean, var = _marginals_at(cols[own], xt, st_)
+            at = torch.as_tensor(own, device=device)
+            pair[0].index_copy_(1, at, mean)
+            pair[1].index_copy_(1, at, var)
+        if sharded:
+            dist.all_reduce(pair, op=dist.ReduceOp.SUM, group=process_group)
+        return pair[0], pair[1]
 
     def _reference_form_not_built(name, how):
         raise NotImplementedError("%s: the reference's form of this call is not built for a model trained with observed=: %s"
@@ -643,7 +735,7 @@ def dp_gp_lvm(y_train,
         def per_dimension_terms(self):
             """[D_local x 5] f_hat terms and the info flags of the last evaluation (0 fine, > 0 failed factorisation,
             DPGP_INFO_ILL_CONDITIONED = -2: fp32 Psi2 no longer trustworthy for this output dim).  A model trained with observed=:
-            [D x 5] and [D], zero rows for the columns never observed."""
+            [D_local x 5] and [D_local], zero rows for the columns never observed."""
             if masked is not None:
                 if masked.terms is None:
                     evaluate()
@@ -679,7 +771,8 @@ def dp_gp_lvm(y_train,
         @property
         def prediction_terms(self):
             """[D* x 5] f_hat terms of the test points in the last predict_* call (the observed dims for missing data; with
-            `observed`: [slots x 5], one slot per output dim that has an observed entry, ascending)."""
+            `observed`: [slots x 5], one slot per output dim that has an observed entry, ascending).  On a sharded model it stays
+            local: the slots of this rank's columns ([0 x 5] where none of them has an observed test entry)."""
             return pred_state.get('terms')
 
         @property
@@ -716,8 +809,13 @@ def dp_gp_lvm(y_train,
             shared-inducing masked test bound (models/frozen_bound_d.py) with every measured entry counting, the training-side f_hat
             the model's own masked one, q(X*) starts at the nearest training neighbour over the jointly observed columns.
             Without observed= it is the reference's call, which such a model does not take: NotImplementedError.  AssertionError
-            for reference_compat=True; observed= is taken by such a model only."""
-            if masked is not None:
+            for reference_compat=True; observed= is taken by such a model and by a sharded model only.
+
+            On a model sharded over a process group (trained on complete data or with observed=) the call takes observed= in the
+            same way: each rank evaluates the shared-inducing bound on its columns, ONE packed all-reduce sums f_hat*, KL(q(X*)) is
+            added once on every rank; a start of q(X*) that was not supplied is rank 0's, broadcast.  Without observed=:
+            AssertionError (the reference's form runs on one GPU)."""
+            if masked is not None or (split and observed is not None):
                 if observed is None:
                     _reference_form_not_built('predict_new_latent_variables', 'pass observed=, the mask of the measured entries of '
                                               'y_test [N* x D] (utils.missing.observed_mask(y_test) reads it off the NaNs)')
@@ -730,7 +828,7 @@ def dp_gp_lvm(y_train,
                     test_ll = f_hat_test - ops.kl_qx(xt, st_)
                     return out[1] - out[2] + test_ll, xt, torch.diag_embed(st_), test_ll
             assert observed is None, 'observed= is taken by a model trained with observed='
-            assert not sharded and world == 1, 'prediction paths run on one GPU'
+            assert not split, ONE_GPU
             y_test = np.asarray(y_test, dtype=np.float64)
             num_test_points, test_dims = np.shape(y_test)
             assert test_dims == num_dimensions, \
@@ -753,17 +851,20 @@ def dp_gp_lvm(y_train,
             observed: as predict_missing_data (y_test [N* x D]; True everywhere is allowed here): the gradient of the masked
             bound, fp64, by the weighted test-point operators.  form (with observed only, AssertionError otherwise): 'slots', one
             slot with its own copy of Z, Psi1* and adjoint per output dim, or 'shared', the same bound on one copy of Z with no
-            [D x N* x M] array (models/frozen_bound_d.py, ops.psi_latent_adjoint)."""
+            [D x N* x M] array (models/frozen_bound_d.py, ops.psi_latent_adjoint).
+            On a model sharded over a process group: observed= with form='shared' only (AssertionError otherwise); each rank
+            evaluates its columns, ONE all-reduce of the packed (f_hat*, d mu*, d S*) — 1 + 2 N* Q fp64 values — sums them, the KL
+            gradient is added once on every rank; prediction_terms then holds this rank's columns only."""
             _form_arg(form, observed)
             if observed is not None:
-                bound, _ = _masked_bound(*_masked(y_test, observed), form)
+                bound, _ = _masked_bound(*_masked(y_test, observed, form=form), form)
                 xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
                     _t(x_test_var.detach().cpu().numpy() if torch.is_tensor(x_test_var) else x_test_var)
                 with torch.no_grad():
                     _, dmu, ds = bound.evaluate(xt, st_, grad=True)
                     pred_state['terms'] = bound.terms
                 return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)
-            assert not sharded and world == 1, 'prediction paths run on one GPU'
+            assert not split, ONE_GPU
             y_t = _t(np.asarray(y_test, dtype=np.float64))
             dd = y_t.shape[1]
             xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
@@ -782,10 +883,12 @@ def dp_gp_lvm(y_train,
             """Adam on q(X*) (mean and softplus-parametrised variances) maximising f_hat_test - KL(q(X*)) for test points
             observed in their first Do output dims; returns (x_test_mean, x_test_var) to hand to predict_*.  observed: as
             predict_missing_data; the slots' factors are formed once, no host synchronisation inside the loop.  form: as
-            test_latent_gradients."""
+            test_latent_gradients.  On a model sharded over a process group (observed= with form='shared' only): one packed
+            all-reduce per iteration; a start that is not supplied is rank 0's, broadcast once, and every rank applies the same
+            reduced gradient, so the ranks' q(X*) stay bit-identical."""
             _form_arg(form, observed)
             if observed is not None:
-                y0, obs = _masked(y_test, observed)
+                y0, obs = _masked(y_test, observed, form=form)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound, _ = _masked_bound(y0, obs, form)
                 raw = torch.log(torch.expm1(st_))
@@ -798,6 +901,7 @@ def dp_gp_lvm(y_train,
                         opt.step()
                     pred_state['terms'] = bound.terms
                     return xt, F.softplus(raw)
+            assert not split, ONE_GPU
             y_test = np.asarray(y_test, dtype=np.float64)
             xt, st_ = _init_test_latents(y_test, np.asarray(y_train)[:, :y_test.shape[1]], use_pca, x_test_mean, x_test_var)
             raw = torch.log(torch.expm1(st_))
@@ -814,14 +918,15 @@ def dp_gp_lvm(y_train,
             """(mean, var), each [N* x len(columns)]: the per-entry predictive moments of the output dims `columns` (default: all
             D) at q(X*) = (x_test_mean, x_test_var [N* x Q]) under each column's mixed kernel of this evaluation, observation
             noise 1/beta_d included; one call of ops.qx_psi_point_moments (see _marginals_at for the formulas and for the sign
-            of the trace term against predict_missing_data's array).  fp64, one GPU, torch.no_grad."""
-            assert not sharded and world == 1, 'prediction paths run on one GPU'
+            of the trace term against predict_missing_data's array).  fp64, torch.no_grad.  On a model sharded over a process
+            group (any precision, with or without observed=): `columns` are global, each rank computes those it owns and one sum
+            all-reduce assembles the pair in the caller's column order, the same tensors on every rank."""
             cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
             assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
             val = lambda a: _t(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
             evaluate()
             with torch.no_grad():
-                return _marginals_at(cols, val(x_test_mean), val(x_test_var))
+                return (_assembled_marginals if split else _marginals_at)(cols, val(x_test_mean), val(x_test_var))
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -850,9 +955,17 @@ def dp_gp_lvm(y_train,
             (NaN = missing); f_hat* is always the shared-inducing bound, the training-side f_hat the model's own masked one, and the
             last two entries are the per-entry moments of predictive_marginals on missing_columns, predicted_mean [N* x Du] and
             predicted_var [N* x Du] — per entry whatever marginal_variance says (no [Du x N* x N*] array is built for such a
-            model).  AssertionError for reference_compat=True."""
+            model).  AssertionError for reference_compat=True.
+
+            On a model sharded over a process group: observed= with form='shared' (a mask-trained model always runs that bound);
+            the bound is global — the training-side f_hat and KL of the sharded evaluation, f_hat* summed over the ranks by ONE
+            packed all-reduce, KL(q(X*)) subtracted once — and the last two entries are predictive_marginals' per-entry moments
+            [N* x Du] of the global missing_columns, assembled by one sum all-reduce, whatever marginal_variance says; every rank
+            returns the same tensors.  prediction_terms stays local: this rank's columns only."""
             _form_arg(form, observed if masked is None else True)
-            if masked is not None:
+            if split and masked is None:
+                assert observed is not None and form == 'shared', ONE_GPU
+            if masked is not None or split:
                 if observed is None and np.ndim(y_test) == 2 and np.shape(y_test)[1] != num_dimensions:
                     _reference_form_not_built('predict_missing_data', 'pass y_test [N* x D] with NaN at the missing entries, or with observed=')
                 y0, obs = _masked(y_test, _missing.observed_mask(y_test) if observed is None else observed, predict=True,
@@ -863,7 +976,8 @@ def dp_gp_lvm(y_train,
                     f_hat_test, _, _ = bound.evaluate(xt, st_)
                     pred_state['terms'] = bound.terms
                     lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
-                    predicted_mean, predicted_var = _marginals_at_masked(pred_state['missing_columns'], xt, st_)
+                    predicted_mean, predicted_var = (_assembled_marginals if split else _marginals_at_masked)(
+                        pred_state['missing_columns'], xt, st_)
                 return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_var
             if observed is not None:
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
@@ -877,7 +991,7 @@ def dp_gp_lvm(y_train,
                     if marginal_variance:
                         predicted_covar = _marginals_at(pred_state['missing_columns'], xt, st_)[1]
                 return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_covar
-            assert not sharded and world == 1, 'prediction paths run on one GPU'
+            assert not split, ONE_GPU
             y_test = np.asarray(y_test, dtype=np.float64)
             num_test_points, num_observed_dims = np.shape(y_test)
             assert num_observed_dims < num_dimensions, \
@@ -904,13 +1018,15 @@ def dp_gp_lvm(y_train,
             beta_d Psi1_d[n,:] (K_d + beta_d Psi2_d)^-1 Psi1_d^T y_d (Psi2_d and y_d over the rows at which d was observed); observed
             entries as given, a never-observed column 0.  fp64 device tensor.  return_variance=True: (filled, var), var [N x D] the
             per-entry variance of predictive_marginals at the training q(X) at the unobserved entries and 0 at the observed ones;
-            filled is the same tensor either way."""
+            filled is the same tensor either way.  On a model sharded over a process group each rank computes its columns and one
+            sum all-reduce assembles them: filled (and var) are [N x D] and the same on every rank."""
             assert masked is not None, 'impute_training_data needs a model trained with observed='
             evaluate()
             with torch.no_grad():
-                mean, var = _marginals_at_masked(np.arange(num_dimensions), x_mean.detach(), F.softplus(x_var_raw).detach())
+                mean, var = (_assembled_marginals if split else _marginals_at_masked)(
+                    np.arange(num_dimensions), x_mean.detach(), F.softplus(x_var_raw).detach())
                 obs = torch.as_tensor(train_obs, device=device)
-                filled = torch.where(obs, y_local, mean)
+                filled = torch.where(obs, _t(y_train) if split else y_local, mean)
                 return (filled, torch.where(obs, torch.zeros_like(var), var)) if return_variance else filled
 
     return DP_GP_LVM()

@@ -67,3 +67,34 @@ class _TestBoundD:
         d_mu, d_s = ops.psi_latent_adjoint(self.z, mu, s, self.gamma, self.alpha, self.y, g_v.contiguous(),
                                            adj.g2_difference(self.kinv).contiguous(), weights=self.weights)
         return f, d_mu, d_s
+
+
+class _ShardedTestBoundD:
+    """The test bound of a D-sharded model: `local` is the _TestBoundD of this rank's columns that have an observed test entry, or
+    None where there is none (the rank then contributes zeros and still joins).  The bound is a sum over columns of terms on the
+    replicated (Z, q(X*)), so one evaluation is the local one followed by ONE sum all-reduce of a packed fp64 buffer: f_hat* and,
+    with grad, d_mu and d_s (1 + 2 N* Q values).  process_group None: the local partial values, no exchange.  KL(q(X*)) is not in
+    here: the caller adds it once, after the exchange, identically on every rank."""
+
+    def __init__(self, local, n_t, q, device, process_group=None):
+        self.local, self.n_t, self.q, self.device, self.group = local, n_t, q, device, process_group
+        self.terms = torch.zeros((0, 5), dtype=TORCH_DTYPE, device=device)
+        self.info = torch.zeros(0, dtype=torch.int32, device=device)
+
+    def evaluate(self, mu, s, grad=False):
+        """(f_hat*, None, None), or with grad (f_hat*, d_mu, d_s): the values summed over the ranks."""
+        nq = self.n_t * self.q
+        flat = torch.zeros(1 + (2 * nq if grad else 0), dtype=TORCH_DTYPE, device=self.device)
+        if self.local is not None:
+            res = self.local.evaluate(mu, s, grad=grad)
+            flat[0] = res[0]
+            if grad:
+                flat[1:1 + nq] = res[1].reshape(-1)
+                flat[1 + nq:] = res[2].reshape(-1)
+            self.terms, self.info = self.local.terms, self.local.info
+        if self.group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+        if not grad:
+            return flat[0], None, None
+        return flat[0], flat[1:1 + nq].reshape(self.n_t, self.q), flat[1 + nq:].reshape(self.n_t, self.q)

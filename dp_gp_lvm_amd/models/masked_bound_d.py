@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from ..utils import missing as _missing
 from ..utils.constants import GP_DEFAULT_JITTER
 from ..utils.types import TORCH_DTYPE
 from . import collapsed
@@ -37,8 +38,9 @@ class _MaskedBoundD:
     def __init__(self, y0, observed, device):
         f64 = TORCH_DTYPE
         observed = np.asarray(observed)
-        cols = np.flatnonzero(observed.any(axis=0))
-        assert cols.size, 'observed must hold at least one True entry'
+        # (the columns of one rank of a D-sharded model may hold no observed entry: an empty batch, on which no operator is launched;
+        #  "at least one True" is the model's check on the global mask)
+        cols = _missing.observed_columns(observed)
         self.n, self.d = observed.shape
         self.device = device
         self.cols_np = cols
@@ -80,6 +82,11 @@ class _MaskedBoundD:
         """f_hat as a 1-element tensor; with grad also (d_mu [N,Q], d_s [N,Q], d_z [M,Q], d_gamma [Dc,Q], d_alpha_beta [Dc,2]).
         self.terms: [Dc x 5]; self.info [Dc]: 0 where K_d and A_d factorised."""
         n_d = self.n_d
+        if self.cols_np.size == 0:                          # no column of this share was observed: f_hat = 0, zero derivatives
+            zeros = lambda *shape: torch.zeros(shape, dtype=TORCH_DTYPE, device=self.device)
+            self.terms = zeros(0, 5)
+            return (zeros(1), (zeros(*mu.shape), zeros(*s.shape), zeros(*z.shape), zeros(0, z.shape[1]), zeros(0, 2))) if grad \
+                else zeros(1)
         c = self.chain(z, mu, s, gamma, alpha, beta)
         v, ch = c['v'], c['chain'].project(c['v'][:, :, None])                                    # u [Dc, M, 1]
         uu = torch.sum(ch.u * ch.u, dim=(1, 2))

@@ -54,6 +54,14 @@ def group_columns_by_pattern(observed):
     return [(np.asarray(cols, dtype=np.int64), w) for cols, w in groups]
 
 
+def observed_columns(observed, lo=0, hi=None):
+    """The columns among [lo, hi) (default: all) with at least one observed entry, ascending, counted from `lo`: the operator batch
+    of a masked over-D bound on that share of the columns (a D-sharded model: lo, hi = the rank's bounds).  May be empty; the
+    batches of the shares of a partition of [0, D), each shifted by its lo, make up the batch of the whole mask."""
+    observed = np.asarray(observed)
+    return np.flatnonzero(observed[:, lo:hi].any(axis=0))
+
+
 def missing_columns(observed):
     """Columns with at least one unobserved entry, ascending."""
     return np.flatnonzero(~np.asarray(observed).all(axis=0))
