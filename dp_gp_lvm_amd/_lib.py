@@ -36,6 +36,7 @@ SIGNATURES = {
     'dpgp_elbo_fhat_t': (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _d, _i, _vp, _vp,
                               _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dpgp_elbo_grad_chain': (_i, [_i, _i, _i, _i, _vp, _vp, _d, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dpgp_elbo_grad_chain_ex': (_i, [_i, _i, _i, _i, _vp, _vp, _d, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dpgp_elbo_grad_psi_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'dpgp_elbo_grad_psi_workspace_bytes_ex': (_sz, [_i, _i, _i, _i, _i]),
     'dpgp_elbo_fhat_step': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

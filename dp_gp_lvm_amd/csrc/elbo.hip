@@ -191,9 +191,11 @@ static int elbo_run(int D, int N, int M, int Q, const double *y, int ldy, const 
 
 // Backward pass, stage A (grad.hip): adjoints of the per-output dense algebra from the workspace of a finished forward
 // evaluation (same D, N, M, Q, prec; prec must be mixed or f64: the chain is fp64).
-extern "C" int dpgp_elbo_grad_chain(int D, int N, int M, int Q, const double *alpha, const double *beta, double jitter,
-                                    int prec, void *ws, size_t ws_bytes, double *g_psi2, double *w_kuu, double *g_v,
-                                    double *d_alpha_beta, int *info, void *stream) {
+// psi2_slabs: 0 = the forward's own count of Psi2 slabs, 1 after dpgp_elbo_fhat_step (which leaves ONE slab whatever the layout says: the
+// slabs behind it hold whatever an earlier evaluation left there)
+extern "C" int dpgp_elbo_grad_chain_ex(int D, int N, int M, int Q, const double *alpha, const double *beta, double jitter,
+                                       int prec, void *ws, size_t ws_bytes, int psi2_slabs, double *g_psi2, double *w_kuu, double *g_v,
+                                       double *d_alpha_beta, int *info, void *stream) {
     if (D <= 0) return -1;
     if (N <= 0) return -2;
     if (M <= 0) return -3;
@@ -210,15 +212,22 @@ extern "C" int dpgp_elbo_grad_chain(int D, int N, int M, int Q, const double *al
     if (!g_v) return -13;
     if (!d_alpha_beta) return -14;
     if (!info) return -15;
+    if (psi2_slabs < 0 || psi2_slabs > L.ns2) return -16;
     unsigned char *w = (unsigned char *)ws;
     const double *yy = reinterpret_cast<const double *>(w + L.off_yy), *vpart = reinterpret_cast<const double *>(w + L.off_v);
     double *la = reinterpret_cast<double *>(w + L.off_la);
     // the f16 psi2 kernel leaves ns2 slabs; (slab count as in elbo_run)
+    const int ns2 = psi2_slabs ? psi2_slabs : L.ns2;
     if (prec == DPGP_PREC_MIXED)
-        return launch_chain_grad<float>(D, N, M, reinterpret_cast<const float *>(w + L.off_p2), L.ns2, vpart, L.ns1, alpha,
+        return launch_chain_grad<float>(D, N, M, reinterpret_cast<const float *>(w + L.off_p2), ns2, vpart, L.ns1, alpha,
                                         beta, yy, jitter, la, g_psi2, w_kuu, g_v, d_alpha_beta, info, (hipStream_t)stream);
-    return launch_chain_grad<double>(D, N, M, reinterpret_cast<const double *>(w + L.off_p2), L.ns2, vpart, L.ns1, alpha,
+    return launch_chain_grad<double>(D, N, M, reinterpret_cast<const double *>(w + L.off_p2), ns2, vpart, L.ns1, alpha,
                                      beta, yy, jitter, la, g_psi2, w_kuu, g_v, d_alpha_beta, info, (hipStream_t)stream);
+}
+extern "C" int dpgp_elbo_grad_chain(int D, int N, int M, int Q, const double *alpha, const double *beta, double jitter,
+                                    int prec, void *ws, size_t ws_bytes, double *g_psi2, double *w_kuu, double *g_v,
+                                    double *d_alpha_beta, int *info, void *stream) {
+    return dpgp_elbo_grad_chain_ex(D, N, M, Q, alpha, beta, jitter, prec, ws, ws_bytes, 0, g_psi2, w_kuu, g_v, d_alpha_beta, info, stream);
 }
 
 // Stage A for M > 128 (M a multiple of 128; other M: the host composes it from the batched operators) from the workspace of a finished

@@ -857,7 +857,7 @@ def elbo_grad_psi_step(y, z, mu, s, gamma, alpha, g_psi2, w_kuu, g_v, workspace,
 def elbo_grad_chain(alpha, beta, workspace, jitter=1e-8, z=None, gamma=None, psi2_slabs=None):
     """Backward pass, stage A: adjoints of the per-output dense algebra from the workspace of a finished ``elbo_fhat`` call
     (dp_gp_lvm.py:108-145 differentiated; prec mixed / f64).  M <= 128: one HIP kernel per output dim with B in LDS
-    (dpgp_elbo_grad_chain).  M > 128 (needs z and gamma, mixed only downstream): composed here from the library's batched
+    (dpgp_elbo_grad_chain_ex).  M > 128 (needs z and gamma, mixed only downstream): composed here from the library's batched
     Cholesky / triangular solves and plain fp64 GEMMs (``_elbo_grad_chain_large``).
     psi2_slabs: the number of Psi2 partial slabs the forward evaluation left (1 after ``elbo_fhat_step``; default: the layout's).
     Returns (g_psi2 [D,Mp,Mp], w_kuu [D,Mp,Mp], g_v [D,Mp], d_alpha_beta [D,2], info [D]); see include/dpgp.h."""
@@ -875,10 +875,10 @@ def elbo_grad_chain(alpha, beta, workspace, jitter=1e-8, z=None, gamma=None, psi
     gv = torch.empty((d, mp), dtype=f64, device=dev)
     dab = torch.empty((d, 2), dtype=f64, device=dev)
     info = torch.empty(d, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().dpgp_elbo_grad_chain(d, n, m, q, alpha.data_ptr(), beta.data_ptr(), float(jitter),
-                                               _lib.PREC[workspace.prec], workspace.ws.data_ptr(), workspace.nbytes,
-                                               gp.data_ptr(), wk.data_ptr(), gv.data_ptr(), dab.data_ptr(), info.data_ptr(),
-                                               _stream()), 'dpgp_elbo_grad_chain')
+    _lib.check(_lib.lib().dpgp_elbo_grad_chain_ex(d, n, m, q, alpha.data_ptr(), beta.data_ptr(), float(jitter),
+                                                  _lib.PREC[workspace.prec], workspace.ws.data_ptr(), workspace.nbytes,
+                                                  0 if psi2_slabs is None else int(psi2_slabs), gp.data_ptr(), wk.data_ptr(),
+                                                  gv.data_ptr(), dab.data_ptr(), info.data_ptr(), _stream()), 'dpgp_elbo_grad_chain_ex')
     return gp, wk, gv, dab, info
 
 

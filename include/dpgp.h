@@ -402,6 +402,11 @@ int dpgp_elbo_fhat_ex(int D, int N, int M, int Q, const double *y, int ldy, cons
 int dpgp_elbo_grad_chain(int D, int N, int M, int Q, const double *alpha, const double *beta, double jitter, int prec,
                          void *ws, size_t ws_bytes, double *g_psi2, double *w_kuu, double *g_v, double *d_alpha_beta,
                          int *info, void *stream);
+/* As dpgp_elbo_grad_chain, reading psi2_slabs Psi2 slabs of the workspace: 0 = the forward's own count (dpgp_elbo_grad_chain), 1 after
+ * dpgp_elbo_fhat_step, which leaves one slab whatever dpgp_elbo_workspace_layout reports. */
+int dpgp_elbo_grad_chain_ex(int D, int N, int M, int Q, const double *alpha, const double *beta, double jitter, int prec,
+                            void *ws, size_t ws_bytes, int psi2_slabs, double *g_psi2, double *w_kuu, double *g_v,
+                            double *d_alpha_beta, int *info, void *stream);
 /* Stage A for M > 128, M a multiple of 128 (-3 otherwise: the host side composes it from dpgp_potrf_batched / dpgp_trsm_batched /
  * dpgp_gemm_strided_f64 then): the same adjoints from the forward evaluation's workspace, on [D][M][M] fp64 matrices in memory — the
  * persistent-workgroup Cholesky and solve (L^-1 with every block row stored), five strided MFMA products and three streaming kernels
