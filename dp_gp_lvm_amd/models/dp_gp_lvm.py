@@ -31,7 +31,7 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
-from . import collapsed, marginals as _marginals
+from . import collapsed, marginals as _marginals, predictor as _predictor
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .frozen_bound import _TestBound
@@ -654,6 +654,35 @@ def dp_gp_lvm(y_train,
             mean[:, here], var[:, here] = mn[:, :, 0].transpose(0, 1), vr[:, :, 0].transpose(0, 1)
         return mean, var
 
+    def _frozen_predictor(cols):
+        """The training side of _marginals_at / _marginals_at_masked of the output dims `cols`, formed once, as a
+        predictor.FrozenPredictor (its forward is their operator call on the same arrays)."""
+        cols = np.asarray(cols)
+        idx = torch.as_tensor(cols, device=device)
+        f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
+        z, mu, s_train = f64(x_u.detach()), f64(x_mean.detach()), f64(F.softplus(x_var_raw).detach())
+        if masked is None:
+            gu, au, bu = f64(buf['gamma'][idx]), f64(buf['alpha'][:, 0][idx]), f64(buf['beta'][:, 0][idx])
+            psi_1 = ops.psi1(z, mu, s_train, gu, au)
+            psi_2 = ops.psi2(z, mu, s_train, gu, au)
+            k_uu = ops.ard_rbf_gram(z, None, gu, au, bu, include_noise=False, include_jitter=True, jitter=GP_DEFAULT_JITTER)
+            li, _ = collapsed.factors(k_uu)
+            r0 = collapsed.Chain(li, psi_2, bu).r0
+            y_u = _t(np.asarray(y_train)[:, cols]).to(TORCH_DTYPE).transpose(0, 1).contiguous()[:, :, None]
+            r, c = collapsed.posterior(r0, collapsed.k_inverse(li), bu, ops.matmul(psi_1.transpose(1, 2), y_u))
+            here = torch.arange(cols.size, device=device)
+            return _predictor.of_columns(z, gu, au, bu, c.contiguous(), r[:, :, 0].contiguous(), here, au + 1.0 / bu, False, device)
+        pos, seen = np.searchsorted(masked.cols_np, cols), np.isin(cols, masked.cols_np)
+        au, bu = buf['alpha'][:, 0][idx].contiguous(), buf['beta'][:, 0][idx].contiguous()
+        here = torch.as_tensor(np.flatnonzero(seen), dtype=torch.long, device=device)
+        gu, a_, b_ = buf['gamma'][idx[here]].contiguous(), au[here].contiguous(), bu[here].contiguous()
+        c = rhs = None
+        if seen.any():
+            sel = torch.as_tensor(pos[seen], dtype=torch.long, device=device)
+            c, rhs = masked.posterior(x_u.detach(), x_mean.detach(), F.softplus(x_var_raw).detach(), gu, a_, b_, sel=sel)
+            c, rhs = f64(c), f64(rhs)
+        return _predictor.of_columns(z, f64(gu), f64(a_), f64(b_), c, rhs, here, f64(au + 1.0 / bu), True, device)
+
     def _assembled_marginals(cols, xt, st_):
         """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
         into a zero-filled [2 x N* x len(cols)] buffer, one sum all-reduce completes it; every rank returns the same (mean, var).
@@ -927,6 +956,19 @@ def dp_gp_lvm(y_train,
             evaluate()
             with torch.no_grad():
                 return (_assembled_marginals if split else _marginals_at)(cols, val(x_test_mean), val(x_test_var))
+
+        @staticmethod
+        def frozen_predictor(columns=None):
+            """A models/predictor.FrozenPredictor of the output dims `columns` (default: all D): p(x_mean, x_var) gives the bits of
+            predictive_marginals, differentiably in q(X*); p.vjp is its vector-Jacobian product (ops.psi_latent_adjoint: the
+            columns' kernels share Z and q(X*)).  The training side is built once, here, at the model's current parameters: stale
+            after further training.  Not built for a model sharded over a process group: AssertionError."""
+            assert not split, 'frozen_predictor is not built for a model sharded over a process group'
+            cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
+            assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+            evaluate()
+            with torch.no_grad():
+                return _frozen_predictor(cols)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1682,6 +1724,15 @@ def dp_gp_lvm_t(y_train,
             cols = _columns_arg(columns)
             with torch.no_grad():
                 return _moments().at(_values(x_test_mean), _values(x_test_var), cols)
+
+        @staticmethod
+        def frozen_predictor(columns=None):
+            """A models/predictor.FrozenPredictor of the output dims `columns` (default: all D): p(x_mean, x_var) gives the bits of
+            predictive_marginals, differentiably in q(X*); p.vjp is its vector-Jacobian product (the mixture's on the host, then
+            ops.qx_psi_point_moments_adjoint on the T atoms).  The training side is built once, here, at the model's current
+            parameters: stale after further training.  Not built for a sharded model: AssertionError."""
+            cols = _columns_arg(columns)
+            return _predictor.of_mixture(_moments(), cols, device)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

@@ -32,7 +32,7 @@ from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .frozen_bound import _TestBound, _as_device, kernel_slots
 from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
-from . import collapsed, marginals as _marginals
+from . import collapsed, marginals as _marginals, predictor as _predictor
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -539,6 +539,15 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             return _marginals_at(_as_device(x_test_mean, dev_), _as_device(x_test_var, dev_), columns)
 
         @staticmethod
+        def frozen_predictor(columns=None):
+            """A models/predictor.FrozenPredictor of the output dims `columns` (default: all D): p(x_mean, x_var) gives the bits of
+            predictive_marginals, differentiably in q(X*); p.vjp is its vector-Jacobian product (ops.qx_psi_point_moments_adjoint).
+            The training side is built once, here, at the model's current parameters: stale after further training."""
+            cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+            with torch.no_grad():
+                return _predictor.of_marginals(_train_marginals(), cols, dev_)
+
+        @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
                                  observed=None, marginal_variance=False):
             """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
@@ -998,6 +1007,18 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             vs = list(range(num_views)) if views is None else [int(v) for v in views]
             assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
             return _marginals_at(_as_device(x_test_mean, dev_), _as_device(x_test_var, dev_), vs)
+
+        @staticmethod
+        def frozen_predictor(views=None):
+            """One models/predictor.FrozenPredictor per view of `views` (default: all V, in order), each over all D_v columns of its
+            view: p(x_mean, x_var) gives the bits of that view's predictive_marginals, differentiably in q(X*); p.vjp is its
+            vector-Jacobian product.  The training side of all views is built once, here, at the model's current parameters: stale
+            after further training."""
+            vs = list(range(num_views)) if views is None else [int(v) for v in views]
+            assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
+            with torch.no_grad():
+                train = _train_marginals()
+                return [_predictor.of_marginals(train[v], _marginals.columns_arg(None, num_dimensions[v], dev_), dev_) for v in vs]
 
         @staticmethod
         def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,

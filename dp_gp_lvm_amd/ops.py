@@ -383,6 +383,72 @@ def qx_psi_pointwise(z, mu, s, gamma, alpha, c, r, zfac=None):
     return tr, quad
 
 
+def _qx_point_adjoint(a, name, shape, mu):
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+        raise TypeError('%s must be a float64 torch.Tensor' % name)
+    if a.device != mu.device:
+        raise RuntimeError('%s must live on the device of the inputs' % name)
+    if tuple(a.shape) != shape:
+        raise ValueError('%s must be %s, got %s' % (name, list(shape), tuple(a.shape)))
+    return a.contiguous()
+
+
+def qx_psi_pointwise_adjoint(z, mu, s, gamma, alpha, c, r, h, gq, gt, zfac=None):
+    """(d_mu, d_s) [N,Q] of  L = sum_knj h (psi1_kn . r_kj) + sum_knj gq (r_kj^T psi2_kn r_kj) + sum_kng gt <c_kg, psi2_kn>
+    (dpgp_qx_psi_pointwise_adjoint_f64): the latent adjoint of qx_psi_pointwise's two outputs (adjoints gt [K,N,G] of tr, gq [K,N,J]
+    of quad) and of psi1 . r (adjoint h [K,N,J]), summed over the kernels; inputs as qx_psi_pointwise.  Derivatives with respect to
+    the variances s.  The adjoint of psi2_kn is formed before it meets the exponentials: one exponential per (k, n, pair) whatever
+    G + J is; nothing of size N M M is formed.  Fixed summation order, the same bits on every run; a zero adjoint gives exactly 0."""
+    z, mu, s, gamma, alpha, zfac, k, n, m, q = _qx_args(z, mu, s, gamma, alpha, zfac)
+    c, r = _qx_point_args(c, r, k, m, mu)
+    g, j = c.shape[1], r.shape[2]
+    h = _qx_point_adjoint(h, 'h', (k, n, j), mu)
+    gq = _qx_point_adjoint(gq, 'gq', (k, n, j), mu)
+    gt = _qx_point_adjoint(gt, 'gt', (k, n, g), mu)
+    d_mu = torch.empty((n, q), dtype=torch.float64, device=mu.device)
+    d_s = torch.empty_like(d_mu)
+    l = _lib.lib()
+    wsb = l.dpgp_qx_psi_pointwise_adjoint_workspace_bytes(k, g, j, n, m, q)
+    ws = _ws(wsb, mu.device)
+    _lib.check(l.dpgp_qx_psi_pointwise_adjoint_f64(k, g, j, n, m, q, z.data_ptr(), mu.data_ptr(), s.data_ptr(), gamma.data_ptr(),
+                                                   alpha.data_ptr(), None if zfac is None else zfac.data_ptr(), c.data_ptr(),
+                                                   r.data_ptr(), h.data_ptr(), gq.data_ptr(), gt.data_ptr(), d_mu.data_ptr(),
+                                                   d_s.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_qx_psi_pointwise_adjoint_f64')
+    return d_mu, d_s
+
+
+def point_moments_adjoints(gidx, g, mean, g_mean, g_var):
+    """The adjoints (h, gq, gt) of (psi1 . r, quad, tr) that the combination step of qx_psi_point_moments passes back:
+    mean = psi1 . r,  var = const - tr[gidx] + quad - mean^2.  gidx [K,J] int, g the number of trace columns; a gidx outside
+    [0, g) has no trace term and contributes nothing.  Plain tensor algebra on the tensors' device; the gather's transpose is a
+    product with the one-hot matrix of gidx, not index_add, whose atomic adds on the GPU would not give the same bits twice."""
+    h = g_mean - 2.0 * mean * g_var
+    onehot = (gidx.to(torch.int64)[:, :, None] == torch.arange(g, device=gidx.device)[None, None, :]).to(g_var.dtype)
+    gt = -torch.bmm(g_var, onehot)
+    return h, g_var, gt
+
+
+def qx_psi_point_moments_adjoint(z, mu, s, gamma, alpha, c, r, gidx, beta, mean, g_mean, g_var, zfac=None):
+    """The vector-Jacobian product of qx_psi_point_moments with respect to q(X) = (mu, s): (d_mu, d_s) [N,Q] of
+    sum g_mean . mean + sum g_var . var, with mean [K,N,J] the operator's first output at the same inputs and g_mean, g_var
+    [K,N,J] fp64.  A host composition on qx_psi_pointwise_adjoint: h = g_mean - 2 mean g_var, gq = g_var, gt[k,n,g] = -sum of
+    g_var[k,n,j] over the columns with gidx[k,j] = g.  beta enters var as a constant only and is accepted for symmetry."""
+    if not isinstance(gidx, torch.Tensor) or gidx.dtype != torch.int32:
+        raise TypeError('gidx must be an int32 torch.Tensor')
+    if not isinstance(c, torch.Tensor) or c.dim() != 4:
+        raise ValueError('c must be [K x G x M x M]')
+    for name, a in (('mean', mean), ('g_mean', g_mean), ('g_var', g_var)):
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % name)
+        if a.shape != g_var.shape or a.dim() != 3:
+            raise ValueError('mean, g_mean and g_var must be [K x N x J]')
+    if tuple(gidx.shape) != (g_var.shape[0], g_var.shape[2]):
+        raise ValueError('gidx must be [K x J], got %s' % (tuple(gidx.shape),))
+    h, gq, gt = point_moments_adjoints(gidx, c.shape[1], mean, g_mean, g_var)
+    return qx_psi_pointwise_adjoint(z, mu, s, gamma, alpha, c, r, h, gq, gt, zfac=zfac)
+
+
 def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     """(d_mu, d_s) [N*,Q] of  L = sum_b <g_psi2_b, sum_n weights[b,n] psi2_bn> + sum_b g_v_b . (Psi1_b^T y_b)  for B kernels
     (gamma [B,Q], alpha [B]) that share the inducing inputs z [M,Q] and q(X*) = (mu, s) [N*,Q] (dpgp_psi_latent_adjoint_f64, fp64):

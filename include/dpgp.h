@@ -250,6 +250,28 @@ int dpgp_qx_psi_point_moments_f64(int K, int G, int J, int N, int M, int Q, cons
                                   const int *gidx, const double *beta, double *mean, double *var, void *ws, size_t ws_bytes,
                                   void *stream);
 
+/* ---- Latent adjoint of the per-point contractions (csrc/qx_psi_point_adjoint.hip).  Inputs as dpgp_qx_psi_pointwise_f64, plus the
+ *      adjoints h[K][N][J], gq[K][N][J], gt[K][N][G].  With psi1_kn[m], psi2_kn[m,m'] test point n's own statistics of kernel k:
+ *        L = sum_knj h (psi1_kn . r_kj) + sum_knj gq (r_kj^T psi2_kn r_kj) + sum_kng gt <c_kg, psi2_kn>
+ *        d_mu[N][Q] = dL/dmu,   d_s[N][Q] = dL/ds        (s: variances; summed over the kernels; no z, gamma or alpha outputs)
+ *      Per kernel the adjoint of psi2_kn is formed first, T[N x pairs] = gq [N x J] (r r')[J x pairs] + gt [N x G] c~[G x pairs]
+ *      (a pair m <= m' visited once, c symmetrised), multiplied element-wise with the point's exponentials and contracted with
+ *      the 1 + 2Q moment columns (1, zbar_q, zbar_q^2): both products on the fp64 matrix pipe, one exponential per (k, n, pair)
+ *      and per chunk of up to 64 of the G + J columns (32 for Q > 32).  The Psi1 term is the
+ *      same over single inducing points.  Nothing of size N M M, K N M, pairs x J or pairs x G is written to memory.  The
+ *      workspace holds partial (d_mu, d_s) of slabs of kernels, pair tiles and column chunks only; a second launch adds them in
+ *      slab order: no atomics, the same bits on every run.  A zero adjoint contributes exactly 0.0.
+ *      1 <= K, G, J, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, G -2, J -3, N -4, M -5, Q -6, z -7, mu -8, s -9,
+ *      gamma -10, alpha -11, (zfac: nullable, no code), c -13, r -14, h -15, gq -16, gt -17, d_mu -18, d_s -19, ws -20,
+ *      ws_bytes too small -21.
+ *   ws: dpgp_qx_psi_pointwise_adjoint_workspace_bytes(K,G,J,N,M,Q) (a host function; 0 for a shape out of range). */
+size_t dpgp_qx_psi_pointwise_adjoint_workspace_bytes(int K, int G, int J, int N, int M, int Q);
+int dpgp_qx_psi_pointwise_adjoint_f64(int K, int G, int J, int N, int M, int Q, const double *z, const double *mu, const double *s,
+                                      const double *gamma, const double *alpha, const double *zfac, const double *c,
+                                      const double *r, const double *h, const double *gq, const double *gt, double *d_mu,
+                                      double *d_s, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Latent adjoint of B kernels that share inducing inputs AND q(X*) (csrc/psi_latent_adjoint.hip): the frozen over-D model at
  *      test time.  z[M][Q], q(X*) = (mu[N][Q], s[N][Q]: variances), gamma[B][Q], alpha[B]; y[N][ldy]: zero-filled data, column b
  *      for kernel b; w[B][N]: weights of the test points (NULL = all ones; any finite reals); stage-A adjoints g_v[B][M] and
