@@ -53,8 +53,26 @@ template <int KS> struct PairsCfg { static constexpr int G = PP_G(KS); };
 #define PP_DEEP_PREFETCH 1         // groups of two resident tiles fetch their row operands two row tiles ahead
 #endif
 #ifndef PP_SCALAR_ADD
-#define PP_SCALAR_ADD 1            // 1: the 16 accumulations per tile as v_add_f32 (inline asm keeps the compiler from packing
-#endif                             //    them into v_pk_add_f32, which costs more issue time beside MFMAs: MI355X guide)
+#define PP_SCALAR_ADD 1            // 1: the 16 accumulations per tile as single v_add_f32 (v_pk_add_f32 costs more issue time
+#endif                             //    beside MFMAs: MI355X guide)
+
+// acc += exp2(x), one term of a column sum.  PP_SCALAR_ADD: the sum is pinned in its register after every addition, which
+// keeps the compiler from packing two of them into a v_pk_add_f32 and from re-associating them.  The addition itself is the
+// compiler's: an earlier version wrote it as an asm statement, for which the compiler pads no hazard, and wherever its
+// scheduler placed that v_add_f32 directly behind the v_exp_f32 whose result it reads, the transcendental's result was not
+// there yet (wrong sums on the GPU).
+__device__ __forceinline__ void pairs_accumulate(float &acc, float x) {
+#ifdef PP_DIAG_NO_EXP                  // (timing experiments only: wrong results)
+    const float e = x;
+#else
+    const float e = __builtin_amdgcn_exp2f(x);
+#endif
+#if PP_SCALAR_ADD
+    acc = dpgp_pin(acc + e);
+#else
+    acc += e;
+#endif
+}
 
 // the column operands of GG pair tiles tb, tb + 4, ...: operand order (psi2_consts.h), 64 lanes x 16 bytes contiguous per
 // (tile, K-step)
@@ -71,9 +89,10 @@ __device__ __forceinline__ void pairs_load(pp_h8 (&bop)[GG][KS], int tb, const _
 // GG pair tiles tb, tb + 4, ... of one wave against the ntile row tiles of the A image in LDS.  The GG column operands stay in
 // registers; the exponent tiles alternate between two result registers sets (c0, c1): the MFMA chain of the next tile is
 // issued before the exponentials of the current one are evaluated.  GG is even or 1.
-// bop: the operands of this group (pairs_load); tb_next >= 0: the operands of the group at tb_next are fetched into bop as soon
-// as the last MFMA of this group has been issued, i.e. beneath this group's epilogue.
-template <int KS, int GG, int NW>
+// bop: the operands of this group (pairs_load); REFILL: the operands of the group at tb_next are fetched into bop tile by tile
+// through the last row tile, each as soon as its tile's last MFMA chain has been issued (a template parameter, not a test of
+// tb_next: behind a branch the compiler cannot count the loads in flight, and the epilogue would wait for all of them).
+template <int KS, int GG, int NW, bool REFILL>
 __device__ __forceinline__ void pairs_group(int tb, pp_h8 (&bop)[GG][KS], int tb_next, const _Float16 *__restrict__ aimg,
                                             const _Float16 *__restrict__ img,
                                             const unsigned *__restrict__ pmap, const float *__restrict__ scale, int ntile,
@@ -134,20 +153,31 @@ __device__ __forceinline__ void pairs_group(int tb, pp_h8 (&bop)[GG][KS], int tb
             const int kend = (ks + PP_MFMA_PER_STEP < KS) ? ks + PP_MFMA_PER_STEP : KS;
             const int v0 = (16 * ks) / KS, v1 = (16 * kend) / KS;
 #pragma unroll
-            for (int v = v0; v < v1; ++v) {
-#ifdef PP_DIAG_NO_EXP              // (timing experiments only: wrong results)
-                const float e = cu[v];
-#else
-                const float e = __builtin_amdgcn_exp2f(cu[v]);
-#endif
-#if PP_SCALAR_ADD
-                asm("v_add_f32 %0, %0, %1" : "+v"(ac[v & 3]) : "v"(e));
-#else
-                ac[v & 3] += e;
-#endif
-            }
+            for (int v = v0; v < v1; ++v) pairs_accumulate(ac[v & 3], cu[v]);
             __builtin_amdgcn_sched_barrier(0);
         }
+    };
+    // The last stage of a group: the exponentials + accumulations of the CURRENT tile alone (a chain issued here would be dead
+    // code).
+    auto drain = [&](float (&ac)[4], const pp_f16v &cu) __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) pairs_accumulate(ac[v & 3], cu[v]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // The column operands of tile g of the NEXT group, fetched in the last row tile as soon as the last chain of this group's
+    // tile g has been issued (its registers are free from there on): the next group's first chain finds them present.
+    auto refill = [&](int g) __attribute__((always_inline)) {
+        if constexpr (!REFILL) return;
+        // (wave-uniform tile address + one lane offset for all tiles: no address register pair per tile)
+        const pp_h8 *src = reinterpret_cast<const pp_h8 *>(img) + (size_t)(tb_next + NW * g) * KS * 64;
+        const unsigned lo = 32u * half + l5;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) bop[g][ks] = src[ks * 64 + lo];
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto copy_a = [&](pp_h8 (&d)[KS], const pp_h8 (&a)[KS]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) d[ks] = a[ks];
     };
     pp_f16v c0, c1;
     if constexpr (GG == 2 && PP_DEEP_PREFETCH) {
@@ -158,20 +188,25 @@ __device__ __forceinline__ void pairs_group(int tb, pp_h8 (&bop)[GG][KS], int tb
         load_a(a0, 0);
         load_a(a1, min(1, ntile - 1));
         mma(c0, a0, bop[0]);
+        // (all row tiles but the last, which follows the loop with its operands in a0)
 #pragma unroll 1
-        for (int nt = 0; nt < ntile; nt += 3) {
+        for (int nt = 0; nt + 1 < ntile; nt += 3) {
             load_a(a2, min(nt + 2, ntile - 1));
             stage(c1, a0, bop[1], acc[0], c0);
-            stage(c0, a1, bop[0], acc[1], c1);                     // (behind the last row tile: one surplus MFMA chain)
-            if (nt + 1 >= ntile) break;
+            stage(c0, a1, bop[0], acc[1], c1);
+            if (nt + 2 >= ntile) { copy_a(a0, a1); break; }
             load_a(a0, min(nt + 3, ntile - 1));
             stage(c1, a1, bop[1], acc[0], c0);
             stage(c0, a2, bop[0], acc[1], c1);
-            if (nt + 2 >= ntile) break;
+            if (nt + 3 >= ntile) { copy_a(a0, a2); break; }
             load_a(a1, min(nt + 4, ntile - 1));
             stage(c1, a2, bop[1], acc[0], c0);
             stage(c0, a0, bop[0], acc[1], c1);
         }
+        refill(0);
+        stage(c1, a0, bop[1], acc[0], c0);
+        refill(1);
+        drain(acc[1], c1);
     } else {
         // (the row loop is unrolled twice so that the two operand buffers swap roles without register moves: the 16 v_mov of
         //  a_cur = a_nxt were 7 % of the vector issue time of a row tile at G = 6)
@@ -180,7 +215,7 @@ __device__ __forceinline__ void pairs_group(int tb, pp_h8 (&bop)[GG][KS], int tb
         mma(c0, a_0, bop[0]);
         auto row = [&](const pp_h8 (&a_cur)[KS], const pp_h8 (&a_nxt)[KS]) __attribute__((always_inline)) {
             if constexpr (GG == 1) {
-                stage(c1, a_nxt, bop[0], acc[0], c0);              // (behind the last row tile: one surplus MFMA chain)
+                stage(c1, a_nxt, bop[0], acc[0], c0);
                 c0 = c1;
             } else {
 #pragma unroll
@@ -191,16 +226,37 @@ __device__ __forceinline__ void pairs_group(int tb, pp_h8 (&bop)[GG][KS], int tb
                 }
             }
         };
+        // (all row tiles but the last)
 #pragma unroll 1
-        for (int nt = 0; nt < ntile; nt += 2) {
-            load_a(a_1, min(nt + 1, ntile - 1));
+        for (int nt = 0; nt + 1 < ntile; nt += 2) {
+            load_a(a_1, nt + 1);
             row(a_0, a_1);
-            if (nt + 1 >= ntile) break;
-            load_a(a_0, min(nt + 2, ntile - 1));
+            if (nt + 2 >= ntile) break;
+            load_a(a_0, nt + 2);
             row(a_1, a_0);
         }
+        // The last row tile, peeled: the next group's operands are fetched between its stages, and its last stage has no chain
+        // to issue (drain).  Its row operands are in a_0 or a_1 by the parity of ntile; they are read once more into a_0 (KS
+        // ds_read_b128): merging the two buffers with a copy costs the register allocation 16 more registers throughout the
+        // loop, and spills.
+        load_a(a_0, ntile - 1);
+        refill(0);
+        if constexpr (GG == 1) {
+            drain(acc[0], c0);
+        } else {
+#pragma unroll
+            for (int g = 0; g < GG; g += 2) {
+                stage(c1, a_0, bop[g + 1], acc[g], c0);
+                refill(g + 1);
+                if (g + 2 < GG) {
+                    stage(c0, a_0, bop[g + 2], acc[g + 1], c1);
+                    refill(g + 2);
+                } else {
+                    drain(acc[g + 1], c1);
+                }
+            }
+        }
     }
-    if (tb_next >= 0) pairs_load<KS, GG, NW>(bop, tb_next, img, l5, half);
     // ---- column sums: add the lane halves, scale by alpha^2 exp2(beta_p), store (first chunk) or accumulate ----
 #pragma unroll
     for (int g = 0; g < GG; ++g) {
@@ -312,22 +368,21 @@ __global__ __launch_bounds__(64 * NW, PP_WAVES) void psi2_pairs_kernel(int N, in
         if (tb + NW * (G - 1) < t1) {
             pp_h8 bop[G][KS];
             pairs_load<KS, G, NW>(bop, tb, img, l5, half);
-            for (; tb + NW * (G - 1) < t1; tb += NW * G) {
-                const int nx = tb + NW * G;
-                pairs_group<KS, G, NW>(tb, bop, nx + NW * (G - 1) < t1 ? nx : -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out,
-                                   Mp, chunk);
-            }
+            for (; tb + NW * (2 * G - 1) < t1; tb += NW * G)
+                pairs_group<KS, G, NW, true>(tb, bop, tb + NW * G, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
+            pairs_group<KS, G, NW, false>(tb, bop, -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
+            tb += NW * G;
         }
         if constexpr (G > 2)
             for (; tb + NW < t1; tb += 2 * NW) {
                 pp_h8 bop[2][KS];
                 pairs_load<KS, 2, NW>(bop, tb, img, l5, half);
-                pairs_group<KS, 2, NW>(tb, bop, -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
+                pairs_group<KS, 2, NW, false>(tb, bop, -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
             }
         for (; tb < t1; tb += NW) {
             pp_h8 bop[1][KS];
             pairs_load<KS, 1, NW>(bop, tb, img, l5, half);
-            pairs_group<KS, 1, NW>(tb, bop, -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
+            pairs_group<KS, 1, NW, false>(tb, bop, -1, aimg, img, pmap, sc_b, ntile, l5, half, poison, out, Mp, chunk);
         }
     }
 }
