@@ -90,6 +90,10 @@ SIGNATURES = {
     'dpgp_qx_psi_point_moments_f64': (_i, [_i] * 6 + [_vp] * 12 + [_vp, _sz, _vp]),
     'dpgp_qx_psi_pointwise_adjoint_workspace_bytes': (_sz, [_i] * 6),
     'dpgp_qx_psi_pointwise_adjoint_f64': (_i, [_i] * 6 + [_vp] * 13 + [_vp, _sz, _vp]),
+    'dpgp_ard_rbf_point_metric_workspace_bytes': (_sz, [_i] * 4),
+    'dpgp_ard_rbf_point_metric_f64': (_i, [_i] * 4 + [_vp] * 6 + [_vp, _sz, _vp]),
+    'dpgp_ard_rbf_point_jacobian_workspace_bytes': (_sz, [_i] * 5),
+    'dpgp_ard_rbf_point_jacobian_f64': (_i, [_i] * 5 + [_vp] * 6 + [_vp, _sz, _vp]),
     'dpgp_psi_latent_adjoint_workspace_bytes': (_sz, [_i] * 4),
     'dpgp_psi_latent_adjoint_f64': (_i, [_i] * 4 + [_vp] * 6 + [_i] + [_vp] * 5 + [_vp, _sz, _vp]),
     'dpgp_psi2_weighted_f64': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),

@@ -654,9 +654,10 @@ def dp_gp_lvm(y_train,
             mean[:, here], var[:, here] = mn[:, :, 0].transpose(0, 1), vr[:, :, 0].transpose(0, 1)
         return mean, var
 
-    def _frozen_predictor(cols):
-        """The training side of _marginals_at / _marginals_at_masked of the output dims `cols`, formed once, as a
-        predictor.FrozenPredictor (its forward is their operator call on the same arrays)."""
+    def _frozen_columns(cols):
+        """The training side of _marginals_at / _marginals_at_masked of the output dims `cols`, formed once: the arguments of
+        predictor.of_columns (z, gamma [K,Q], alpha [K], beta [K], c [K,M,M], r [K,M], here, prior_var [J], scatter) for the K
+        columns of `cols` that were observed in training, at the places `here`."""
         cols = np.asarray(cols)
         idx = torch.as_tensor(cols, device=device)
         f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
@@ -671,7 +672,7 @@ def dp_gp_lvm(y_train,
             y_u = _t(np.asarray(y_train)[:, cols]).to(TORCH_DTYPE).transpose(0, 1).contiguous()[:, :, None]
             r, c = collapsed.posterior(r0, collapsed.k_inverse(li), bu, ops.matmul(psi_1.transpose(1, 2), y_u))
             here = torch.arange(cols.size, device=device)
-            return _predictor.of_columns(z, gu, au, bu, c.contiguous(), r[:, :, 0].contiguous(), here, au + 1.0 / bu, False, device)
+            return z, gu, au, bu, c.contiguous(), r[:, :, 0].contiguous(), here, au + 1.0 / bu, False
         pos, seen = np.searchsorted(masked.cols_np, cols), np.isin(cols, masked.cols_np)
         au, bu = buf['alpha'][:, 0][idx].contiguous(), buf['beta'][:, 0][idx].contiguous()
         here = torch.as_tensor(np.flatnonzero(seen), dtype=torch.long, device=device)
@@ -681,7 +682,33 @@ def dp_gp_lvm(y_train,
             sel = torch.as_tensor(pos[seen], dtype=torch.long, device=device)
             c, rhs = masked.posterior(x_u.detach(), x_mean.detach(), F.softplus(x_var_raw).detach(), gu, a_, b_, sel=sel)
             c, rhs = f64(c), f64(rhs)
-        return _predictor.of_columns(z, f64(gu), f64(a_), f64(b_), c, rhs, here, f64(au + 1.0 / bu), True, device)
+        return z, f64(gu), f64(a_), f64(b_), c, rhs, here, f64(au + 1.0 / bu), True
+
+    def _frozen_predictor(cols):
+        """_frozen_columns as a predictor.FrozenPredictor (its forward is _marginals_at's operator call on the same arrays)."""
+        return _predictor.of_columns(*_frozen_columns(cols), device)
+
+    def _latent_geometry(cols):
+        """The pieces of the Jacobian and the metric of the output dims `cols`: the observed columns as the K kernels of a
+        marginals._Marginals with one column each (None when no column of `cols` was observed in training), their places `here`,
+        and sum_d alpha_d diag(gamma_d) [Q x Q] over the columns never observed (the prior of their Jacobian rows)."""
+        z, gu, au, bu, c, r, here, _, _ = _frozen_columns(cols)
+        idx = torch.as_tensor(np.asarray(cols), device=device)
+        prior = buf['alpha'][:, 0][idx].to(TORCH_DTYPE)[:, None] * buf['gamma'][idx].to(TORCH_DTYPE)              # [J, Q]
+        unseen = torch.ones(len(cols), dtype=torch.bool, device=device)
+        unseen[here] = False
+        prior_unseen = torch.diag_embed(torch.sum(prior[unseen], dim=0))
+        k = int(here.numel())
+        if not k:
+            return None, here, prior_unseen
+        marg = _marginals._Marginals(z[None].expand(k, -1, -1), gu, au, bu, None, c[:, None], r[:, :, None],
+                                     torch.zeros((k, 1), dtype=torch.int32, device=device))
+        return marg, here, prior_unseen
+
+    def _geometry_columns(columns):
+        cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
+        assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+        return cols
 
     def _assembled_marginals(cols, xt, st_):
         """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
@@ -969,6 +996,50 @@ def dp_gp_lvm(y_train,
             evaluate()
             with torch.no_grad():
                 return _frozen_predictor(cols)
+
+        @staticmethod
+        def predictive_jacobian(x, columns=None):
+            """[N* x len(columns) x Q]: the mean of the Jacobian d f_d / d x of the noise-free map of the output dims `columns`
+            (default: all D) at the DETERMINISTIC latent points x [N* x Q] (numpy or torch), b_d(x)^T r_d under each column's
+            mixed kernel of this evaluation: the derivative of predictive_marginals' mean at x_test_var = 0.  One call of
+            ops.ard_rbf_point_jacobian with every column its own kernel; the features [D, N*, M, Q] are never formed.  A column
+            never observed in training has a zero row.  The training side is built once per call.  fp64, torch.no_grad.  Not
+            built for a model sharded over a process group: AssertionError."""
+            assert not split, 'predictive_jacobian is not built for a model sharded over a process group'
+            cols = _geometry_columns(columns)
+            xp = _marginals.points_arg(x, num_latent_dims, device)
+            evaluate()
+            with torch.no_grad():
+                marg, here, _ = _latent_geometry(cols)
+                out = torch.zeros((xp.shape[0], cols.size, num_latent_dims), dtype=TORCH_DTYPE, device=device)
+                if marg is not None:
+                    out[:, here] = marg.jacobian(xp)[:, :, 0].transpose(0, 1)
+                return out
+
+        @staticmethod
+        def latent_metric(x, columns=None):
+            """[N* x Q x Q]: the expected Riemannian metric G(x) = sum_d E[J_d J_d^T] of the map from latent space to the output
+            dims `columns` (default: all D) at the latent points x [N* x Q] (Tosi et al., UAI 2014; formulas in
+            models/marginals.py), every column under its own mixed kernel: one call of ops.ard_rbf_point_metric over
+            K = len(columns) kernels, summed over them in blocks of points.  With the columns of one discovered group it shows which region and which
+            latent directions that group uses.  A column never observed in training contributes alpha_d diag(gamma_d).  fp64.
+            Not built for a model sharded over a process group: AssertionError."""
+            assert not split, 'latent_metric is not built for a model sharded over a process group'
+            cols = _geometry_columns(columns)
+            xp = _marginals.points_arg(x, num_latent_dims, device)
+            evaluate()
+            with torch.no_grad():
+                marg, _, prior_unseen = _latent_geometry(cols)
+                g = prior_unseen[None].expand(xp.shape[0], -1, -1)
+                return g.clone() if marg is None else marg.metric_total(xp) + g
+
+        @staticmethod
+        def magnification(x, columns=None):
+            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), as exp(1/2 logdet) from a Cholesky
+            factorisation of G.  Not built for a model sharded over a process group: AssertionError."""
+            assert not split, 'magnification is not built for a model sharded over a process group'
+            with torch.no_grad():
+                return _marginals.magnification(DP_GP_LVM.latent_metric(x, columns))
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1733,6 +1804,34 @@ def dp_gp_lvm_t(y_train,
             parameters: stale after further training.  Not built for a sharded model: AssertionError."""
             cols = _columns_arg(columns)
             return _predictor.of_mixture(_moments(), cols, device)
+
+        @staticmethod
+        def predictive_jacobian(x, columns=None):
+            """[N* x len(columns) x Q]: the mean of the Jacobian d f_d / d x of the noise-free map of the output dims `columns`
+            (default: all D) at the DETERMINISTIC latent points x [N* x Q] (numpy or torch), sum_t phi_td b_t(x)^T r_td: the
+            derivative of predictive_marginals' mean at x_test_var = 0 (ops.ard_rbf_point_jacobian on the T atoms).  The training
+            side is built once per call.  fp64, torch.no_grad."""
+            cols = _columns_arg(columns)
+            with torch.no_grad():
+                return _moments().jacobian(_marginals.points_arg(x, num_latent_dims, device), cols)
+
+        @staticmethod
+        def latent_metric(x, columns=None):
+            """[N* x Q x Q]: the expected Riemannian metric of the map from latent space to the output dims `columns` (default:
+            all D) at the latent points x [N* x Q] (Tosi et al., UAI 2014), the mixture's second moment over the atoms
+            (frozen_bound_t._MomentsT.metric; one call of ops.ard_rbf_point_metric on the T atoms).  With the columns of one
+            discovered group it shows which region and which latent directions that group uses.  A column never observed in
+            training contributes sum_t phi_td alpha_t diag(gamma_t).  fp64."""
+            cols = _columns_arg(columns)
+            with torch.no_grad():
+                return _moments().metric(_marginals.points_arg(x, num_latent_dims, device), cols)
+
+        @staticmethod
+        def magnification(x, columns=None):
+            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), as exp(1/2 logdet) from a Cholesky
+            factorisation of G."""
+            with torch.no_grad():
+                return _marginals.magnification(DP_GP_LVM_T.latent_metric(x, columns))
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

@@ -10,6 +10,7 @@ import torch
 from .. import ops
 from ..utils.types import TORCH_DTYPE
 from . import collapsed
+from .marginals import _Marginals
 from .masked_bound_t import _PatternLayout, slot_column_values
 
 
@@ -103,3 +104,20 @@ class _MomentsT:
         tr_d = tr.index_select(2, pat.clamp(min=0)) * seen                                         # [T, N*, J]
         var_t = (self.aat + 1.0 / self.bat)[:, None, None] - tr_d + quad - mean_t * mean_t
         return mixture_moments(self.phit.index_select(1, cols), mean_t, var_t)
+
+    def _atoms(self):
+        """The T atoms as the kernels of a marginals._Marginals: every atom sees all D columns, column d on its pattern p(d)."""
+        gidx = self.pattern.to(torch.int32)[None].expand(self.r.shape[0], -1)
+        return _Marginals(self.z_t, self.gat, self.aat, self.bat, self.zfac, self.c, self.r, gidx)
+
+    def jacobian(self, x, cols):
+        """[N* x len(cols) x Q]: the mean of the mixture's Jacobian rows at the deterministic latent points x,
+        sum_t phi_td b_t(x)^T r_td (ops.ard_rbf_point_jacobian on the T atoms)."""
+        jac_t = self._atoms().jacobian(x, cols)                                                    # [T, N*, J, Q]
+        return torch.sum(self.phit.index_select(1, cols)[:, None, :, None] * jac_t, dim=0)
+
+    def metric(self, x, cols):
+        """[N* x Q x Q]: the expected metric over the columns `cols`, the second moment of the mixture over the atoms as
+        mixture_moments takes it for the variance: sum_t ( n_t alpha_t diag(gamma_t) + b_t^T P_t b_t ), n_t = sum_d phi_td,
+        P_t = sum_d phi_td (r_td r_td^T - C_t,p(d))  (marginals._Marginals.metric_total with phi as the columns' weights)."""
+        return self._atoms().metric_total(x, cols, weights=self.phit)

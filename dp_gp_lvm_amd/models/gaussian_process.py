@@ -548,6 +548,33 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
                 return _predictor.of_marginals(_train_marginals(), cols, dev_)
 
         @staticmethod
+        def predictive_jacobian(x, columns=None):
+            """[N* x len(columns) x Q]: the mean of the Jacobian d f_d / d x of the noise-free map of the output dims `columns`
+            (default: all D) at the DETERMINISTIC latent points x [N* x Q] (numpy or torch): the derivative of
+            predictive_marginals' mean at x_test_var = 0 (models/marginals.py; one call of ops.ard_rbf_point_jacobian).
+            The training side is built once per call.  fp64, torch.no_grad."""
+            cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+            with torch.no_grad():
+                return _train_marginals().jacobian(_marginals.points_arg(x, num_latent_dims, dev_), cols)[0]
+
+        @staticmethod
+        def latent_metric(x, columns=None):
+            """[N* x Q x Q]: the expected Riemannian metric G(x) = sum_d E[J_d J_d^T] of the map from latent space to the output
+            dims `columns` (default: all D) at the latent points x [N* x Q] (Tosi et al., UAI 2014; formulas in
+            models/marginals.py; one call of ops.ard_rbf_point_metric).  Works on a model trained on complete data and on one
+            trained with observed= (a column never observed in training contributes its prior alpha diag(gamma)).  fp64."""
+            cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+            with torch.no_grad():
+                return _train_marginals().metric(_marginals.points_arg(x, num_latent_dims, dev_), cols)[0]
+
+        @staticmethod
+        def magnification(x, columns=None):
+            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), the volume element of the learnt map
+            (what GPy draws as plot_magnification), as exp(1/2 logdet) from a Cholesky factorisation of G."""
+            with torch.no_grad():
+                return _marginals.magnification(BayesianGPLVM.latent_metric(x, columns))
+
+        @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
                                  observed=None, marginal_variance=False):
             """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
@@ -978,6 +1005,11 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                    for i, v in enumerate(views)]
         return [o[0][0] for o in out], [o[1][0] for o in out]
 
+    def _views_arg(views):
+        vs = list(range(num_views)) if views is None else [int(v) for v in views]
+        assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
+        return vs
+
     class ManifoldRelevanceDetermination(Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
         test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
@@ -1019,6 +1051,32 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             with torch.no_grad():
                 train = _train_marginals()
                 return [_predictor.of_marginals(train[v], _marginals.columns_arg(None, num_dimensions[v], dev_), dev_) for v in vs]
+
+        @staticmethod
+        def predictive_jacobian(x, views=None):
+            """One tensor [N* x D_v x Q] per view of `views` (default: all V, in order): the mean of the Jacobian of the view's
+            noise-free map at the deterministic latent points x [N* x Q], as bayesian_gp_lvm.predictive_jacobian."""
+            vs = _views_arg(views)
+            with torch.no_grad():
+                train, xp = _train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_)
+                return [train[v].jacobian(xp)[0] for v in vs]
+
+        @staticmethod
+        def latent_metric(x, views=None, total=False):
+            """One expected metric [N* x Q x Q] per view of `views` (default: all V, in order) at the latent points x [N* x Q],
+            as bayesian_gp_lvm.latent_metric with the view's own kernel: which latent directions each view stretches.
+            total=True: their sum, one tensor, the metric of the map to the chosen views' stacked columns."""
+            vs = _views_arg(views)
+            with torch.no_grad():
+                train, xp = _train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_)
+                out = [train[v].metric(xp)[0] for v in vs]
+            return torch.sum(torch.stack(out), dim=0) if total else out
+
+        @staticmethod
+        def magnification(x, views=None):
+            """One magnification factor sqrt(det G_v(x)) [N*] per view of `views` (default: all V, in order)."""
+            with torch.no_grad():
+                return [_marginals.magnification(g) for g in ManifoldRelevanceDetermination.latent_metric(x, views)]
 
         @staticmethod
         def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,

@@ -10,6 +10,12 @@ psi1*(n), Psi2*(n) test point n's own statistics.  Observation noise 1/beta is i
 r_d = 0 and no trace term: mean 0, variance alpha + 1/beta.  The training side (the chain of models/masked_bound.py) is formed once
 per _Marginals; summed over the test points the variance is the reference-shaped array's entry,
     sum_n var(n,d) = covar[d,0,0] + (N* - 1)/beta                            (gaussian_process._predictive_moments).
+
+The same training side gives the geometry of the map from latent space to data at a DETERMINISTIC latent point x (Tosi et al.,
+"Metrics for probabilistic geometries", UAI 2014): with b_mq(x) = d k_m(x) / d x_q the Jacobian row of column d is Gaussian,
+    mean m_d(x) = b(x)^T r_d [Q],     covariance Sigma_d(x) = alpha diag(gamma) - b(x)^T (K_uu^-1 - P_p(d)) b(x) [Q x Q]
+(d^2 k(x, x') / dx_q dx'_q' = alpha gamma_q delta_qq' at x' = x; the noise-free function: no 1/beta), and the expected metric over
+a set of columns is G(x) = sum_d (m_d m_d^T + Sigma_d); sqrt(det G) is the magnification factor.  _Marginals.jacobian / .metric.
 """
 import numpy as np
 import torch
@@ -36,11 +42,67 @@ class _Marginals:
         return ops.qx_psi_point_moments(self.z, mu.contiguous(), s.contiguous(), self.gamma, self.alpha, self.c, r, gidx, self.beta,
                                         zfac=self.zfac)
 
+    def jacobian(self, x, cols=None):
+        """[K, N*, len(cols), Q]: the mean of the Jacobian row of every column at the deterministic latent points x [N*,Q],
+        m_d(x) = b(x)^T r_d with b_mq = d k_m / d x_q (ops.ard_rbf_point_jacobian; the module's text for r)."""
+        r = self.r if cols is None else self.r.index_select(2, cols).contiguous()
+        return ops.ard_rbf_point_jacobian(self.z, x.contiguous(), self.gamma, self.alpha, r)
+
+    def metric(self, x, cols=None, weights=None):
+        """[K, N*, Q, Q]: every kernel's share of the expected metric of the noise-free map at x [N*,Q] over the columns `cols`,
+            G_k(x) = sum_d w_kd (m_d m_d^T + Sigma_d) = n_k alpha_k diag(gamma_k) + b_k(x)^T P_k b_k(x)
+            Sigma_d = alpha_k diag(gamma_k) - b^T c_p(d) b,   P_k = sum_d w_kd (r_d r_d^T - c_p(d)),   n_k = sum_d w_kd
+        weights [K, D] (default: ones; the over-T model passes phi).  P_k is R diag(w) R^T and a pattern-count-weighted sum of c,
+        both by ops.matmul; the quadratic form is ONE call of ops.ard_rbf_point_metric.  A column never observed in training
+        (gidx < 0, r = 0) has no c term: it contributes w alpha diag(gamma).  1/beta does not enter."""
+        p, prior = self._metric_operands(cols, weights)
+        return ops.ard_rbf_point_metric(self.z, x.contiguous(), self.gamma, self.alpha, p) + prior[:, None]
+
+    def metric_total(self, x, cols=None, weights=None):
+        """[N*, Q, Q]: metric summed over the K kernels.  The operator's [K, n, Q, Q] result is taken over blocks of n points of at
+        most 2^25 entries, so K = D kernels on a large grid need no array of size K N* Q^2 (a point's bits do not depend on its
+        block)."""
+        p, prior = self._metric_operands(cols, weights)
+        x = x.contiguous()
+        k, q = self.z.shape[0], self.z.shape[2]
+        step = max(1, (1 << 25) // (k * q * q))
+        out = [torch.sum(ops.ard_rbf_point_metric(self.z, x[i:i + step], self.gamma, self.alpha, p), dim=0)
+               for i in range(0, x.shape[0], step)]
+        return torch.cat(out) + torch.sum(prior, dim=0)
+
+    def _metric_operands(self, cols, weights):
+        """(P [K, M, M], n_k alpha_k diag(gamma_k) [K, Q, Q]) of metric's text."""
+        r, gidx = self.r, self.gidx
+        if cols is not None:
+            r, gidx = r.index_select(2, cols).contiguous(), gidx.index_select(1, cols)
+        k, m, g = r.shape[0], r.shape[1], self.c.shape[1]
+        w = torch.ones(gidx.shape, dtype=TORCH_DTYPE, device=r.device) if weights is None else \
+            (weights if cols is None else weights.index_select(1, cols))
+        p = ops.matmul(r * w[:, None, :], r.transpose(1, 2))                                       # [K, M, M]
+        hit = gidx[:, :, None] == torch.arange(g, dtype=gidx.dtype, device=r.device)               # [K, J, G]
+        counts = torch.sum(hit.to(TORCH_DTYPE) * w[:, :, None], dim=1)                              # [K, G]
+        ops.matmul(counts[:, None, :].contiguous(), self.c.reshape(k, g, m * m), out=p.view(k, 1, m * m), alpha=-1.0, beta=1.0)
+        return p, (torch.sum(w, dim=1) * self.alpha)[:, None, None] * torch.diag_embed(self.gamma)
+
 
 def columns_arg(columns, d, device):
     cols = np.arange(d) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
     assert cols.size >= 1 and cols.min() >= 0 and cols.max() < d, 'columns must be output dims in [0, D)'
     return torch.as_tensor(cols, dtype=torch.long, device=device)
+
+
+def points_arg(x, q, device):
+    """x [N* x Q] (numpy array or torch tensor) as a contiguous fp64 tensor on the device."""
+    x = x.detach() if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+    x = x.to(device=device, dtype=TORCH_DTYPE).contiguous()
+    assert x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == q, 'x must be [N* x Q]'
+    return x
+
+
+def magnification(g):
+    """sqrt(det G) [N*] of the metrics g [N*, Q, Q], as exp(1/2 logdet) from their Cholesky factors (ops.potrf_batched)."""
+    l, _ = ops.potrf_batched(g.contiguous())
+    return torch.exp(torch.sum(torch.log(torch.diagonal(l, dim1=-2, dim2=-1)), dim=-1))
 
 
 def one_kernel(c, y, beta, slots, columns, d):

@@ -487,6 +487,65 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     return d_mu, d_s
 
 
+def _point_metric_args(z, x, gamma, alpha, a, name, what):
+    """The checks of the two operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
+    (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M] or r [K,M,J], `what` its wording)."""
+    args = (('z', z), ('x', x), ('gamma', gamma), ('alpha', alpha), (name, a))
+    for nm, v in args:
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % nm)
+    if z.dim() != 3 or min(z.shape) < 1:
+        raise ValueError('z must be [K x M x Q], got %s' % (tuple(z.shape),))
+    k, m, q = z.shape
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != q:
+        raise ValueError('x must be [N x Q] with Q = %d, got %s' % (q, tuple(x.shape)))
+    if tuple(gamma.shape) != (k, q):
+        raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
+    if alpha.numel() != k:
+        raise ValueError('alpha must be [K], got %s' % (tuple(alpha.shape),))
+    if a.dim() != 3 or a.shape[0] != k or a.shape[1] != m or a.shape[2] < 1 or (name == 'p' and a.shape[2] != m):
+        raise ValueError('%s must be %s, got %s' % (name, what, tuple(a.shape)))
+    for nm, v in args:
+        if not v.is_cuda or v.device != z.device:
+            raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
+    return z.contiguous(), x.contiguous(), gamma.contiguous(), alpha.reshape(-1).contiguous(), a.contiguous(), k, x.shape[0], m, q
+
+
+def ard_rbf_point_metric(z, x, gamma, alpha, p):
+    """The quadratic form of the derivative features at deterministic latent points (dpgp_ard_rbf_point_metric_f64): with
+    b_kmq(x_n) = d k_km(x_n) / d x_q = -gamma_kq (x_nq - z_kmq) alpha_k exp(-1/2 sum_q gamma_kq (x_nq - z_kmq)^2) of the kernels
+    z [K,M,Q], gamma [K,Q], alpha [K] at the points x [N,Q], returns
+        g [K,N,Q,Q] = sum_{m,m'} p[k,m,m'] b_kmq(x_n) b_km'q'(x_n)          p [K,M,M], used as given (not symmetrised)
+    The alpha diag(gamma) term of the expected metric is the caller's.  The features [K,N,M,Q] are never formed in memory; fixed
+    summation order, the same bits on every run.  float64 tensors (TypeError) of these shapes (ValueError) on one GPU
+    (RuntimeError)."""
+    z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]')
+    g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_point_metric_workspace_bytes(k, n, m, q)
+    ws = _ws(wsb, z.device)
+    _lib.check(l.dpgp_ard_rbf_point_metric_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
+                                               p.data_ptr(), g.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_ard_rbf_point_metric_f64')
+    return g
+
+
+def ard_rbf_point_jacobian(z, x, gamma, alpha, r):
+    """The derivative features contracted with weights (dpgp_ard_rbf_point_jacobian_f64): b as in ard_rbf_point_metric,
+        jac [K,N,J,Q] = sum_m b_kmq(x_n) r[k,m,j]                            r [K,M,J]
+    the Jacobian of the predictive means sum_m k_km(x_n) r[k,m,j] with respect to x_n.  Same rules as ard_rbf_point_metric."""
+    z, x, gamma, alpha, r, k, n, m, q = _point_metric_args(z, x, gamma, alpha, r, 'r', '[K x M x J] with J >= 1')
+    j = r.shape[2]
+    jac = torch.empty((k, n, j, q), dtype=torch.float64, device=z.device)
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_point_jacobian_workspace_bytes(k, j, n, m, q)
+    ws = _ws(wsb, z.device)
+    _lib.check(l.dpgp_ard_rbf_point_jacobian_f64(k, j, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
+                                                 r.data_ptr(), jac.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_ard_rbf_point_jacobian_f64')
+    return jac
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

@@ -64,3 +64,17 @@ def make_problem(cfg=None, shape=None, truncation_level=DEFAULT_TRUNCATION, seed
             p[k] = np.ascontiguousarray(p[k][d_slice])
         p['y'] = np.ascontiguousarray(p['y'][:, d_slice])
     return p
+
+
+def grouped_outputs(n, d, groups=3, noise=0.05, seed=1):
+    """Structured data for the examples: a latent space x [N, groups] ~ N(0, I) and `groups` blocks of output dims, block g a random
+    linear map of tanh of the latent coordinates (g, g + 1 mod groups) plus noise: the blocks use different latent directions,
+    which is what the DP over the output dims should find.  Returns (y [N,D] column-standardised, x, block index of every dim [D])."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, groups))
+    y, block = np.empty((n, d)), np.empty(d, dtype=np.int64)
+    for g, idx in enumerate(np.array_split(np.arange(d), groups)):
+        w = rng.standard_normal((2, len(idx)))
+        y[:, idx] = np.tanh(x[:, [g, (g + 1) % groups]]) @ w + noise * rng.standard_normal((n, len(idx)))
+        block[idx] = g
+    return (y - y.mean(axis=0)) / y.std(axis=0), x, block

@@ -272,6 +272,32 @@ int dpgp_qx_psi_pointwise_adjoint_f64(int K, int G, int J, int N, int M, int Q, 
                                       const double *r, const double *h, const double *gq, const double *gt, double *d_mu,
                                       double *d_s, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Latent-space metric and predictive Jacobian at deterministic latent points (csrc/ard_rbf_point_metric.hip).  K kernels with
+ *      their own inducing inputs z[K][M][Q], gamma[K][Q], alpha[K]; points x[N][Q] (no variances).  With
+ *        k_km(x_n)  = alpha_k exp(-1/2 sum_q gamma_kq (x_nq - z_kmq)^2)
+ *        b_kmq(x_n) = d k_km / d x_q = -gamma_kq (x_nq - z_kmq) k_km(x_n)
+ *      the operators are
+ *        g[K][N][Q][Q]   = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)       p[K][M][M], any matrices, used as given: a
+ *                                                                               non-symmetric p gives a non-symmetric g
+ *        jac[K][N][J][Q] = sum_m b_kmq(x_n) r[k][m][j]                          r[K][M][J]
+ *      The alpha diag(gamma) term of the expected metric is the caller's.  One launch each: a workgroup owns a kernel and a tile
+ *      of points, makes the features b on the fly (one exponential per (k, n, m) and per slab of 64 rows of p or columns of r)
+ *      and runs both products of the metric, p B and B^T (p B), on the fp64 matrix pipe; p is streamed in 64 x 64 tiles.
+ *      Nothing of size N M Q is written to memory; no atomics, the order of every sum is fixed by (M, Q): the same bits on
+ *      every run, and a kernel's results do not depend on K.  Points far from every z give exact zeros.
+ *      1 <= K, J, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, checked in this order before anything is launched:
+ *      metric:    K -1, N -2, M -3, Q -4, z -5, x -6, gamma -7, alpha -8, p -9, g -10, ws -11, ws_bytes too small -12
+ *      jacobian:  K -1, J -2, N -3, M -4, Q -5, z -6, x -7, gamma -8, alpha -9, r -10, jac -11, ws -12, ws_bytes too small -13
+ *   ws: the results are written from the accumulators, so the queries (host functions) return a token 256 bytes for a shape in
+ *      range and 0 for one out of range; the pair (ws, ws_bytes) keeps the calling convention of the other point operators. */
+size_t dpgp_ard_rbf_point_metric_workspace_bytes(int K, int N, int M, int Q);
+int dpgp_ard_rbf_point_metric_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *gamma,
+                                  const double *alpha, const double *p, double *g, void *ws, size_t ws_bytes, void *stream);
+size_t dpgp_ard_rbf_point_jacobian_workspace_bytes(int K, int J, int N, int M, int Q);
+int dpgp_ard_rbf_point_jacobian_f64(int K, int J, int N, int M, int Q, const double *z, const double *x, const double *gamma,
+                                    const double *alpha, const double *r, double *jac, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Latent adjoint of B kernels that share inducing inputs AND q(X*) (csrc/psi_latent_adjoint.hip): the frozen over-D model at
  *      test time.  z[M][Q], q(X*) = (mu[N][Q], s[N][Q]: variances), gamma[B][Q], alpha[B]; y[N][ldy]: zero-filled data, column b
  *      for kernel b; w[B][N]: weights of the test points (NULL = all ones; any finite reals); stage-A adjoints g_v[B][M] and
