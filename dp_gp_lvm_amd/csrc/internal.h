@@ -2,6 +2,16 @@
 #pragma once
 #include "common.h"
 
+// Tests and experiments: a forced plan value (a number of slabs) from the environment.  0 when the variable is unset or below lo (the
+// plan's own value stands), else the value clamped to hi.  The plan functions read it on every call, so a workspace query and the launch
+// after it agree.
+static inline int dpgp_env_plan(const char *name, int lo, int hi) {
+    const char *e = getenv(name);
+    if (!e) return 0;
+    const int v = atoi(e);
+    return v < lo ? 0 : (v > hi ? hi : v);
+}
+
 // ---- elementwise.hip -------------------------------------------------------------------------------------------
 // gram with explicit output leading dimension / batch stride so the fused ELBO can write straight into its padded
 // Cholesky workspace.  x1 == nullptr: symmetric case, noise/jitter flags honoured.

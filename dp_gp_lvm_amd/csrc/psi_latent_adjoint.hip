@@ -265,12 +265,6 @@ __global__ __launch_bounds__(256) void pl_reduce_kernel(size_t nq, int slabs, co
 
 struct PlPlan { int T, tiles, ntn, nchunks, nct, ct, cslabs, cols_per_slab, pslabs, tiles_per_slab; };
 
-int pl_env(const char *name, int lo, int hi) {               // (experiments and tests: a forced number of slabs)
-    const char *e = getenv(name);
-    if (!e) return 0;
-    const int v = atoi(e);
-    return v < lo ? 0 : (v > hi ? hi : v);
-}
 
 PlPlan pl_plan(int B, int N, int M, int Q) {
     PlPlan p;
@@ -285,12 +279,12 @@ PlPlan pl_plan(int B, int N, int M, int Q) {
     // repeats the per-column staging).  DPGP_PLA_COL_SLABS / DPGP_PLA_PAIR_SLABS force the two counts (clamped to B / the tiles)
     const long base = (long)p.ntn * p.nchunks;
     long cs = (PL_TARGET_WGS + base - 1) / base;
-    if (const int v = pl_env("DPGP_PLA_COL_SLABS", 1, B)) cs = v;
+    if (const int v = dpgp_env_plan("DPGP_PLA_COL_SLABS", 1, B)) cs = v;
     cs = cs < 1 ? 1 : (cs > B ? B : cs);
     p.cols_per_slab = dpgp_ceil_div(B, (int)cs);
     p.cslabs = dpgp_ceil_div(B, p.cols_per_slab);
     long ps = (PL_TARGET_WGS + base * p.cslabs - 1) / (base * p.cslabs);
-    if (const int v = pl_env("DPGP_PLA_PAIR_SLABS", 1, p.tiles)) ps = v;
+    if (const int v = dpgp_env_plan("DPGP_PLA_PAIR_SLABS", 1, p.tiles)) ps = v;
     ps = ps < 1 ? 1 : (ps > p.tiles ? p.tiles : ps);
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, (int)ps);
     p.pslabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);

@@ -644,12 +644,6 @@ __global__ __launch_bounds__(256) void qp_param_reduce_kernel(int B, int M, int 
 // Tests and experiments: a forced number of slabs, read on every plan so that the workspace queries and the launches agree.
 // DPGP_QP_N_SLABS: the n slabs of the stats kernel and of both terms of the parameter adjoint (clamped to the staged steps);
 // DPGP_QP_PAIR_SLABS: the pair-tile slabs of the adjoint (clamped to the tiles).  The grouped plans go through the same code.
-int qp_env(const char *name, int lo, int hi) {
-    const char *e = getenv(name);
-    if (!e) return 0;
-    const int v = atoi(e);
-    return v < lo ? 0 : (v > hi ? hi : v);
-}
 
 struct QpStatsPlan { int T, tiles, slabs, n_per_slab; };
 QpStatsPlan qp_stats_plan(int B, int N, int M) {
@@ -658,7 +652,7 @@ QpStatsPlan qp_stats_plan(int B, int N, int M) {
     p.tiles = qp_tiles(M);
     const int chunks = dpgp_ceil_div(N, QP_SN);
     int sl = dpgp_ceil_div(QP_TARGET_WGS / 2, p.tiles * B);
-    if (const int v = qp_env("DPGP_QP_N_SLABS", 1, chunks)) sl = v;
+    if (const int v = dpgp_env_plan("DPGP_QP_N_SLABS", 1, chunks)) sl = v;
     sl = sl < 1 ? 1 : (sl > chunks ? chunks : sl);
     p.n_per_slab = dpgp_ceil_div(chunks, sl) * QP_SN;
     p.slabs = dpgp_ceil_div(N, p.n_per_slab);
@@ -674,7 +668,7 @@ QpAdjPlan qp_adj_plan(int B, int N, int M, int Q) {
     p.qchunks = dpgp_ceil_div(Q, QP_QCHUNK);
     long base = (long)p.nt * B * p.qchunks;
     int sl = (int)((QP_TARGET_WGS + base - 1) / base);
-    if (const int v = qp_env("DPGP_QP_PAIR_SLABS", 1, p.tiles)) sl = v;
+    if (const int v = dpgp_env_plan("DPGP_QP_PAIR_SLABS", 1, p.tiles)) sl = v;
     sl = sl < 1 ? 1 : (sl > p.tiles ? p.tiles : sl);
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, sl);
     p.slabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);
@@ -691,7 +685,7 @@ QpParamPlan qp_param_plan(int B, int N, int M, int Q) {
     const int chunks = dpgp_ceil_div(N, QP_SN);
     const long base = (long)p.tiles * B * p.qchunks;
     int sl = (int)((QP_TARGET_WGS / 2 + base - 1) / base);
-    const int forced = qp_env("DPGP_QP_N_SLABS", 1, chunks);
+    const int forced = dpgp_env_plan("DPGP_QP_N_SLABS", 1, chunks);
     if (forced) sl = forced;
     sl = sl < 1 ? 1 : (sl > chunks ? chunks : sl);
     p.n_per_slab = dpgp_ceil_div(chunks, sl) * QP_SN;
@@ -1478,7 +1472,7 @@ QgAdjPlan qg_adj_plan(int K, int P, int N, int M, int Q) {
     p.qchunks = dpgp_ceil_div(Q, QP_QCHUNK);
     const long base = (long)p.nt * K * p.qchunks * p.pchunks;
     int sl = (int)((QP_TARGET_WGS + base - 1) / base);
-    if (const int v = qp_env("DPGP_QP_PAIR_SLABS", 1, p.tiles)) sl = v;
+    if (const int v = dpgp_env_plan("DPGP_QP_PAIR_SLABS", 1, p.tiles)) sl = v;
     sl = sl < 1 ? 1 : (sl > p.tiles ? p.tiles : sl);
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, sl);
     p.slabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);

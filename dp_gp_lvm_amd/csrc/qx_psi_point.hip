@@ -213,6 +213,10 @@ __global__ __launch_bounds__(256) void pw_reduce_kernel(int K, int G, int J, int
 }
 
 struct PwPlan { int T, tiles, ntn, nchunks, nct, ct, slabs, tiles_per_slab; };
+
+// Tests and experiments: DPGP_PW_PAIR_SLABS forces the number of pair-tile slabs (clamped to the tiles; unset or < 1: the plan's own).
+// It is read on every plan, so the workspace queries and the launches agree; the moments operator plans through the same function.
+
 PwPlan pw_plan(int K, int G, int J, int N, int M, int Q) {
     PwPlan p;
     p.T = dpgp_ceil_div(M, PW_TILE);
@@ -224,6 +228,7 @@ PwPlan pw_plan(int K, int G, int J, int N, int M, int Q) {
     p.ct = p.nct <= 1 ? 1 : p.nct <= 2 ? 2 : p.nct <= 4 ? 4 : 8;
     const long base = (long)p.ntn * K * p.nchunks;
     long sl = (PW_TARGET_WGS + base - 1) / base;
+    if (const int v = dpgp_env_plan("DPGP_PW_PAIR_SLABS", 1, p.tiles)) sl = v;
     sl = sl < 1 ? 1 : (sl > p.tiles ? p.tiles : sl);
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, (int)sl);
     p.slabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);

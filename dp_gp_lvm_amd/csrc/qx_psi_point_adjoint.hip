@@ -321,6 +321,10 @@ __global__ __launch_bounds__(256) void pa_reduce_kernel(size_t nq, int slabs, co
 
 struct PaPlan { int T, tiles, ntn, nchunks, nct, ct, mt, kslabs, k_per_slab, pslabs, tiles_per_slab; };
 
+// Tests and experiments: a forced number of slabs, read on every plan so that the workspace query and the launch agree.
+// DPGP_PA_K_SLABS: the slabs of kernels k (clamped to K);  DPGP_PA_PAIR_SLABS: the pair-tile slabs (clamped to the tiles).
+// Unset or < 1: the plan's own.
+
 PaPlan pa_plan(int K, int G, int J, int N, int M, int Q) {
     PaPlan p;
     p.T = dpgp_ceil_div(M, PA_TILE);
@@ -336,10 +340,12 @@ PaPlan pa_plan(int K, int G, int J, int N, int M, int Q) {
     // enough workgroups to fill the GPU: first by slabs of kernels (no work is repeated), then by slabs of pair tiles
     const long base = (long)p.ntn * p.nchunks;
     long ks = (PA_TARGET_WGS + base - 1) / base;
+    if (const int v = dpgp_env_plan("DPGP_PA_K_SLABS", 1, K)) ks = v;
     ks = ks < 1 ? 1 : (ks > K ? K : ks);
     p.k_per_slab = dpgp_ceil_div(K, (int)ks);
     p.kslabs = dpgp_ceil_div(K, p.k_per_slab);
     long ps = (PA_TARGET_WGS + base * p.kslabs - 1) / (base * p.kslabs);
+    if (const int v = dpgp_env_plan("DPGP_PA_PAIR_SLABS", 1, p.tiles)) ps = v;
     ps = ps < 1 ? 1 : (ps > p.tiles ? p.tiles : ps);
     p.tiles_per_slab = dpgp_ceil_div(p.tiles, (int)ps);
     p.pslabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);

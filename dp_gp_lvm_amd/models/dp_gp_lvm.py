@@ -15,6 +15,8 @@ The same holds for a model trained with observed= (its bound runs on the local c
 per-entry moments and for the shared-inducing test bound, whose sums over columns are completed by one all-reduce each
 (DESIGN.md section 7.15).
 """
+import contextlib
+import gc
 import os
 import numpy as np
 import torch
@@ -79,6 +81,23 @@ def weighted_shard_bounds(costs, rank, world_size, align=1):
         for k in range(world_size, 0, -1):
             cuts.append(best[k][cuts[-1]][2])
     return min(cuts[rank] * align, d), min(cuts[rank + 1] * align, d)
+
+
+@contextlib.contextmanager
+def _graph_capture(graph):
+    """torch.cuda.graph(graph) with Python's cyclic garbage collector held off for the length of the capture.  A model that went out of
+    use inside a reference cycle keeps its torch.cuda.CUDAGraph until a collection, torch no longer collects on entry, and a collection
+    that falls inside a capture destroys that graph there: destroying a graph is not permitted while a stream is capturing, the
+    destructor throws and the process aborts.  So: collect first, then capture with the collector disabled."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _adam(params, learning_rate):
@@ -357,7 +376,7 @@ def dp_gp_lvm(y_train,
             evaluate()                                   # (first call outside the capture: function attributes, warm-up)
             torch.cuda.synchronize()
             gph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gph):
+            with _graph_capture(gph):
                 evaluate(_local_part_only=True)
             graph_state['graph'] = gph
         graph_state['graph'].replay()
@@ -1456,7 +1475,7 @@ def dp_gp_lvm_t(y_train,
                     evaluate()
             cur.wait_stream(side)
             g_ = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_):
+            with _graph_capture(g_):
                 with torch.no_grad():
                     graph['out'] = _evaluate_fused(finish=False) if fused_t is not None else _objective_of(raw_vars)
             graph['g'] = g_
@@ -1549,7 +1568,7 @@ def dp_gp_lvm_t(y_train,
                         _local_flat()
                 cur.wait_stream(side)
                 g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_):
+                with _graph_capture(g_):
                     grad_graph['flat'] = _local_flat()
                 grad_graph['g'] = g_
             grad_graph['g'].replay()

@@ -126,7 +126,7 @@ def qp_tiles(m):
 
 
 def forced(env, name, hi):
-    """qp_env(name, 1, hi): 0 when unset or below 1 (the natural value stands), else the value clamped to hi."""
+    """dpgp_env_plan(name, 1, hi) of csrc/internal.h: 0 when unset or below 1 (the natural value stands), else the value clamped to hi."""
     if name not in env:
         return 0
     v = int(env[name])
