@@ -304,94 +304,98 @@ static inline size_t lds_chol_elems(int nbf, int nborder) {      // dinv tile + 
     return (size_t)TSZ * (size_t)(1 + nbf * (nbf + 1) / 2) + (size_t)nborder * nbf * LDT;
 }
 
-// ---- pivot reciprocal root to working precision, for the pivot chain: native seed + Newton steps written out so that the
-// dependent chain is known (v_rsq_f64 is good to 5.2e-8 relative on gfx950, scratch/ubench/lat64.hip: two steps; v_rsq_f32 to
-// one ulp: one step) ----
-__device__ __forceinline__ double pivot_rsqrt(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    const double h = 0.5 * d;
-    double e = __builtin_fma(-(h * y), y, 0.5);
-    y = __builtin_fma(y, e, y);
-    e = __builtin_fma(-(h * y), y, 0.5);
-    return __builtin_fma(y, e, y);
-}
-__device__ __forceinline__ float pivot_rsqrt(float d) {
-    float y = __builtin_amdgcn_rsqf(d);
-    const float e = __builtin_fmaf(-(0.5f * d * y), y, 0.5f);
-    return __builtin_fmaf(y, e, y);
-}
-
 // ---- the register panel of potrf_lds: DPP row broadcasts (row = 16 lanes) ------------------------------------------------
 // On gfx950 v_fmac_f64 with a row_newbcast source costs what a plain v_fma_f64 does (4.9 cycles of issue,
 // scratch/ubench/lat64b.hip) against 17 + 5 for a v_readlane pair into SGPRs + fma: the broadcast is free.  Rules this code
 // keeps: (1) a VALU write needs two wait states before a DPP read of the same register and the compiler's hazard recognizer
-// does not see into asm statements — the one place where a producer stands directly in front of its DPP consumer carries its
-// own s_nop; (2) the statements are volatile, so they stay in source order; (3) everything that belongs between two column
-// updates sits INSIDE one asm statement: around every separate asm statement the compiler puts a conservative s_nop
+// does not see into asm statements — the two places where a producer can stand directly in front of its DPP consumer carry
+// their own s_nop; (2) the statements are volatile, so they stay in source order; (3) everything that belongs between two
+// column updates sits INSIDE one asm statement: around every separate asm statement the compiler puts a conservative s_nop
 // (125 per block column in the first version).
 // One column c > J of pivot J for this lane's two rows (a: its row below the tile, g: its copy of row lane & 15 of the
-// tile), preceded by operation N of the reciprocal chain of the NEXT pivot (PivotChain; N >= NOPS: none).
+// tile): both lose (their own entry of column J of L) x (entry c of column J of L), the second factor being tg of lane c of
+// the row of lanes.  The product is the same on lane i for column c as on lane c for column i, so the redundant copies of the
+// diagonal tile stay symmetric BIT FOR BIT.  (The first version eliminated with multipliers a_iJ / d_J times row J of the
+// tile: the two copies of an entry then differ by a rounding, the factor that comes out is that of a slightly unsymmetric
+// matrix, and the difference is magnified by every later multiplier: componentwise backward errors of 1e3 u at M = 32 and
+// beyond 1e5 u at M = 64 on the grams with jitter 1e-8 that the models factor — tests/test_gpu_dense_edges.py, P1.)
+// Preceded by operation N of the reciprocal-root chain of the NEXT pivot (PivotChain; N >= NOPS: none).
 #define DPGP_FMAC2_F64                                                                                          \
-    "v_fmac_f64_dpp %[a], -%[g], %[ta] row_newbcast:%[j] row_mask:0xf bank_mask:0xf\n\t"                        \
-    "v_fmac_f64_dpp %[g], -%[g], %[tg] row_newbcast:%[j] row_mask:0xf bank_mask:0xf"
+    "v_fmac_f64_dpp %[a], -%[tg], %[ta] row_newbcast:%[c] row_mask:0xf bank_mask:0xf\n\t"                       \
+    "v_fmac_f64_dpp %[g], -%[tg], %[tg] row_newbcast:%[c] row_mask:0xf bank_mask:0xf"
 #define DPGP_FMAC2_F32                                                                                          \
-    "v_fmac_f32_dpp %[a], -%[g], %[ta] row_newbcast:%[j] row_mask:0xf bank_mask:0xf\n\t"                        \
-    "v_fmac_f32_dpp %[g], -%[g], %[tg] row_newbcast:%[j] row_mask:0xf bank_mask:0xf"
-// The reciprocal of the next pivot, two Newton steps from v_rcp_f64 (good to 4.6e-8 relative, scratch/ubench/lat64.hip; one
-// step from v_rcp_f32), as single operations that ride in front of the column updates: the compiler does not move this
-// dependent chain in between them by itself (16 x ~30 cycles of exposed latency per block column).
+    "v_fmac_f32_dpp %[a], -%[tg], %[ta] row_newbcast:%[c] row_mask:0xf bank_mask:0xf\n\t"                       \
+    "v_fmac_f32_dpp %[g], -%[tg], %[tg] row_newbcast:%[c] row_mask:0xf bank_mask:0xf"
+// The reciprocal root of the next pivot to working precision, as single operations that ride in front of the column updates
+// (the compiler does not move this dependent chain in between them by itself: 16 x ~30 cycles of exposed latency per block
+// column).  fp64: v_rsq_f64 (good to 5.2e-8 relative, scratch/ubench/lat64.hip) and ONE third-order step, y (1 + e / 2 +
+// 3 e^2 / 8) with e = 1 - d y^2 (the next term, 5 e^3 / 16, is 1e-22): six operations, one more than the reciprocal the first
+// version carried.  fp32: v_rsq_f32 (one ulp) and one Newton step.
 template <typename T> struct PivotChain {
-    T d, y, e, rcp;
-    static constexpr int NOPS = sizeof(T) == 8 ? 5 : 3;
+    T d, h, y, t, e, p, q, r;
+    static constexpr int NOPS = sizeof(T) == 8 ? 6 : 4;
+    __device__ __forceinline__ void start(T d_) {             // (h: fp32 only, off the chain)
+        d = d_;
+        h = (T)0.5 * d_;
+    }
     __device__ __forceinline__ void finish_from(int n0) {     // operations n0 .. NOPS - 1 on their own (short columns)
         if constexpr (sizeof(T) == 8) {
-            if (n0 <= 0) y = __builtin_amdgcn_rcp((double)d);
-            if (n0 <= 1) e = fma(-d, y, (T)1);
-            if (n0 <= 2) y = fma(y, e, y);
-            if (n0 <= 3) e = fma(-d, y, (T)1);
-            if (n0 <= 4) rcp = fma(y, e, y);
+            if (n0 <= 0) y = __builtin_amdgcn_rsq((double)d);
+            if (n0 <= 1) t = d * y;
+            if (n0 <= 2) e = fma(-t, y, (T)1);
+            if (n0 <= 3) p = fma(e, (T)0.375, (T)0.5);
+            if (n0 <= 4) q = e * p;
+            if (n0 <= 5) r = fma(y, q, y);
         } else {
-            if (n0 <= 0) y = __builtin_amdgcn_rcpf((float)d);
-            if (n0 <= 1) e = fma(-d, y, (T)1);
-            if (n0 <= 2) rcp = fma(y, e, y);
+            if (n0 <= 0) y = __builtin_amdgcn_rsqf((float)d);
+            if (n0 <= 1) t = h * y;
+            if (n0 <= 2) e = fma(-t, y, (T)0.5);
+            if (n0 <= 3) r = fma(y, e, y);
         }
     }
 };
-template <typename T, int J, int N> struct PanelColumn {
+template <typename T, int C, int N> struct PanelColumn {       // column C (= the lane of the row that holds its second factor)
     static __device__ __forceinline__ void run(T &a, T &g, T ta, T tg, PivotChain<T> &nx) {
         if constexpr (sizeof(T) == 8) {
             if constexpr (N == 0)
-                asm volatile("v_rcp_f64 %[y], %[d]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [y] "=&v"(nx.y) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [j] "n"(J));
-            else if constexpr (N == 1 || N == 3)
-                asm volatile("v_fma_f64 %[e], -%[d], %[y], 1.0\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [e] "=&v"(nx.e) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [y] "v"(nx.y), [j] "n"(J));
+                asm volatile("v_rsq_f64 %[y], %[d]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [y] "=&v"(nx.y) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [c] "n"(C));
+            else if constexpr (N == 1)
+                asm volatile("v_mul_f64 %[t], %[d], %[y]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [t] "=&v"(nx.t) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [y] "v"(nx.y), [c] "n"(C));
             else if constexpr (N == 2)
-                asm volatile("v_fma_f64 %[y], %[y], %[e], %[y]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [y] "+v"(nx.y) : [ta] "v"(ta), [tg] "v"(tg), [e] "v"(nx.e), [j] "n"(J));
+                asm volatile("v_fma_f64 %[e], -%[t], %[y], 1.0\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [e] "=&v"(nx.e) : [ta] "v"(ta), [tg] "v"(tg), [t] "v"(nx.t), [y] "v"(nx.y), [c] "n"(C));
+            else if constexpr (N == 3)
+                asm volatile("v_fma_f64 %[p], %[e], %[k], 0.5\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [p] "=&v"(nx.p) : [ta] "v"(ta), [tg] "v"(tg), [e] "v"(nx.e), [k] "v"((T)0.375), [c] "n"(C));
             else if constexpr (N == 4)
-                asm volatile("v_fma_f64 %[r], %[y], %[e], %[y]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [r] "=&v"(nx.rcp) : [ta] "v"(ta), [tg] "v"(tg), [y] "v"(nx.y), [e] "v"(nx.e), [j] "n"(J));
+                asm volatile("v_mul_f64 %[q], %[e], %[p]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [q] "=&v"(nx.q) : [ta] "v"(ta), [tg] "v"(tg), [e] "v"(nx.e), [p] "v"(nx.p), [c] "n"(C));
+            else if constexpr (N == 5)
+                asm volatile("v_fma_f64 %[r], %[y], %[q], %[y]\n\t" DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g), [r] "=&v"(nx.r) : [ta] "v"(ta), [tg] "v"(tg), [y] "v"(nx.y), [q] "v"(nx.q), [c] "n"(C));
             else
-                asm volatile(DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g) : [ta] "v"(ta), [tg] "v"(tg), [j] "n"(J));
+                asm volatile(DPGP_FMAC2_F64 : [a] "+v"(a), [g] "+v"(g) : [ta] "v"(ta), [tg] "v"(tg), [c] "n"(C));
         } else {
             if constexpr (N == 0)
-                asm volatile("v_rcp_f32 %[y], %[d]\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [y] "=&v"(nx.y) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [j] "n"(J));
+                asm volatile("v_rsq_f32 %[y], %[d]\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [y] "=&v"(nx.y) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [c] "n"(C));
             else if constexpr (N == 1)
-                asm volatile("v_fma_f32 %[e], -%[d], %[y], 1.0\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [e] "=&v"(nx.e) : [ta] "v"(ta), [tg] "v"(tg), [d] "v"(nx.d), [y] "v"(nx.y), [j] "n"(J));
+                asm volatile("v_mul_f32 %[t], %[h], %[y]\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [t] "=&v"(nx.t) : [ta] "v"(ta), [tg] "v"(tg), [h] "v"(nx.h), [y] "v"(nx.y), [c] "n"(C));
             else if constexpr (N == 2)
-                asm volatile("v_fma_f32 %[r], %[y], %[e], %[y]\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [r] "=&v"(nx.rcp) : [ta] "v"(ta), [tg] "v"(tg), [y] "v"(nx.y), [e] "v"(nx.e), [j] "n"(J));
+                asm volatile("v_fma_f32 %[e], -%[t], %[y], 0.5\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [e] "=&v"(nx.e) : [ta] "v"(ta), [tg] "v"(tg), [t] "v"(nx.t), [y] "v"(nx.y), [c] "n"(C));
+            else if constexpr (N == 3)
+                asm volatile("v_fma_f32 %[r], %[y], %[e], %[y]\n\t" DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g), [r] "=&v"(nx.r) : [ta] "v"(ta), [tg] "v"(tg), [y] "v"(nx.y), [e] "v"(nx.e), [c] "n"(C));
             else
-                asm volatile(DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g) : [ta] "v"(ta), [tg] "v"(tg), [j] "n"(J));
+                asm volatile(DPGP_FMAC2_F32 : [a] "+v"(a), [g] "+v"(g) : [ta] "v"(ta), [tg] "v"(tg), [c] "n"(C));
         }
     }
 };
-// column J + 1 of pivot J, then the next pivot d = (updated) g[J + 1] of lane J + 1, broadcast to the row of lanes
+// column J + 1 of pivot J, then the next pivot d = (updated) g[J + 1] of lane J + 1, broadcast to the row of lanes.  The first
+// statement of a pivot step: tg has just been written by a vector instruction of the compiler's, and is read by DPP here.
 template <typename T, int J> struct PanelNextPivot {
     static __device__ __forceinline__ T run(T &a, T &g, T ta, T tg) {
         T d;
         if constexpr (sizeof(T) == 8)
-            asm volatile(DPGP_FMAC2_F64 "\n\ts_nop 1\n\tv_mov_b64_dpp %[d], %[g] row_newbcast:%[j1] row_mask:0xf bank_mask:0xf"
-                         : [a] "+v"(a), [g] "+v"(g), [d] "=&v"(d) : [ta] "v"(ta), [tg] "v"(tg), [j] "n"(J), [j1] "n"(J + 1));
+            asm volatile("s_nop 1\n\t" DPGP_FMAC2_F64 "\n\ts_nop 1\n\tv_mov_b64_dpp %[d], %[g] row_newbcast:%[c] row_mask:0xf bank_mask:0xf"
+                         : [a] "+v"(a), [g] "+v"(g), [d] "=&v"(d) : [ta] "v"(ta), [tg] "v"(tg), [c] "n"(J + 1));
         else
-            asm volatile(DPGP_FMAC2_F32 "\n\ts_nop 1\n\tv_mov_b32_dpp %[d], %[g] row_newbcast:%[j1] row_mask:0xf bank_mask:0xf"
-                         : [a] "+v"(a), [g] "+v"(g), [d] "=&v"(d) : [ta] "v"(ta), [tg] "v"(tg), [j] "n"(J), [j1] "n"(J + 1));
+            asm volatile("s_nop 1\n\t" DPGP_FMAC2_F32 "\n\ts_nop 1\n\tv_mov_b32_dpp %[d], %[g] row_newbcast:%[c] row_mask:0xf bank_mask:0xf"
+                         : [a] "+v"(a), [g] "+v"(g), [d] "=&v"(d) : [ta] "v"(ta), [tg] "v"(tg), [c] "n"(J + 1));
         return d;
     }
 };
@@ -408,10 +412,10 @@ template <typename T, int J, int NOP> __device__ __forceinline__ T row_bcast(T v
     return r;
 }
 
-// Pivots J .. 15 of one block column held one matrix row per lane, in the square-root-free (L D L^T) form: g = this lane's
-// copy of row (lane & 15) of the diagonal tile (full symmetric row; every row of 16 lanes holds the whole tile), a = the
-// lane's own row below the tile.  pc: the finished chain of pivot J.  dsel collects pivot (lane & 15) on each lane.  On exit
-// g[j] / a[j] hold column j of the Schur complement at pivot j: the entries of L are those times rsqrt(d_j) (the caller's).
+// Pivots J .. 15 of one block column held one matrix row per lane: g = this lane's copy of row (lane & 15) of the diagonal
+// tile (full symmetric row; every row of 16 lanes holds the whole tile), a = the lane's own row below the tile.  pc: the
+// finished chain of pivot J.  dsel collects pivot (lane & 15) on each lane.  On exit g[j] / a[j] hold column j of L (for
+// j <= lane & 15 in g; what g holds above the diagonal means nothing).
 // Which chain operation rides in front of the q-th of the 14 - J columns behind the next pivot's: every other column while
 // there is room (an asm statement that reads what the statement directly before it wrote gets a conservative s_nop from the
 // compiler), every column otherwise; 99 = none.
@@ -427,32 +431,25 @@ template <typename T> constexpr int panel_chain_placed(int J) {
 template <typename T, int J, int C> struct PanelColumns {       // columns C .. 15 of pivot J
     static __device__ __forceinline__ void run(T (&g)[16], T (&a)[16], T ta, T tg, PivotChain<T> &nx) {
         if constexpr (C < 16) {
-            PanelColumn<T, J, panel_chain_op<T>(J, C - J - 2)>::run(a[C], g[C], ta, tg, nx);   // (reads row J of the tile before changing its own)
+            PanelColumn<T, C, panel_chain_op<T>(J, C - J - 2)>::run(a[C], g[C], ta, tg, nx);
             PanelColumns<T, J, C + 1>::run(g, a, ta, tg, nx);
         }
     }
 };
 template <typename T, int J> struct PanelStep {
     static __device__ __forceinline__ void run(T (&g)[16], T (&a)[16], const PivotChain<T> &pc, T &dsel, int li) {
+        const T tg = g[J] * pc.r, ta = a[J] * pc.r;           // column J of L for the lane's two rows: S_iJ / sqrt(d_J)
+        g[J] = tg;
+        a[J] = ta;
         if constexpr (J < 15) {
-            const T tg = g[J] * pc.rcp, ta = a[J] * pc.rcp;   // multipliers a_iJ / d_J of the two rows
-            // the next pivot's column first, so that its reciprocal is under way while the other columns are updated
+            // the next pivot's column first, so that its reciprocal root is under way while the other columns are updated
             PivotChain<T> nx;
-            nx.d = PanelNextPivot<T, J>::run(a[J + 1], g[J + 1], ta, tg);
+            nx.start(PanelNextPivot<T, J>::run(a[J + 1], g[J + 1], ta, tg));
             dsel = (li == J + 1) ? nx.d : dsel;
             PanelColumns<T, J, J + 2>::run(g, a, ta, tg, nx);
             nx.finish_from(panel_chain_placed<T>(J));         // what the remaining columns had no room for
             PanelStep<T, J + 1>::run(g, a, nx, dsel, li);
         }
-    }
-};
-// g[j], a[j] *= r[lane j of the row]   (r = rsqrt of the pivots, one per lane)
-template <typename T, int J> struct PanelScale {
-    static __device__ __forceinline__ void run(T (&g)[16], T (&a)[16], T r) {
-        const T rj = row_bcast<T, J, J == 0>(r);
-        g[J] *= rj;
-        a[J] *= rj;
-        if constexpr (J < 15) PanelScale<T, J + 1>::run(g, a, r);
     }
 };
 
@@ -654,8 +651,8 @@ __device__ __forceinline__ void potrf_lds_update(T *tiles, T *dummy, int nbf, in
 // Right-looking over block columns of 16, with a look-ahead of one block column:
 //   PANEL k (registers, one matrix row per lane): every row of 16 lanes holds the 16 rows of the diagonal tile (full symmetric
 //     rows, redundantly) and every lane one row below it (64 per wave; the border vectors are rows like any other).  Pivot j:
-//     each lane scales its own entries of column j by 1/d and updates its two rows with one v_fmac_f64 per column whose
-//     second factor — the entry of row j of the tile — comes from lane j of its own row of lanes by DPP.  The rows come out
+//     each lane scales its own entries of column j by 1/sqrt(d) and updates its two rows with one v_fmac_f64 per column c whose
+//     second factor — the scaled entry (c, j) of the tile — comes from lane c of its own row of lanes by DPP.  The rows come out
 //     as L_kk and A_Ik L_kk^-T: no inverse of the diagonal tile, no panel product, no cross-wave traffic.
 //     (Round 2 factored + inverted the diagonal tile on one wave with v_readlane broadcasts — 3.7 us of the 5-6 us per
 //     step — and formed the panel with that inverse on the matrix pipe.)
@@ -684,15 +681,14 @@ __device__ __forceinline__ int potrf_lds_panel(T *tiles, T *border, int nbf, int
         }
         asm volatile("s_nop 4");                              // (EXEC restored by the predicated loads -> DPP)
         PivotChain<T> pc;
-        pc.d = row_bcast<T, 0, 0>(g[0]);
+        pc.start(row_bcast<T, 0, 0>(g[0]));
         T dsel = pc.d;                                        // lane li ends up with pivot li
         pc.finish_from(0);
         PanelStep<T, 0>::run(g, a, pc, dsel, li);
         // non-positive (or NaN) pivots: found once per tile from the 16 collected pivots; the factorisation runs on (its
-        // numbers mean nothing from there on; the callers report info and poison the results)
+        // numbers are NaN from there on; the callers report info and poison the results)
         const unsigned long long nonpos = __builtin_amdgcn_ballot_w64(!(dsel > (T)0)) & 0xffffull;
         bad = nonpos ? __builtin_ctzll(nonpos) + 1 : 0;
-        PanelScale<T, 0>::run(g, a, pivot_rsqrt(dsel));
         if (rowp) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) rowp[c] = a[c];

@@ -3,7 +3,8 @@
 // M = 512).  Per panel step k, for all B matrices at once:
 //   1. diag   (B workgroups)              : L_kk = chol(A_kk) (128 x 128) and W_kk = L_kk^-1, LDS-resident (potrf_lds +
 //                                           trtri_lds); a launch of its own only for k = 0 (see 3.)
-//   2. panel  (B x row blocks x 2)        : P_i = A_ik W_kk^T for the 64-row blocks below, into a panel buffer
+//   2. panel  (B x row blocks x 2)        : P_i = A_ik W_kk^T for the 64-row blocks below, into a panel buffer, then
+//      refine (B x row blocks)            : P_i += (A_ik - P_i L_kk^T) W_kk^T, which takes cond(L_kk) out of the backward error
 //   3. update (B x lower pairs of blocks) : A_IJ -= P_I P_J^T (128 x 128 x 128 MFMA block products), the trailing update.
 //                                           The workgroup that owns the NEXT diagonal 128 x 128 block updates it and factors
 //                                           + inverts it right away (look-ahead: the ~90 us of that latency-bound step
@@ -144,6 +145,77 @@ __global__ __launch_bounds__(256, 2) void pbig_panel(int Mw, int k, const T *__r
     pbig_store<T>(pbuf + ((size_t)b * Mw + RB * i) * PW + RB * c, PW, acc);
 }
 
+// a 64 x 64 block of L_kk out of the matrix: a diagonal one (lower != 0) has the entries above its diagonal read as zero (what the
+// array holds there is A's upper triangle, which is never read)
+template <typename T> __device__ __forceinline__ void pbig_stage_lower(const T *__restrict__ g, int ld, T *__restrict__ s, int lower) {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    for (int e = threadIdx.x; e < RB * RB / 4; e += 256) {
+        const int r = e >> 4, c4 = (e & 15) * 4;
+        const t4 v = *reinterpret_cast<const t4 *>(g + (size_t)r * ld + c4);
+        T *d = s + r * RB_LD + c4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = (lower && c4 + q > r) ? (T)0 : v[q];
+    }
+}
+
+// step 2b: one step of iterative refinement of the 64 panel rows of row block i,  P += (A_ik - P L_kk^T) W_kk^T.  The product with
+// the explicit inverse alone leaves |P L_kk^T - A_ik| ~ cond(L_kk) u |P| |L_kk^T|: on the grams with jitter 1e-8 that the models factor
+// (cond(L_kk) ~ 1e5) componentwise backward errors of 1e5 .. 6e7 u, i.e. up to the size of the jitter itself
+// (tests/test_gpu_dense_edges.py, P3).  After the step what remains is the rounding of the residual, a small multiple of u |P| |L_kk^T|.
+// Both products use the triangular structure in 64 x 64 blocks (three of four each): 1.5 x the flops of step 2.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void pbig_panel_refine(int Mw, int k, const T *__restrict__ w, const T *__restrict__ winv,
+                                                            T *__restrict__ pbuf) {
+    typedef typename Mfma<T>::acc_t acc_t;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T *xs = reinterpret_cast<T *>(smem_raw), *ys = xs + RB * RB_LD;
+    const int b = blockIdx.x, i = blockIdx.y;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15;
+    const T *Wb = w + (size_t)b * Mw * Mw;
+    const T *Aik = Wb + (size_t)(PW * (k + 1) + RB * i) * Mw + PW * k;
+    const T *Lkk = Wb + (size_t)(PW * k) * Mw + PW * k;
+    const T *Wk = winv + (size_t)b * PW * PW;
+    T *Pi = pbuf + ((size_t)b * Mw + RB * i) * PW;
+    acc_t r[2][4];
+    // R = A_ik - P L_kk^T, column half c: the K halves h <= c (L_kk is lower triangular)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+#pragma unroll
+        for (int J = 0; J < 4; ++J)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) r[c][J][v] = Aik[(size_t)(16 * wv + Mfma<T>::row(lane, v)) * Mw + RB * c + 16 * J + li];
+#pragma unroll
+        for (int h = 0; h <= c; ++h) {
+            __syncthreads();
+            pbig_stage<T>(Pi + RB * h, PW, xs);
+            pbig_stage_lower<T>(Lkk + (size_t)(RB * c) * Mw + RB * h, Mw, ys, c == h);
+            __syncthreads();
+            pbig_mma_half<T>(xs, ys, r[c], (T)-1);
+        }
+    }
+    // P += R W_kk^T, column half c: the K halves h <= c (W_kk is lower triangular, with explicit zeros above its diagonal)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        acc_t d[4];
+#pragma unroll
+        for (int J = 0; J < 4; ++J)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) d[J][v] = Pi[(size_t)(16 * wv + Mfma<T>::row(lane, v)) * PW + RB * c + 16 * J + li];
+#pragma unroll
+        for (int h = 0; h <= c; ++h) {
+            __syncthreads();
+#pragma unroll
+            for (int J = 0; J < 4; ++J)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) xs[(16 * wv + Mfma<T>::row(lane, v)) * RB_LD + 16 * J + li] = r[h][J][v];
+            pbig_stage<T>(Wk + (size_t)(RB * c) * PW + RB * h, PW, ys);
+            __syncthreads();
+            pbig_mma_half<T>(xs, ys, d, (T)1);
+        }
+        pbig_store<T>(Pi + RB * c, PW, d);
+    }
+}
+
 // one 128 x 128 trailing block: A_IJ -= P_I P_J^T, K = 128 staged in four quarters of 32 through LDS; every wave owns 32
 // rows x 128 columns of the block in registers (16 result tiles).  128 x 128 rather than 64 x 64 per workgroup: the panel
 // rows are fetched from memory once per 128 x 128 block (8 flops per byte moved instead of 5.5; the 64 x 64 version ran at
@@ -269,6 +341,8 @@ int launch_potrf_big(int B, int M, T *a, int *info, T *ws, hipStream_t st) {
                             (int)lds_diag) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(pbig_panel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_blk) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(pbig_panel_refine<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds_blk) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(pbig_update<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_upd) != hipSuccess)
         return DPGP_ERR_LAUNCH;
@@ -283,6 +357,9 @@ int launch_potrf_big(int B, int M, T *a, int *info, T *ws, hipStream_t st) {
     for (int k = 0; k + 1 < nblk; ++k) {
         const int nrb = (Mw - PW * (k + 1)) / RB;                 // 64-row blocks below the panel (even, >= 2)
         DPGP_PRELAUNCH(); hipLaunchKernelGGL((pbig_panel<T>), dim3(B, nrb, PW / RB), dim3(256), lds_blk, st, Mw, k, (const T *)w, (const T *)winv,
+                           pbuf);
+        DPGP_LAUNCH_CHECK();
+        DPGP_PRELAUNCH(); hipLaunchKernelGGL((pbig_panel_refine<T>), dim3(B, nrb), dim3(256), lds_blk, st, Mw, k, (const T *)w, (const T *)winv,
                            pbuf);
         DPGP_LAUNCH_CHECK();
         const int nub = nrb / 2;                                   // 128-row blocks below the panel

@@ -47,13 +47,26 @@ static size_t pp_lds_bytes() {
 
 // ---- (c) one wave, one 16-row tile I below the diagonal block: S (staging, [16][PP_SLD]) holds A_Ik on entry and P_I on exit
 // (INPLACE: the inverted diagonal tiles sit in the diagonal slots of `tiles` themselves, linv unused)
-template <bool INPLACE = false>
-__device__ __forceinline__ void pp_trsm_tile(double *S, const double *tiles, const double *linv, int lane) {
+// REFINE: one step of iterative refinement per tile column, x += L_cc^-1 (a - L_cc x).  The product with the explicit inverse of a
+// diagonal tile alone leaves |L_cc x - a| ~ cond(L_cc) u |L_cc| |x|: 3e2 .. 8e3 u of componentwise backward error in the factor of a
+// gram with jitter 1e-8 (tests/test_gpu_dense_edges.py, P4); after the step what remains is the rounding of the residual.  L_cc
+// (zeros above its diagonal) comes from the LDS tiles, or (INPLACE: they hold the inverses) from the stored factor Lg (row stride
+// ldg; tile c at Lg + 16 c (ldg + 1)), which the caller has made visible to the workgroup.
+template <bool INPLACE = false, bool REFINE = false>
+__device__ __forceinline__ void pp_trsm_tile(double *S, const double *tiles, const double *linv, int lane, const double *Lg = nullptr,
+                                             int ldg = 0) {
     typedef f64x4 acc_t;
     const int li = lane & 15, kk = lane >> 4;
     acc_t X[PP_NT];
 #pragma unroll
     for (int c = 0; c < PP_NT; ++c) {
+        double lc[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (REFINE) {                                                             // (early: the loads land beneath the products below)
+            const double *lp = INPLACE ? Lg + (size_t)(16 * c + li) * ldg + 16 * c + kk
+                                       : tiles + lds_tile_index(c, c, PP_NT) * TSZ + li * LDT + kk;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) lc[ks] = lp[4 * ks];
+        }
         acc_t a;
 #pragma unroll
         for (int v = 0; v < 4; ++v) a[v] = S[li * PP_SLD + 16 * c + 4 * v + kk];          // (A_Ic)^T in the accumulator layout
@@ -70,6 +83,13 @@ __device__ __forceinline__ void pp_trsm_tile(double *S, const double *tiles, con
         acc_t x = {0, 0, 0, 0};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) x = __builtin_amdgcn_mfma_f64_16x16x4f64(iv[4 * ks], a[ks], x, 0, 0, 0);
+        if constexpr (REFINE) {
+            acc_t r = a;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) r = __builtin_amdgcn_mfma_f64_16x16x4f64(-lc[ks], x[ks], r, 0, 0, 0);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) x = __builtin_amdgcn_mfma_f64_16x16x4f64(iv[4 * ks], r[ks], x, 0, 0, 0);
+        }
         X[c] = x;
 #ifdef PP_DEBUG_NOPS
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -160,7 +180,7 @@ __global__ __launch_bounds__(256) void pbig_persistent_kernel(int Mw, double *__
                     for (int q = 0; q < 16; ++q)
                         pre[q] = *reinterpret_cast<const pp_f2 *>(Pk + (size_t)(16 * (I + 4) + q) * Mw + 2 * lane);
                 }
-                pp_trsm_tile(S, tiles, linv, lane);
+                pp_trsm_tile<false, true>(S, tiles, linv, lane);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const pp_f2 v = {S[q * PP_SLD + 2 * lane], S[q * PP_SLD + 2 * lane + 1]};
@@ -443,6 +463,7 @@ __global__ __launch_bounds__(256) void pleft_persistent_kernel(int Mw, double *_
             double *tc = tiles + lds_tile_index(c, c, PP_NT) * TSZ;
             tri_inverse_dpp<double>(tc, tc, LDT, lane);
         }
+        __threadfence_block();                                         // (L_kk, stored above, is read back by the refinement of the solve)
         __syncthreads();
         PP_STAMP(8 * k + 3);
         // ---- the blocks below: up to date in the accumulators, solved through the staging tile, stored once ----
@@ -482,7 +503,7 @@ __global__ __launch_bounds__(256) void pleft_persistent_kernel(int Mw, double *_
 #pragma unroll
                         for (int v = 0; v < 4; ++v) S[(kk + 4 * v) * PP_SLD + 16 * Jt + li] = acc[i][Jt][v];
                 }
-                pp_trsm_tile<true>(S, tiles, nullptr, lane);
+                pp_trsm_tile<true, true>(S, tiles, nullptr, lane, Akk, Mw);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const pp_f2 v = {S[q * PP_SLD + 2 * lane], S[q * PP_SLD + 2 * lane + 1]};
@@ -506,7 +527,7 @@ __global__ __launch_bounds__(256) void pleft_persistent_kernel(int Mw, double *_
 //   (d) X_IJ -= L_Ik X_kJ for the blocks I > k, J <= k: the update loop of the factorisation with the A operand chunk from L
 //       (negated) and the B operand chunk [32][128] from block row k of X (row-major in k: no transposition).
 // Used by the fused ELBO for M > 128 (chain_big.hip): only |X|_F^2 leaves the kernel (nrm2[b]); X itself is scratch (the
-// last block row is not even stored).  L[B][Mw][Mw] read-only (lower + zeros), X[B][Mw][Mw] in/out.
+// last block row is not even stored).  L[B][Mw][Mw] read-only (its lower triangle: nothing above the diagonal is read), X[B][Mw][Mw] in/out.
 #define PT_YLD 144                 // row stride of a staged [32][128] chunk of X: lanes (kk, li) of an operand read hit 64 banks
 static size_t pt_lds_bytes() {
     const size_t fact = LA_LDS_HDR + sizeof(double) * ((size_t)TSZ * (PP_NT * (PP_NT + 1) / 2 + PP_NT) + (size_t)4 * 16 * PP_SLD);
@@ -545,8 +566,9 @@ __global__ __launch_bounds__(256) void ptrsm_persistent_kernel(int Mw, const dou
             while (I * (I + 1) / 2 > tt) --I;
             const int J = tt - I * (I + 1) / 2;
             const pp_f2 v = *reinterpret_cast<const pp_f2 *>(Lkk + (size_t)(16 * I + r) * Mw + 16 * J + c2);
-            tiles[tt * TSZ + r * LDT + c2] = v[0];
-            tiles[tt * TSZ + r * LDT + c2 + 1] = v[1];
+            // (whatever the caller's array holds above the diagonal is not read: tf.matrix_triangular_solve's contract)
+            tiles[tt * TSZ + r * LDT + c2] = (I == J && c2 > r) ? 0.0 : v[0];
+            tiles[tt * TSZ + r * LDT + c2 + 1] = (I == J && c2 + 1 > r) ? 0.0 : v[1];
         }
         __syncthreads();
         // ---- (b) inverted diagonal tiles ----
