@@ -55,6 +55,21 @@ extern "C" int dpgp_elbo_workspace_layout(int D, int N, int M, int Q, int prec, 
     return DPGP_OK;
 }
 
+// What the front launch of a finished dpgp_elbo_fhat[_ex] call left inside `ws`: out[6] = { byte offset of K_uu + jitter I of
+// output dim 0 ([Mp][Mp], the square [0, M) x [0, M) written), byte stride between output dims, element size (4 or 8), Mp, byte
+// offset of the pair factors alpha^2 exp(-1/4 r^2) of the pair-tile psi2 kernel (fp32 [D][Ppad], pair (m, m'), m' <= m, at
+// m (m + 1) / 2 + m'; DPGP_ALGO_AUTO), Ppad -- 0 where that kernel does not run (fp64 Psi2, more than 21 latent dims) }
+extern "C" int dpgp_elbo_workspace_front_layout(int D, int N, int M, int Q, int prec, size_t *out) {
+    if (D <= 0 || N <= 0 || M <= 0 || Q <= 0 || prec < 0 || prec > 2) return -1;
+    if (!out) return -6;
+    const ElboLayout L = elbo_layout(D, N, M, Q, prec);
+    const size_t sl = (prec == DPGP_PREC_F32) ? 4 : 8;
+    out[0] = L.off_la; out[1] = sl * la_chain_ws_elems(M); out[2] = sl; out[3] = (size_t)L.Mp;
+    out[4] = L.off_sc;
+    out[5] = (prec != DPGP_PREC_F64 && psi2_pairs_ksteps(Q) <= 8) ? (size_t)psi2_consts_layout(M, Q).Ppad : 0;
+    return DPGP_OK;
+}
+
 // A forked second stream is joined on EVERY way out: an error return between fork and join would otherwise leave work in flight on
 // it that still writes the caller's workspace (and, inside a stream capture, an unjoined stream invalidates the capture).
 struct AuxJoin {
@@ -95,11 +110,16 @@ static int elbo_run(int D, int N, int M, int Q, const double *y, int ldy, const 
     hipEvent_t ev0 = ex ? (hipEvent_t)ex->ev_psi2_begin : nullptr, ev1 = ex ? (hipEvent_t)ex->ev_psi2_end : nullptr;
     int rc;
     // one front launch: KL, y'y, the z-only constants of the psi kernels (incl. the pair image), K_uu + jitter I and — for
-    // the pair-tile psi2 kernel — its per-(output dim, pair) scale table
+    // the pair-tile psi2 kernel — its per-(output dim, pair) scale table.  Forward evaluation: the K_uu blocks write the table from
+    // the squared distances they hold (the pair index m (m + 1) / 2 + m' is the packed lower triangle: a row of a K_uu tile is a
+    // run of the table).  Training step (pgws): extra blocks build it from fp32 distances as before, so that the step's Psi2 and
+    // gradients stay bit for bit what they were.
     const bool pairs_psi2 = (sizeof(TP) == 4 && algo == DPGP_ALGO_AUTO && psi2_pairs_ksteps(Q) <= 8);
+    const bool fac_from_gram = pairs_psi2 && pgws == nullptr;       // (the factors come from the K_uu blocks)
     float *pscale = reinterpret_cast<float *>(ws + L.off_sc);
     if ((rc = launch_elbo_front<TL>(N, Q, mu, s, klp, D, y, ldy, yy, z, M, pconst, gamma, alpha, beta, jitter, la, L.Mp,
-                                    la_chain_ws_elems(M), pairs_psi2 ? pscale : nullptr, st)))
+                                    la_chain_ws_elems(M), (pairs_psi2 && !fac_from_gram) ? pscale : nullptr,
+                                    fac_from_gram ? pscale : nullptr, st)))
         return rc;
     // Psi1^T y needs only the front launch and feeds only the chain: with a second stream in `exec` it runs beside the psi2
     // launch instead of in front of it (12 us of the per-GPU share at D = 64)

@@ -11,12 +11,30 @@
 //   16-byte (fp32) / 32-byte (fp64) store -> 256 B contiguous per 16 lanes.
 // ---------------------------------------------------------------------------------------------------------------
 #define GRAM_T 64
-template <typename TIN, typename T>
+// The pair factor of the pair-tile psi2 kernel (psi2_pairs.hip), alpha^2 exp2(-1/4 log2e r^2), from the squared distance r^2 a
+// gram thread holds.  fp64 r^2: the exponent is split in fp64 into its integer part and a fraction in [-1/2, 1/2], so that the
+// one rounding to fp32 is of the fraction (2^-26 absolute) and not of an exponent as large as 126 (2^-18): the factor is good
+// to the v_exp_f32 result and the product's rounding at every distance, and underflows gradually through v_ldexp_f32.
+template <typename T> __device__ __forceinline__ float gram_pair_factor(float al2, T acc) {
+    if constexpr (sizeof(T) == 8) {
+        double x = (-0.25 * DPGP_LOG2E) * acc;
+        x = x < -300.0 ? -300.0 : x;                           // (a NaN stays one)
+        const double n = rint(x);
+        return ldexpf(al2 * __builtin_amdgcn_exp2f((float)(x - n)), (int)n);
+    } else {
+        return al2 * exp2f((float)(-0.25 * DPGP_LOG2E) * acc);
+    }
+}
+// FRONT (the K_uu tiles of the fused ELBO's front launch, i0 >= j0 only): a tile below the diagonal is also stored transposed
+// into the upper position -- bit for bit what a tile computed there holds, d * d being the same for (a - c) and (c - a) and
+// the order of the latent dims the same -- and with pair_fac != nullptr every row also writes its pair factors j <= i into the
+// pair kernel's scale table (fp32, [b][fac_stride], pair index i (i + 1) / 2 + j: psi2_consts.h).
+template <typename TIN, typename T, bool FRONT = false>
 __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1, int Q, const TIN *__restrict__ x0,
                                           const TIN *__restrict__ x1, const TIN *__restrict__ gamma,
                                           const TIN *__restrict__ alpha, const TIN *__restrict__ beta, int flags, T jitter,
                                           T *__restrict__ out, int ld_out, size_t batch_stride, int symmetric,
-                                          unsigned char *smem_raw) {
+                                          unsigned char *smem_raw, float *__restrict__ pair_fac = nullptr, size_t fac_stride = 0) {
     // both input tiles in LDS, pre-scaled by sqrt(gamma_b), TRANSPOSED: [Q][64], so that a thread's four rows / columns of
     // one latent dim are ONE 16-byte (fp32) read instead of four 4-byte ones (round 2: [64][Q + 1], eight ds_read_b32 per 32
     // vector instructions — the LDS pipe, not the vector unit or HBM, held the 1 GB gram at 4.1 TB/s)
@@ -67,6 +85,7 @@ __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1,
     const T noise = add_noise ? (T)1 / (T)beta[b] : (T)0;
     const T scale = (T)(-0.5 * DPGP_LOG2E);
     T *ob = out + (size_t)b * batch_stride;
+    T vt[FRONT ? 4 : 1][4];                                     // FRONT: the patch, kept for the transposed store
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         int i = i0 + ty * 4 + r;
@@ -80,8 +99,27 @@ __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1,
                 if (add_noise) v[c] += noise;
                 if (add_jitter) v[c] += jitter;
             }
+            if constexpr (FRONT) vt[r][c] = v[c];
         }
         int j = j0 + tx * 4;
+        if constexpr (FRONT) {
+            if (pair_fac != nullptr && j <= i) {
+                const float al2 = (float)(al * al);
+                typedef float fvec4u __attribute__((ext_vector_type(4), aligned(4)));
+                fvec4u f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) f[c] = gram_pair_factor<T>(al2, acc[r][c]);
+                // pair (i, j), j <= i, is entry i (i + 1) / 2 + j of the table: the four columns are one run of it (4-byte aligned)
+                float *pf = pair_fac + (size_t)b * fac_stride + (size_t)i * (i + 1) / 2 + j;
+                if (j + 3 <= i) {
+                    *reinterpret_cast<fvec4u *>(pf) = f;
+                } else {                                        // (across the diagonal: the run ends with the row)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (j + c <= i) pf[c] = f[c];
+                }
+            }
+        }
         T *p = ob + (size_t)i * ld_out + j;
         if (j + 3 < N1 && ((ld_out & 3) == 0)) {
             vec4 vv = {v[0], v[1], v[2], v[3]};
@@ -91,6 +129,25 @@ __device__ __forceinline__ void gram_tile(int b, int i0, int j0, int N0, int N1,
 #pragma unroll
             for (int c = 0; c < 4; ++c)
                 if (j + c < N1) p[c] = v[c];
+        }
+    }
+    if constexpr (FRONT) {
+        if (i0 != j0) {                                         // column c of the patch = four consecutive entries of row j0 + 4 tx + c
+            const int i = i0 + ty * 4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int j = j0 + tx * 4 + c;
+                if (j >= N1 || i >= N0) continue;
+                T *p = ob + (size_t)j * ld_out + i;
+                if (i + 3 < N0 && ((ld_out & 3) == 0)) {
+                    vec4 vv = {vt[0][c], vt[1][c], vt[2][c], vt[3][c]};
+                    *reinterpret_cast<vec4 *>(p) = vv;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (i + r < N0) p[r] = vt[r][c];
+                }
+            }
         }
     }
 }
@@ -618,7 +675,7 @@ __global__ __launch_bounds__(256) void elbo_front_kernel(int N, int Q, const dou
                                                          const double *__restrict__ gamma, const double *__restrict__ alpha,
                                                          const double *__restrict__ beta, TL jitter, TL *__restrict__ kuu,
                                                          int ld_kuu, size_t kuu_stride, int first_scale_block,
-                                                         float *__restrict__ pair_scale) {
+                                                         float *__restrict__ pair_scale, float *__restrict__ pair_fac) {
     __shared__ double scratch[5][64];
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int blk = (int)blockIdx.x;
@@ -630,7 +687,8 @@ __global__ __launch_bounds__(256) void elbo_front_kernel(int N, int Q, const dou
         kl_yy_block<double>(blk, N, Q, mu, s, kl_out, D, y, ldy, yy_out, z, M, consts, first_consts_block, scratch);
         return;
     }
-    // K_uu tiles (fp64 vector work) and scale-table blocks (gather, exp, 17 MB of stores at config 3) are INTERLEAVED in dispatch
+    // Forward evaluation (pair_fac): no scale-table blocks, the K_uu blocks write the table themselves (gram_tile).  Training step
+    // (pair_scale): K_uu tiles (fp64 vector work) and scale-table blocks (gather, exp, 17 MB of stores at config 3) are INTERLEAVED in dispatch
     // order: one after the other they took 22.9 + 20.9 us of the launch's 44 (scratch/front_roles.sh), neither filling the GPU's
     // other half.  Position i of the ng + ns blocks is a scale block iff floor((i + 1) ns / (ng + ns)) > floor(i ns / (ng + ns)).
     const int ng = first_scale_block - first_gram_block, nsb = (int)gridDim.x - first_scale_block;
@@ -653,35 +711,40 @@ __global__ __launch_bounds__(256) void elbo_front_kernel(int N, int Q, const dou
 #ifdef FRONT_DIAG_SKIP
     if (FRONT_DIAG_SKIP & 2) return;
 #endif
-    const int tm = (M + GRAM_T - 1) / GRAM_T, b = g / (tm * tm), r = g - b * tm * tm;
-    gram_tile<double, TL>(b, (r / tm) * GRAM_T, (r % tm) * GRAM_T, M, M, Q, z, z, gamma, alpha, beta, DPGP_FLAG_JITTER, jitter,
-                          kuu, ld_kuu, kuu_stride, 1, smem_raw);
+    // the tm (tm + 1) / 2 tiles on and below the diagonal of every output dim, row-major: r = ti (ti + 1) / 2 + tj, tj <= ti (a
+    // tile below the diagonal fills its mirror image too, gram_tile)
+    const int tm = (M + GRAM_T - 1) / GRAM_T, tl = tm * (tm + 1) / 2, b = g / tl, r = g - b * tl;
+    int ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= r) ++ti;
+    const int tj = r - ti * (ti + 1) / 2;
+    gram_tile<double, TL, true>(b, ti * GRAM_T, tj * GRAM_T, M, M, Q, z, z, gamma, alpha, beta, DPGP_FLAG_JITTER, jitter, kuu,
+                                ld_kuu, kuu_stride, 1, smem_raw, pair_fac, (size_t)psi2_consts_layout(M, Q).Ppad);
 }
 template <typename TL>
 int launch_elbo_front(int N, int Q, const double *mu, const double *s, double *kl_out, int D, const double *y, int ldy,
                       double *yy_out, const double *z, int M, unsigned char *psi2_consts, const double *gamma,
                       const double *alpha, const double *beta, double jitter, TL *kuu, int ld_kuu, size_t kuu_stride,
-                      float *pair_scale, hipStream_t st) {
+                      float *pair_scale, float *pair_fac, hipStream_t st) {
     int blocks = DPGP_KL_NBLK + dpgp_ceil_div(D, 64) * YY_NCH;
     const int first_consts = blocks;
     blocks += dpgp_ceil_div(M, 64) + dpgp_ceil_div(psi2_consts_layout(M, Q).Ppad, PSI2_PAIR_ROWS_PER_BLOCK);
     const int first_gram = blocks, tm = dpgp_ceil_div(M, GRAM_T);
-    blocks += D * tm * tm;
+    blocks += D * (tm * (tm + 1) / 2);                  // tiles on and below the diagonal (gram_tile mirrors the rest)
     const int first_scale = blocks;                     // pair_scale != nullptr: ceil(D / chunk) x ceil(Ppad / 256) more blocks
     if (pair_scale) blocks += dpgp_ceil_div(D, psi2_scale_dchunk(D)) * dpgp_ceil_div(psi2_consts_layout(M, Q).Ppad, 256);
     const size_t lds = sizeof(TL) * 2 * GRAM_T * (Q + 1);
     DPGP_PRELAUNCH(); hipLaunchKernelGGL((elbo_front_kernel<TL>), dim3(blocks), dim3(256), lds, st, N, Q, mu, s, kl_out, D, y, ldy, yy_out,
                        z, M, psi2_consts, first_consts, first_gram, gamma, alpha, beta, (TL)jitter, kuu, ld_kuu, kuu_stride,
-                       first_scale, pair_scale);
+                       first_scale, pair_scale, pair_fac);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;
 }
 template int launch_elbo_front<float>(int, int, const double *, const double *, double *, int, const double *, int, double *,
                                       const double *, int, unsigned char *, const double *, const double *, const double *,
-                                      double, float *, int, size_t, float *, hipStream_t);
+                                      double, float *, int, size_t, float *, float *, hipStream_t);
 template int launch_elbo_front<double>(int, int, const double *, const double *, double *, int, const double *, int, double *,
                                        const double *, int, unsigned char *, const double *, const double *, const double *,
-                                       double, double *, int, size_t, float *, hipStream_t);
+                                       double, double *, int, size_t, float *, float *, hipStream_t);
 
 template <typename TIN>
 int launch_kl_yy(int N, int Q, const TIN *mu, const TIN *s, double *kl_out, int D, const TIN *y, int ldy,

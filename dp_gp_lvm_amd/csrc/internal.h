@@ -37,7 +37,11 @@ template <typename TL>
 int launch_elbo_front(int N, int Q, const double *mu, const double *s, double *kl_out, int D, const double *y, int ldy,
                       double *yy_out, const double *z, int M, unsigned char *psi2_consts, const double *gamma,
                       const double *alpha, const double *beta, double jitter, TL *kuu, int ld_kuu, size_t kuu_stride,
-                      float *pair_scale, hipStream_t st);   // pair_scale != nullptr: also the pair-scale table (psi2_consts.h)
+                      float *pair_scale, float *pair_fac, hipStream_t st);
+// Only the K_uu tiles on and below the diagonal are computed; a tile below it is also stored transposed (the full square is
+// written).  The pair-scale table [D][Ppad] of the pair-tile psi2 kernel (psi2_consts.h), either way or not at all:
+// pair_scale != nullptr: extra blocks build it from fp32 distances (the training step's form); pair_fac != nullptr: the K_uu blocks
+// write it from the fp64 squared distances they hold (no extra blocks; entries p < P only, the padding is never used)
 // psi2_consts != nullptr: the same launch also builds the z-only constants of the f16 psi2 kernel (psi2_consts.h) from
 // z[M,Q] into psi2_consts (psi2_consts_bytes(M, Q) bytes)
 

@@ -152,8 +152,9 @@ __device__ __forceinline__ void psi2_pair_rows(const TIN *__restrict__ z, int M,
 
 // scale[b][p] = alpha_b^2 exp2(beta_bp),  beta_bp = -1/4 log2e sum_q gamma_bq (z_mq - z_m'q)^2: the per-output factor of every
 // pair of the pair-tile psi2 kernel (applied once per column sum instead of once per exponent); 256 pairs per block, thread =
-// pair, straight from z (no dependency on the other constants).  Runs as extra blocks of the front launch of the fused ELBO,
-// or as a launch of its own (psi2_pairs.hip).
+// pair, straight from z (no dependency on the other constants).  Runs as extra blocks of the front launch of the fused ELBO's
+// training step, or as a launch of its own (psi2_pairs.hip).  The forward evaluation has no such blocks: p = m (m + 1) / 2 + m' is
+// the packed lower triangle, and the K_uu blocks of its front launch write the table from the fp64 r^2 they hold (gram_tile).
 // output dims per workgroup of the scale role: 16 at D = 512 (the gather amortised), fewer for few output dims (D = 64: 2 —
 // with 16 the role is 132 long workgroups and the front launch of the per-GPU share takes 16.0 instead of 14.6 us)
 __host__ __device__ inline int psi2_scale_dchunk(int D) {

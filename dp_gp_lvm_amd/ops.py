@@ -754,7 +754,32 @@ class ElboWorkspace:
         # guard[d]: bound on what the rounding of an fp32 Psi2 can do to output dim d's terms (include/dpgp.h,
         # DPGP_INFO_ILL_CONDITIONED); a view into the workspace, valid after an evaluation
         self.guard = self.ws[self.layout[8]:self.layout[8] + 8 * d].view(torch.float64)
+        flay = (ctypes.c_size_t * 6)()
+        _lib.check(l.dpgp_elbo_workspace_front_layout(d, n, m, q, _lib.PREC[prec], ctypes.cast(flay, ctypes.c_void_p)),
+                   'dpgp_elbo_workspace_front_layout')
+        self.front_layout = tuple(int(v) for v in flay)
 
+    def kuu(self):
+        """K_uu + jitter I [D,M,M] as the front launch of the last ``elbo_fhat`` left it: a strided view into the workspace."""
+        d, _, m, _ = self.shape
+        off, stride, elem, mp, _, _ = self.front_layout
+        dt = torch.float32 if elem == 4 else torch.float64
+        flat = self.ws[off:off + stride * d].view(dt)
+        return flat.as_strided((d, m, m), (stride // elem, mp, 1))
+
+    def pair_factors(self):
+        """The pair factors alpha_d^2 exp(-r^2 / 4) the last ``elbo_fhat`` (algo 'auto') left for the pair-tile Psi2 kernel, unpacked
+        from its table to [D,M,M] fp32 (entries m' <= m; zeros above the diagonal), or None where that kernel does not run (fp64
+        Psi2, Q > 21)."""
+        d, _, m, _ = self.shape
+        off, ppad = self.front_layout[4], self.front_layout[5]
+        if ppad == 0:
+            return None
+        tab = self.ws[off:off + 4 * d * ppad].view(torch.float32).view(d, ppad)
+        rows, cols = torch.tril_indices(m, m, device=self.ws.device)
+        out = torch.zeros((d, m, m), dtype=torch.float32, device=self.ws.device)
+        out[:, rows, cols] = tab[:, rows * (rows + 1) // 2 + cols]
+        return out
 
     def __del__(self):
         try:

@@ -410,6 +410,11 @@ size_t dpgp_elbo_workspace_bytes(int D, int N, int M, int Q, int prec);
  * byte offset of guard[D] (fp64: bound on the effect of an fp32 Psi2's rounding on each output dim's terms), D }.
  * Used by the host-side composition of the backward pass's stage A for M > 128 (ops.elbo_grad_chain). */
 int dpgp_elbo_workspace_layout(int D, int N, int M, int Q, int prec, size_t *out);
+/* what the front launch of a finished dpgp_elbo_fhat[_ex] call left inside ws: out[6] = { byte offset of K_uu + jitter I of output
+ * dim 0 ([Mp][Mp], the square [0,M) x [0,M) written), byte stride between output dims, element size (4 or 8), Mp, byte offset of the
+ * pair factors alpha_d^2 exp(-1/4 sum_q gamma_dq (z_mq - z_m'q)^2) of the pair-tile Psi2 kernel (fp32 [D][Ppad], pair (m, m'),
+ * m' <= m, at m (m + 1) / 2 + m'; DPGP_ALGO_AUTO), Ppad -- 0 where that kernel does not run (fp64 Psi2, Q > 21) }. */
+int dpgp_elbo_workspace_front_layout(int D, int N, int M, int Q, int prec, size_t *out);
 int dpgp_elbo_fhat(int D, int N, int M, int Q, const double *y, int ldy, const double *z, const double *mu,
                    const double *s, const double *gamma, const double *alpha, const double *beta, double jitter,
                    int prec, int algo, double *terms, double *sums, int *info, void *ws, size_t ws_bytes,
