@@ -33,7 +33,7 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
-from . import collapsed, marginals as _marginals, predictor as _predictor
+from . import collapsed, geodesic as _geodesic, marginals as _marginals, predictor as _predictor
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .frozen_bound import _TestBound
@@ -729,6 +729,21 @@ def dp_gp_lvm(y_train,
         assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
         return cols
 
+    def _curve_terms(columns, name):
+        """The terms of models/geodesic.py under latent_metric(., columns): _latent_geometry's kernels with their (P, prior) and
+        the prior of the columns never observed, formed once."""
+        assert not split, '%s is not built for a model sharded over a process group' % name
+        cols = _geometry_columns(columns)
+        evaluate()
+        with torch.no_grad():
+            marg, _, prior_unseen = _latent_geometry(cols)
+            if marg is None:
+                weight = torch.diagonal(prior_unseen).contiguous()
+                return lambda x, v: _geodesic.prior_terms(v, weight)
+            p, prior = marg._metric_operands(None, None)
+            prior = torch.cat([prior, prior_unseen[None]])
+        return lambda x, v: marg.curve_terms(x, v, p, prior)
+
     def _assembled_marginals(cols, xt, st_):
         """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
         into a zero-filled [2 x N* x len(cols)] buffer, one sum all-reduce completes it; every rank returns the same (mean, var).
@@ -1059,6 +1074,34 @@ def dp_gp_lvm(y_train,
             assert not split, 'magnification is not built for a model sharded over a process group'
             with torch.no_grad():
                 return _marginals.magnification(DP_GP_LVM.latent_metric(x, columns))
+
+        @staticmethod
+        def curve_energy(curve, columns=None, return_gradient=False):
+            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
+            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
+            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy over K = len(columns)
+            kernels on the C S segments, summed over them in blocks of segments; with the columns of one discovered group, that
+            group's own energy.  The training side is built once per call.  fp64, torch.no_grad.  Not built for a model sharded
+            over a process group: AssertionError."""
+            return _geodesic.curve_energy(_curve_terms(columns, 'curve_energy'), curve, num_latent_dims, device, return_gradient)
+
+        @staticmethod
+        def curve_length(curve, columns=None):
+            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E).  Not built for a model
+            sharded over a process group: AssertionError."""
+            return _geodesic.curve_length(_curve_terms(columns, 'curve_length'), curve, num_latent_dims, device)
+
+        @staticmethod
+        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
+            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
+            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
+            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
+            iterate is returned, so its energy never exceeds the start's.  With the columns of one discovered group: the paths
+            that group considers short.  The training side is built once per call; an iteration is one call of
+            ops.ard_rbf_point_energy plus element-wise work.  fp64.  Not built for a model sharded over a process group:
+            AssertionError."""
+            return _geodesic.latent_geodesic(_curve_terms(columns, 'latent_geodesic'), x_from, x_to, num_latent_dims, device,
+                                             num_segments, num_iterations, learning_rate, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1691,6 +1734,14 @@ def dp_gp_lvm_t(y_train,
     def _columns_arg(columns):
         return _marginals.columns_arg(columns, num_dimensions, device)
 
+    def _curve_terms(columns):
+        """The terms of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+        cols = _columns_arg(columns)
+        with torch.no_grad():
+            mom = _moments()
+            p, prior = mom.curve_operands(cols)
+        return lambda x, v: mom.curve_terms(x, v, p, prior)
+
     class DP_GP_LVM_T(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
@@ -1851,6 +1902,31 @@ def dp_gp_lvm_t(y_train,
             factorisation of G."""
             with torch.no_grad():
                 return _marginals.magnification(DP_GP_LVM_T.latent_metric(x, columns))
+
+        @staticmethod
+        def curve_energy(curve, columns=None, return_gradient=False):
+            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
+            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
+            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy on the T atoms and
+            the C S segments; with the columns of one discovered group, that group's own energy.  The training side is built once
+            per call.  fp64, torch.no_grad."""
+            return _geodesic.curve_energy(_curve_terms(columns), curve, num_latent_dims, device, return_gradient)
+
+        @staticmethod
+        def curve_length(curve, columns=None):
+            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E)."""
+            return _geodesic.curve_length(_curve_terms(columns), curve, num_latent_dims, device)
+
+        @staticmethod
+        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
+            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
+            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
+            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
+            iterate is returned, so its energy never exceeds the start's.  With the columns of one discovered group: the paths
+            that group considers short.  The training side is built once per call; an iteration is one call of
+            ops.ard_rbf_point_energy plus element-wise work.  fp64."""
+            return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, device, num_segments,
+                                             num_iterations, learning_rate, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

@@ -121,3 +121,13 @@ class _MomentsT:
         mixture_moments takes it for the variance: sum_t ( n_t alpha_t diag(gamma_t) + b_t^T P_t b_t ), n_t = sum_d phi_td,
         P_t = sum_d phi_td (r_td r_td^T - C_t,p(d))  (marginals._Marginals.metric_total with phi as the columns' weights)."""
         return self._atoms().metric_total(x, cols, weights=self.phit)
+
+    def curve_operands(self, cols):
+        """(P [T, M, M], prior [T, Q, Q]) of metric's text over the columns `cols`: marginals._Marginals._metric_operands with
+        phi as the columns' weights; formed once per curve call."""
+        self._curve_atoms = self._atoms()
+        return self._curve_atoms._metric_operands(cols, self.phit)
+
+    def curve_terms(self, x, v, p, prior):
+        """marginals._Marginals.curve_terms on the T atoms, (p, prior) from curve_operands."""
+        return self._curve_atoms.curve_terms(x, v, p, prior)

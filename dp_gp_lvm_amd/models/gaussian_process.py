@@ -32,7 +32,7 @@ from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .frozen_bound import _TestBound, _as_device, kernel_slots
 from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
-from . import collapsed, marginals as _marginals, predictor as _predictor
+from . import collapsed, geodesic as _geodesic, marginals as _marginals, predictor as _predictor
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -507,6 +507,14 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             mean, var = _train_marginals().at(xt, st_, _marginals.columns_arg(columns, num_dimensions, dev_))
         return mean[0], var[0]
 
+    def _curve_terms(columns):
+        """The terms of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+        cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+        with torch.no_grad():
+            marg = _train_marginals()
+            p, prior = marg._metric_operands(cols, None)
+        return lambda x, v: marg.curve_terms(x, v, p, prior)
+
     class BayesianGPLVM(Trainable):
         """Accessors as in the reference (gaussian_process.py:276-340), and its two prediction methods (:329-538) with the same
         keywords and return tuples as dp_gp_lvm's, plus test_latent_gradients / optimise_test_latents / prediction_terms.
@@ -573,6 +581,29 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             (what GPy draws as plot_magnification), as exp(1/2 logdet) from a Cholesky factorisation of G."""
             with torch.no_grad():
                 return _marginals.magnification(BayesianGPLVM.latent_metric(x, columns))
+
+        @staticmethod
+        def curve_energy(curve, columns=None, return_gradient=False):
+            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
+            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
+            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy on the C S segments;
+            the training side is built once per call.  fp64, torch.no_grad."""
+            return _geodesic.curve_energy(_curve_terms(columns), curve, num_latent_dims, dev_, return_gradient)
+
+        @staticmethod
+        def curve_length(curve, columns=None):
+            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E)."""
+            return _geodesic.curve_length(_curve_terms(columns), curve, num_latent_dims, dev_)
+
+        @staticmethod
+        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
+            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
+            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
+            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
+            iterate is returned, so its energy never exceeds the start's.  The training side is built once per call; an iteration
+            is one call of ops.ard_rbf_point_energy plus element-wise work.  fp64."""
+            return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, dev_, num_segments,
+                                             num_iterations, learning_rate, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1010,6 +1041,15 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
         return vs
 
+    def _curve_terms(views, total):
+        """The terms of models/geodesic.py of every view of `views` (one entry: their sum, with total), formed once."""
+        vs = _views_arg(views)
+        with torch.no_grad():
+            train = _train_marginals()
+            pairs = [train[v]._metric_operands(None, None) for v in vs]
+        each = [lambda x, v, marg=train[vv], pair=pair: marg.curve_terms(x, v, *pair) for vv, pair in zip(vs, pairs)]
+        return [_geodesic.sum_terms(each)] if total else each
+
     class ManifoldRelevanceDetermination(Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
         test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
@@ -1077,6 +1117,30 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             """One magnification factor sqrt(det G_v(x)) [N*] per view of `views` (default: all V, in order)."""
             with torch.no_grad():
                 return [_marginals.magnification(g) for g in ManifoldRelevanceDetermination.latent_metric(x, views)]
+
+        @staticmethod
+        def curve_energy(curve, views=None, total=False, return_gradient=False):
+            """One curve energy E [C] per view of `views` (default: all V, in order) of the curves `curve` [C x S+1 x Q] (or one
+            curve [S+1 x Q]), as bayesian_gp_lvm.curve_energy under the view's latent_metric; with return_gradient one pair
+            (E, dE / dcurve) per view.  total=True: one result, under the summed metric latent_metric(., views, total=True)."""
+            out = [_geodesic.curve_energy(t, curve, num_latent_dims, dev_, return_gradient) for t in _curve_terms(views, total)]
+            return out[0] if total else out
+
+        @staticmethod
+        def curve_length(curve, views=None, total=False):
+            """One curve length L [C] per view of `views`, as bayesian_gp_lvm.curve_length; total=True: under the summed metric."""
+            out = [_geodesic.curve_length(t, curve, num_latent_dims, dev_) for t in _curve_terms(views, total)]
+            return out[0] if total else out
+
+        @staticmethod
+        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, views=None, total=False,
+                            init=None):
+            """One triple (curve [C x S+1 x Q], length [C], energy [C]) per view of `views`: the view's own geodesics, as
+            bayesian_gp_lvm.latent_geodesic under the view's latent_metric; total=True: one triple, the geodesics under the
+            summed metric.  The training side of all views is built once per call."""
+            out = [_geodesic.latent_geodesic(t, x_from, x_to, num_latent_dims, dev_, num_segments, num_iterations, learning_rate,
+                                             init) for t in _curve_terms(views, total)]
+            return out[0] if total else out
 
         @staticmethod
         def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,

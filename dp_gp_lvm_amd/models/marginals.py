@@ -70,6 +70,24 @@ class _Marginals:
                for i in range(0, x.shape[0], step)]
         return torch.cat(out) + torch.sum(prior, dim=0)
 
+    def curve_terms(self, x, v, p, prior):
+        """(e [N*], dx [N*, Q], dv [N*, Q]): e_n = v_n^T G(x_n) v_n of metric_total's G along the directions v [N*, Q] at the
+        points x [N*, Q], and its gradients with respect to x_n and v_n: what a curve's energy and its gradient are made of
+        (models/geodesic.py).  (p, prior) are _metric_operands' pair, formed once by the caller; prior may hold further
+        constant diagonal metrics [*, Q, Q] (only the diagonals are read).  ONE call of ops.ard_rbf_point_energy per block of
+        points, summed over the K kernels, plus the prior's share sum_q w_q v_q^2 in e and 2 w_q v_q in dv,
+        w_q = sum_k n_k alpha_k gamma_kq.  Blocks of at most 2^25 result entries, as metric_total."""
+        x, v = x.contiguous(), v.contiguous()
+        k, q = self.z.shape[0], self.z.shape[2]
+        step = max(1, (1 << 25) // (k * (2 * q + 1)))
+        parts = []
+        for i in range(0, x.shape[0], step):
+            out = ops.ard_rbf_point_energy(self.z, x[i:i + step], v[i:i + step], self.gamma, self.alpha, p)
+            parts.append([o[0] if k == 1 else torch.sum(o, dim=0) for o in out])
+        e, dx, dv = (ps[0] if len(ps) == 1 else torch.cat(ps) for ps in zip(*parts))
+        w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0)
+        return e + torch.sum(v * v * w, dim=1), dx, dv + 2.0 * v * w
+
     def _metric_operands(self, cols, weights):
         """(P [K, M, M], n_k alpha_k diag(gamma_k) [K, Q, Q]) of metric's text."""
         r, gidx = self.r, self.gidx

@@ -487,10 +487,11 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     return d_mu, d_s
 
 
-def _point_metric_args(z, x, gamma, alpha, a, name, what):
-    """The checks of the two operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
-    (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M] or r [K,M,J], `what` its wording)."""
-    args = (('z', z), ('x', x), ('gamma', gamma), ('alpha', alpha), (name, a))
+def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None):
+    """The checks of the three operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
+    (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M] or r [K,M,J], `what` its wording); dirs: the
+    directions v [N,Q] of ard_rbf_point_energy (a one-element tuple), checked in their place after x."""
+    args = (('z', z), ('x', x)) + (() if dirs is None else (('v', dirs[0]),)) + (('gamma', gamma), ('alpha', alpha), (name, a))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % nm)
@@ -499,6 +500,8 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what):
     k, m, q = z.shape
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != q:
         raise ValueError('x must be [N x Q] with Q = %d, got %s' % (q, tuple(x.shape)))
+    if dirs is not None and tuple(dirs[0].shape) != tuple(x.shape):
+        raise ValueError('v must be [N x Q] as x, got %s' % (tuple(dirs[0].shape),))
     if tuple(gamma.shape) != (k, q):
         raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
     if alpha.numel() != k:
@@ -544,6 +547,27 @@ def ard_rbf_point_jacobian(z, x, gamma, alpha, r):
                                                  r.data_ptr(), jac.data_ptr(), ws.data_ptr(), wsb, _stream()),
                'dpgp_ard_rbf_point_jacobian_f64')
     return jac
+
+
+def ard_rbf_point_energy(z, x, v, gamma, alpha, p):
+    """The quadratic form of ard_rbf_point_metric along the directions v [N,Q] at the points x [N,Q], with both gradients
+    (dpgp_ard_rbf_point_energy_f64): with b as there, c_knm = sum_q b_kmq(x_n) v_nq, returns (e, dx, dv),
+        e [K,N] = sum_{m,m'} p[k,m,m'] c_knm c_knm' = v_n^T g[k,n] v_n,     dx [K,N,Q] = de/dx_n,     dv [K,N,Q] = de/dv_n
+    p [K,M,M] is any matrix; the results depend on its symmetric part only.  The alpha diag(gamma) term of the expected metric
+    is the caller's.  One launch, nothing of size N M in memory; fixed summation order, the same bits on every run.  float64
+    tensors (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
+    z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]', dirs=(v,))
+    v = v.contiguous()
+    e = torch.empty((k, n), dtype=torch.float64, device=z.device)
+    dx = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
+    dv = torch.empty_like(dx)
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_point_energy_workspace_bytes(k, n, m, q)
+    ws = _ws(wsb, z.device)
+    _lib.check(l.dpgp_ard_rbf_point_energy_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), v.data_ptr(), gamma.data_ptr(),
+                                               alpha.data_ptr(), p.data_ptr(), e.data_ptr(), dx.data_ptr(), dv.data_ptr(),
+                                               ws.data_ptr(), wsb, _stream()), 'dpgp_ard_rbf_point_energy_f64')
+    return e, dx, dv
 
 
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):

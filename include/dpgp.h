@@ -298,6 +298,31 @@ size_t dpgp_ard_rbf_point_jacobian_workspace_bytes(int K, int J, int N, int M, i
 int dpgp_ard_rbf_point_jacobian_f64(int K, int J, int N, int M, int Q, const double *z, const double *x, const double *gamma,
                                     const double *alpha, const double *r, double *jac, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Curve energy at deterministic latent points along directions, with both gradients (csrc/ard_rbf_point_energy.hip): what a
+ *      geodesic under the expected metric needs at every segment.  Kernels, points x[N][Q] and p[K][M][M] as for the metric
+ *      operator above; directions v[N][Q], shared by the kernels.  With k_km and b_kmq as above and
+ *        d_knmq = x_nq - z_kmq,   a_knm = sum_q gamma_kq d_knmq v_nq,   c_knm = sum_q b_kmq(x_n) v_nq = -k_km(x_n) a_knm
+ *        w_knm  = sum_m' (p[k][m][m'] + p[k][m'][m]) c_knm'
+ *      the operator gives
+ *        e[K][N]     = sum_{m,m'} p[k][m][m'] c_knm c_knm' = 1/2 sum_m w_knm c_knm       (= v_n^T g[k][n] v_n of the metric operator)
+ *        dx[K][N][Q] = d e / d x_nq = gamma_kq sum_m w_knm k_km (a_knm d_knmq - v_nq)
+ *        dv[K][N][Q] = d e / d v_nq = -gamma_kq sum_m w_knm k_km d_knmq
+ *      p is any matrix; the results depend on its symmetric part only.  The alpha diag(gamma) term of the expected metric is the
+ *      caller's.  One launch: a workgroup owns a kernel and a tile of 16 points, forms c on the fly (one exponential per
+ *      (k, n, m) and per slab of 64 rows of p), runs W = (p + p^T) C on the fp64 matrix pipe with p streamed in symmetrised
+ *      64 x 64 tiles (no limit on M from the LDS) and adds each finished slab's rows to the sums above with the differences d.
+ *      Nothing of size N M is written to memory; no atomics, the order of every sum is fixed by (M, Q): the same bits on every
+ *      run; a point's results depend neither on N, nor on its place in x, nor on K.  Points far from every z give exact zeros.
+ *      1 <= K, N, M;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, N -2, M -3, Q -4, z -5, x -6, v -7, gamma -8,
+ *      alpha -9, p -10, e -11, dx -12, dv -13, ws -14, ws_bytes too small -15.
+ *   ws: the results are written from registers, so the query (a host function) returns a token 256 bytes for a shape in range and
+ *      0 for one out of range; the pair (ws, ws_bytes) keeps the calling convention of the other point operators. */
+size_t dpgp_ard_rbf_point_energy_workspace_bytes(int K, int N, int M, int Q);
+int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *v,
+                                  const double *gamma, const double *alpha, const double *p, double *e, double *dx, double *dv,
+                                  void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Latent adjoint of B kernels that share inducing inputs AND q(X*) (csrc/psi_latent_adjoint.hip): the frozen over-D model at
  *      test time.  z[M][Q], q(X*) = (mu[N][Q], s[N][Q]: variances), gamma[B][Q], alpha[B]; y[N][ldy]: zero-filled data, column b
  *      for kernel b; w[B][N]: weights of the test points (NULL = all ones; any finite reals); stage-A adjoints g_v[B][M] and
