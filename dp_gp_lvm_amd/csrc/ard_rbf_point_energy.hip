@@ -189,9 +189,7 @@ int pe_launch(int K, int N, int M, int Q, const double *z, const double *x, cons
               const double *alpha, const double *p, double *e, double *dx, double *dv, hipStream_t st) {
     const int ntn = dpgp_ceil_div(N, PE_NP);
     const size_t lds = pe_lds(Q);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pe_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(pe_kernel<QT>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((pe_kernel<QT>), dim3((unsigned)((long)K * ntn)), dim3(256), lds, st, N, M, Q, ntn, z, x, v, gamma, alpha,
                        p, e, dx, dv);

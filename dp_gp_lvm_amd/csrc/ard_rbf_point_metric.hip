@@ -186,9 +186,7 @@ int mt_launch(int K, int N, int M, int Q, int R, const double *z, const double *
               const double *a, double *out, hipStream_t st) {
     const int ntn = dpgp_ceil_div(N, MtCfg<QT>::NP);
     const size_t lds = mt_lds(Q, MtCfg<QT>::NP, MtCfg<QT>::BS);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(mt_kernel<QT, JAC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(mt_kernel<QT, JAC>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((mt_kernel<QT, JAC>), dim3((unsigned)((long)K * ntn)), dim3(256), lds, st, N, M, Q, R, ntn, z, x, gamma,
                        alpha, a, out);

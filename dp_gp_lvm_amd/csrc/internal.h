@@ -12,6 +12,39 @@ static inline int dpgp_env_plan(const char *name, int lo, int hi) {
     return v < lo ? 0 : (v > hi ? hi : v);
 }
 
+// Raises a kernel's dynamic-LDS limit where the launch needs more than the 48 KiB every kernel may have.
+static inline int dpgp_set_dyn_lds(const void *fn, size_t lds) {
+    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return DPGP_ERR_LAUNCH;
+    return DPGP_OK;
+}
+
+// Two-level slab split of the per-point adjoint operators (psi_latent_adjoint.hip, qx_psi_point_adjoint.hip): enough workgroups
+// to fill the GPU (target), first by slabs of the n_outer kernels / columns (no work is repeated), then by slabs of the pair tiles
+// (each repeats the per-kernel staging).  base: the workgroups of one slab pair.  env_outer / env_pair force the two counts
+// (dpgp_env_plan, clamped to n_outer / tiles).
+struct DpgpSlabSplit { int outer_slabs, outer_per_slab, pair_slabs, tiles_per_slab; };
+static inline DpgpSlabSplit dpgp_slab_split(long base, int target, int n_outer, int tiles, const char *env_outer,
+                                            const char *env_pair) {
+    DpgpSlabSplit p;
+    long os = (target + base - 1) / base;
+    if (const int v = dpgp_env_plan(env_outer, 1, n_outer)) os = v;
+    os = os < 1 ? 1 : (os > n_outer ? n_outer : os);
+    p.outer_per_slab = (n_outer + (int)os - 1) / (int)os;
+    p.outer_slabs = (n_outer + p.outer_per_slab - 1) / p.outer_per_slab;
+    long ps = (target + base * p.outer_slabs - 1) / (base * p.outer_slabs);
+    if (const int v = dpgp_env_plan(env_pair, 1, tiles)) ps = v;
+    ps = ps < 1 ? 1 : (ps > tiles ? tiles : ps);
+    p.tiles_per_slab = (tiles + (int)ps - 1) / (int)ps;
+    p.pair_slabs = (tiles + p.tiles_per_slab - 1) / p.tiles_per_slab;
+    return p;
+}
+
+// ---- psi_latent_adjoint.hip --------------------------------------------------------------------------------------
+// the second launch of the per-point adjoint operators: (d_mu, d_s)[n][q] = the slabs part[slab][2][N][Q] added in slab order
+// (nq = N Q)
+int launch_point_adjoint_slab_sum(size_t nq, int slabs, const double *part, double *d_mu, double *d_s, hipStream_t st);
+
 // ---- elementwise.hip -------------------------------------------------------------------------------------------
 // gram with explicit output leading dimension / batch stride so the fused ELBO can write straight into its padded
 // Cholesky workspace.  x1 == nullptr: symmetric case, noise/jitter flags honoured.

@@ -29,6 +29,7 @@
 // wave-uniform branch; a scale of 0 that is not skipped multiplies finite moments: exactly 0.0 either way.
 // The accumulators go to part[slab][2][N][Q]; a second launch adds the slabs in slab order.  No atomics: the same bits on every run.
 #include "internal.h"
+#include "qx_tile.h"
 
 #define PL_TILE 32
 #define PL_NP 64            // test points per workgroup: 4 waves x 16 MFMA rows
@@ -45,14 +46,6 @@ struct PlArgs {
     const double *z, *mu, *s, *gamma, *alpha, *y, *w, *gv, *g2;
     double *part;
 };
-
-// tile index -> (I, J), I <= J, row-major over the upper block triangle (as pw_tile_ij)
-__device__ __forceinline__ void pl_tile_ij(int idx, int T, int &I, int &J) {
-    int i = 0;
-    while (idx >= T - i) { idx -= T - i; ++i; }
-    I = i;
-    J = i + idx;
-}
 
 template <int CT, bool QREG>
 __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
@@ -109,16 +102,10 @@ __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
                 sg[q * PL_NP + i] = n0 + i < N ? g / fma(k2 * g, a.s[(size_t)n0 * Q + e], 1.0) : 0.0;
             }
             if (t < PL_NP) {
-                double v = 0.0, sc_ = 0.0;
+                double sc_ = 0.0;
                 const int n = n0 + t;
-                if (n < N) {
-                    const double *sn = a.s + (size_t)n * Q;
-                    double l = 0.0;
-                    for (int q = 0; q < Q; ++q) l += log(fma(k2 * gk[q], sn[q], 1.0));
-                    v = (p2 ? 1.0 : al) * exp(-0.5 * l);
-                    sc_ = p2 ? (a.w ? a.w[(size_t)b * N + n] : 1.0) : 0.5 * a.y[(size_t)n * a.ldy + b];
-                }
-                sc[t] = v;
+                if (n < N) sc_ = p2 ? (a.w ? a.w[(size_t)b * N + n] : 1.0) : 0.5 * a.y[(size_t)n * a.ldy + b];
+                sc[t] = dpgp_point_prefactor(n, N, Q, gk, a.s, k2, p2 ? 1.0 : al);
                 ssc[t] = sc_;
             }
             for (int q = t; q < Q; q += 256) gm[q] = gk[q];
@@ -127,24 +114,15 @@ __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
             const bool on = wave_live && __any(scale != 0.0);  // (wave-uniform)
             if (!__syncthreads_or(on)) continue;               // (workgroup-uniform: nothing of this column counts here)
             const double c2 = sc[pi];
-            // Q <= 16: the exponent kexp sum_q g_q (mu_q - zbar_q)^2 as  e0 + sum_q zbar_q (pw_q zbar_q + pl_q): two FMAs per q and step
-            double pl[QREG ? PL_QR : 1], pw[QREG ? PL_QR : 1], e0 = 0.0;
-            if constexpr (QREG) {
-#pragma unroll
-                for (int q = 0; q < PL_QR; ++q) {
-                    const double mq = q < Q ? smu[q * PL_NP + pi] : 0.0;
-                    pw[q] = q < Q ? kexp * sg[q * PL_NP + pi] : 0.0;
-                    pl[q] = -2.0 * pw[q] * mq;
-                    e0 = fma(pw[q] * mq, mq, e0);
-                }
-            }
+            DpgpPointExponent<QREG ? PL_QR : 1> ex;            // (Q <= 16: the expanded exponent, two FMAs per q and step)
+            if constexpr (QREG) ex.setup(Q, kexp, smu, sg, PL_NP, pi);
             f64x4 acc[CT];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
             const int t_lo = p2 ? tile_lo : 0, t_hi = p2 ? tile_hi : a.T;
             for (int tile = t_lo; tile < t_hi; ++tile) {
                 int I = tile, Jt = tile;
-                if (p2) pl_tile_ij(tile, a.T, I, Jt);
+                if (p2) dpgp_tile_ij(tile, a.T, I, Jt);
                 const bool diag = I == Jt;
                 const int m0 = I * PL_TILE, c0 = Jt * PL_TILE;
                 const int nr = min(PL_TILE, M - m0), nc = min(PL_TILE, M - c0);
@@ -188,11 +166,9 @@ __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
                     for (int st = s_lo; st < s_hi; ++st) {
                         const int cc = 4 * st + kk;
                         const double *zq = zz + (size_t)cc * Q;
-                        double e = e0;
+                        double e = 0.0;
                         if constexpr (QREG) {
-#pragma unroll
-                            for (int q = 0; q < PL_QR; ++q)
-                                if (q < Q) e = fma(zq[q], fma(pw[q], zq[q], pl[q]), e);
+                            e = ex.at(Q, zq);
                         } else {
                             for (int q = 0; q < Q; ++q) {
                                 const double d = smu[q * PL_NP + pi] - zq[q];
@@ -209,15 +185,7 @@ __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
             }
             // the column's moments -> its contribution to (d_mu, d_s)
             __syncthreads();                                   // (every wave is done with zc / zb / sF / sW: sM lies over them)
-            if (on) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    if (ct < nct) {
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr)
-                            sM[(wave * 16 + Mfma<double>::row(lane, rr)) * MS + 16 * ct + (lane & 15)] = acc[ct][rr];
-                    }
-            }
+            if (on) dpgp_spill_moment_tiles(acc, nct, sM, MS, wave, lane);
             __syncthreads();
             if (on) {
                 const int cw = 16 * nct;
@@ -241,20 +209,12 @@ __global__ __launch_bounds__(256) void pl_kernel(const PlArgs a) {
     const int n = n0 + pi;
     if (n >= N) return;
     const size_t slab = ((size_t)cslab * a.pslabs + pslab) * a.nchunks + chunk;
-    double *pb = a.part + slab * 2 * (size_t)N * Q;
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int q = kk + 4 * j;
-        if (q < Q) {
-            pb[(size_t)n * Q + q] = dmu[j];
-            pb[((size_t)N + n) * Q + q] = dsv[j];
-        }
-    }
+    dpgp_write_point_partials(a.part + slab * 2 * (size_t)N * Q, n, N, Q, kk, dmu, dsv);
 }
 
-// d_mu[n][q], d_s[n][q]: the slabs added in slab order
-__global__ __launch_bounds__(256) void pl_reduce_kernel(size_t nq, int slabs, const double *__restrict__ part, double *__restrict__ d_mu,
-                                                        double *__restrict__ d_s) {
+// d_mu[n][q], d_s[n][q]: the slabs added in slab order (launch_point_adjoint_slab_sum, also qx_psi_point_adjoint.hip's)
+__global__ __launch_bounds__(256) void point_adjoint_slab_sum_kernel(size_t nq, int slabs, const double *__restrict__ part,
+                                                                     double *__restrict__ d_mu, double *__restrict__ d_s) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= 2 * nq) return;
     double acc = 0.0;
@@ -275,19 +235,9 @@ PlPlan pl_plan(int B, int N, int M, int Q) {
     p.nct = dpgp_ceil_div(tiles16, dpgp_ceil_div(tiles16, PL_MAXCT));   // chunks of equal width
     p.nchunks = dpgp_ceil_div(tiles16, p.nct);
     p.ct = p.nct <= 1 ? 1 : p.nct <= 2 ? 2 : p.nct <= 4 ? 4 : 8;
-    // enough workgroups to fill the GPU: first by slabs of columns b (no work is repeated), then by slabs of pair tiles (each
-    // repeats the per-column staging).  DPGP_PLA_COL_SLABS / DPGP_PLA_PAIR_SLABS force the two counts (clamped to B / the tiles)
-    const long base = (long)p.ntn * p.nchunks;
-    long cs = (PL_TARGET_WGS + base - 1) / base;
-    if (const int v = dpgp_env_plan("DPGP_PLA_COL_SLABS", 1, B)) cs = v;
-    cs = cs < 1 ? 1 : (cs > B ? B : cs);
-    p.cols_per_slab = dpgp_ceil_div(B, (int)cs);
-    p.cslabs = dpgp_ceil_div(B, p.cols_per_slab);
-    long ps = (PL_TARGET_WGS + base * p.cslabs - 1) / (base * p.cslabs);
-    if (const int v = dpgp_env_plan("DPGP_PLA_PAIR_SLABS", 1, p.tiles)) ps = v;
-    ps = ps < 1 ? 1 : (ps > p.tiles ? p.tiles : ps);
-    p.tiles_per_slab = dpgp_ceil_div(p.tiles, (int)ps);
-    p.pslabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);
+    // slabs of columns b, then of pair tiles; DPGP_PLA_COL_SLABS / DPGP_PLA_PAIR_SLABS force the two counts
+    const DpgpSlabSplit sp = dpgp_slab_split((long)p.ntn * p.nchunks, PL_TARGET_WGS, B, p.tiles, "DPGP_PLA_COL_SLABS", "DPGP_PLA_PAIR_SLABS");
+    p.cslabs = sp.outer_slabs; p.cols_per_slab = sp.outer_per_slab; p.pslabs = sp.pair_slabs; p.tiles_per_slab = sp.tiles_per_slab;
     return p;
 }
 
@@ -310,9 +260,7 @@ bool pl_shape_ok(int B, int N, int M, int Q) {
 template <int CT, bool QREG> int pl_launch(const PlPlan &p, PlArgs a, hipStream_t st) {
     const size_t lds = pl_lds(a.Q, CT);
     a.region = pl_region(a.Q, CT);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(pl_kernel<CT, QREG>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(pl_kernel<CT, QREG>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((pl_kernel<CT, QREG>), dim3((unsigned)((long)p.ntn * p.nchunks * p.cslabs), p.pslabs), dim3(256), lds, st, a);
     DPGP_LAUNCH_CHECK();
@@ -325,6 +273,14 @@ template <bool QREG> int pl_dispatch(const PlPlan &p, const PlArgs &a, hipStream
 }
 
 }  // namespace
+
+int launch_point_adjoint_slab_sum(size_t nq, int slabs, const double *part, double *d_mu, double *d_s, hipStream_t st) {
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL(point_adjoint_slab_sum_kernel, dim3((unsigned)((2 * nq + 255) / 256)), dim3(256), 0, st, nq, slabs, part, d_mu,
+                       d_s);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
 
 extern "C" size_t dpgp_psi_latent_adjoint_workspace_bytes(int B, int N, int M, int Q) {
     if (!pl_shape_ok(B, N, M, Q)) return 0;
@@ -363,10 +319,5 @@ extern "C" int dpgp_psi_latent_adjoint_f64(int B, int N, int M, int Q, const dou
     a.part = static_cast<double *>(ws);
     const int rc = Q <= PL_QR ? pl_dispatch<true>(p, a, st) : pl_dispatch<false>(p, a, st);
     if (rc) return rc;
-    const size_t nq = (size_t)N * Q;
-    DPGP_PRELAUNCH();
-    hipLaunchKernelGGL(pl_reduce_kernel, dim3((unsigned)((2 * nq + 255) / 256)), dim3(256), 0, st, nq, p.cslabs * p.pslabs * p.nchunks,
-                       (const double *)a.part, d_mu, d_s);
-    DPGP_LAUNCH_CHECK();
-    return DPGP_OK;
+    return launch_point_adjoint_slab_sum((size_t)N * Q, p.cslabs * p.pslabs * p.nchunks, a.part, d_mu, d_s, st);
 }

@@ -42,6 +42,7 @@
 // tile's pair loop when all 64 points of the wave have weight 0 for kernel b.  Either way its contribution is exactly 0.
 // The parameter adjoint skips a point of weight 0 as the stats kernel does, on its staged weight; its Psi1 term is not weighted.
 #include "internal.h"
+#include "qx_tile.h"
 
 #define QP_TILE 32
 #define QP_HSTRIDE (QP_TILE + 1)
@@ -54,14 +55,6 @@
 namespace {
 
 int qp_tiles(int M) { const int t = dpgp_ceil_div(M, QP_TILE); return t * (t + 1) / 2; }
-
-// tile index -> (I, J), I <= J, row-major over the upper block triangle
-__device__ __forceinline__ void qp_tile_ij(int idx, int T, int &I, int &J) {
-    int i = 0;
-    while (idx >= T - i) { idx -= T - i; ++i; }
-    I = i;
-    J = i + idx;
-}
 
 // pair factor F[m][m'] (alpha^2 exp(-1/4 sum gamma dz^2)), from zfac when given
 __device__ __forceinline__ double qp_pair_factor(const double *zfac, size_t b, int M, int Q, int m, int mp, const double *zm,
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(256) void qp_psi2_kernel(int N, int M, int Q, int T
     double *gm = zc + (size_t)QP_TILE * Q;                  // [Q]
     const int t = threadIdx.x, b = blockIdx.z, slab = blockIdx.y;
     int I, J;
-    qp_tile_ij(blockIdx.x, T, I, J);
+    dpgp_tile_ij(blockIdx.x, T, I, J);
     const int m0 = I * QP_TILE, c0 = J * QP_TILE;
     const double *zb = z + (size_t)b * M * Q;
     for (int k = t; k < QP_TILE * Q; k += 256) {
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(64) void qp_adjoint_kernel(int B, int N, int M, int
     const int tile_lo = slab * tiles_per_slab, tile_hi = min(T * (T + 1) / 2, tile_lo + tiles_per_slab);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
         int I, J;
-        qp_tile_ij(tile, T, I, J);
+        dpgp_tile_ij(tile, T, I, J);
         if (WEIGHTED && !pairs && I != J) continue;            // every weight of the wave is 0 and no Psi1 term here
         const int m0 = I * QP_TILE, c0 = J * QP_TILE;
         const int nr = min(QP_TILE, M - m0), nc = min(QP_TILE, M - c0);
@@ -380,7 +373,7 @@ __global__ __launch_bounds__(256) void qp_param_kernel(int B, int N, int M, int 
     const int b = blockIdx.z / qchunks, q0 = (blockIdx.z % qchunks) * QP_PCHUNK;
     const int nq = min(QP_PCHUNK, Q - q0);
     int I, J;
-    qp_tile_ij(blockIdx.x, T, I, J);
+    dpgp_tile_ij(blockIdx.x, T, I, J);
     const bool diag = I == J;
     const int m0 = I * QP_TILE, c0 = J * QP_TILE;
     {
@@ -713,18 +706,12 @@ size_t qp_adj_lds(int Q) {
     return sizeof(double) * ((size_t)3 * Q * QP_NT + (size_t)2 * QP_TILE * Q + QP_TILE * QP_HSTRIDE + Q);
 }
 
-int qp_set_lds(const void *fn, size_t lds) {
-    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
-    return DPGP_OK;
-}
-
 template <int KQ, bool WEIGHTED>
 int qp_launch_adjoint(const QpAdjPlan &p, int B, int N, int M, int Q, const double *z, const double *mu, const double *s,
                       const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g1,
                       const double *g2, double *part, hipStream_t st) {
     const size_t lds = qp_adj_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_adjoint_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qp_adjoint_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qp_adjoint_kernel<KQ, WEIGHTED>), dim3(p.nt, p.slabs, B * p.qchunks), dim3(QP_NT), lds, st, B, N, M, Q,
                        p.T, p.tiles_per_slab, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part);
@@ -737,7 +724,7 @@ int qp_launch_psi2(const QpStatsPlan &p, int B, int N, int M, int Q, const doubl
                    const double *gamma, const double *alpha, const double *zfac, const double *wt, double *part,
                    hipStream_t st) {
     const size_t lds = qp_stats_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_psi2_kernel<WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qp_psi2_kernel<WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qp_psi2_kernel<WEIGHTED>), dim3(p.tiles, p.slabs, B), dim3(256), lds, st, N, M, Q, p.T, p.n_per_slab,
                        z, mu, s, gamma, alpha, zfac, wt, part);
@@ -761,7 +748,7 @@ int qp_launch_param(const QpParamPlan &p, int B, int N, int M, int Q, const doub
                     const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g2,
                     double *part, hipStream_t st) {
     const size_t lds = qp_param_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_param_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qp_param_kernel<KQ, WEIGHTED>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qp_param_kernel<KQ, WEIGHTED>), dim3(p.tiles, p.slabs, B * p.qchunks), dim3(256), lds, st, B, N, M, Q,
                        p.T, p.n_per_slab, z, mu, s, gamma, alpha, zfac, wt, g2, part);
@@ -913,7 +900,7 @@ extern "C" int dpgp_qx_psi_param_adjoint_weighted_f64(int B, int N, int M, int Q
                       : qp_dispatch_param<false>(p, B, N, M, Q, z, mu, s, gamma, alpha, zfac, nullptr, g2, part, st);
     if (rc) return rc;
     const size_t lds1 = qp_param_psi1_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_param_psi1_kernel), lds1)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qp_param_psi1_kernel), lds1)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL(qp_param_psi1_kernel, dim3(p.T, p.slabs1, B), dim3(256), lds1, st, B, N, M, Q, p.n_per_slab1, z, mu, s, gamma,
                        alpha, g1, part1);
@@ -968,7 +955,7 @@ __global__ __launch_bounds__(256) void qg_psi2_kernel(int P, int N, int M, int Q
     const int kb = blockIdx.z / pchunks, p0 = (blockIdx.z % pchunks) * PC;
     const int np = min(PC, P - p0);
     int I, J;
-    qp_tile_ij(blockIdx.x, T, I, J);
+    dpgp_tile_ij(blockIdx.x, T, I, J);
     const int m0 = I * QP_TILE, c0 = J * QP_TILE;
     const double *zb = z + (size_t)kb * M * Q;
     for (int k = t; k < QP_TILE * Q; k += 256) {
@@ -1119,7 +1106,7 @@ __global__ __launch_bounds__(256) void qg_adjoint_kernel(int K, int P, int N, in
     const int tile_lo = slab * tiles_per_slab, tile_hi = min(T * (T + 1) / 2, tile_lo + tiles_per_slab);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
         int I, J;
-        qp_tile_ij(tile, T, I, J);
+        dpgp_tile_ij(tile, T, I, J);
         if (!wg_pairs && (I != J || !with_psi1)) continue;     // (workgroup-uniform) nothing weighted and no Psi1 term here
         const int m0 = I * QP_TILE, c0 = J * QP_TILE;
         const int nr = min(QP_TILE, M - m0), nc = min(QP_TILE, M - c0);
@@ -1249,7 +1236,7 @@ __global__ __launch_bounds__(256) void qg_param_kernel(int K, int P, int N, int 
     const int pl = pcn * PC, np = min(PC, P - pl), q0 = qc * QP_PCHUNK;
     const int nq = min(QP_PCHUNK, Q - q0);
     int I, J;
-    qp_tile_ij(blockIdx.x, T, I, J);
+    dpgp_tile_ij(blockIdx.x, T, I, J);
     const bool diag = I == J;
     const int m0 = I * QP_TILE, c0 = J * QP_TILE;
     {
@@ -1496,7 +1483,7 @@ template <int PC>
 int qg_launch_psi2(const QgStatsPlan &p, int K, int P, int N, int M, int Q, const double *z, const double *mu, const double *s,
                    const double *gamma, const double *alpha, const double *zfac, const double *wt, double *part, hipStream_t st) {
     const size_t lds = qg_stats_lds(Q, PC);
-    if (qp_set_lds(reinterpret_cast<const void *>(qg_psi2_kernel<PC>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qg_psi2_kernel<PC>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qg_psi2_kernel<PC>), dim3(p.s.tiles, p.s.slabs, K * p.pchunks), dim3(256), lds, st, P, N, M, Q, p.s.T,
                        p.s.n_per_slab, p.pchunks, z, mu, s, gamma, alpha, zfac, wt, part);
@@ -1509,7 +1496,7 @@ int qg_launch_adjoint(const QgAdjPlan &p, int K, int P, int N, int M, int Q, con
                       const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g1,
                       const double *g2, double *part, hipStream_t st) {
     const size_t lds = qg_adj_lds(Q, PC, p.nw);
-    if (qp_set_lds(reinterpret_cast<const void *>(qg_adjoint_kernel<KQ, PC>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qg_adjoint_kernel<KQ, PC>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qg_adjoint_kernel<KQ, PC>), dim3(p.nt, p.slabs, K * p.qchunks * p.pchunks), dim3(QP_NT * p.nw), lds, st,
                        K, P, N, M, Q, p.T, p.tiles_per_slab, p.pchunks, z, mu, s, gamma, alpha, zfac, wt, g1, g2, part);
@@ -1533,7 +1520,7 @@ int qg_launch_param(const QgParamPlan &p, int K, int P, int N, int M, int Q, con
                     const double *gamma, const double *alpha, const double *zfac, const double *wt, const double *g2,
                     double *part, hipStream_t st) {
     const size_t lds = qg_param_lds(Q, PC);
-    if (qp_set_lds(reinterpret_cast<const void *>(qg_param_kernel<KQ, PC>), lds)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qg_param_kernel<KQ, PC>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((qg_param_kernel<KQ, PC>), dim3(p.s.tiles, p.s.slabs, K * p.s.qchunks * p.pchunks), dim3(256), lds, st, K,
                        P, N, M, Q, p.s.T, p.s.n_per_slab, p.pchunks, z, mu, s, gamma, alpha, zfac, wt, g2, part);
@@ -1672,7 +1659,7 @@ extern "C" int dpgp_qx_psi_param_adjoint_grouped_f64(int K, int P, int N, int M,
                                : qg_dispatch_param<8>(p, K, P, N, M, Q, z, mu, s, gamma, alpha, zfac, w, g2, part, st);
     if (rc) return rc;
     const size_t lds1 = qp_param_psi1_lds(Q);
-    if (qp_set_lds(reinterpret_cast<const void *>(qp_param_psi1_kernel), lds1)) return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(qp_param_psi1_kernel), lds1)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL(qp_param_psi1_kernel, dim3(p.s.T, p.s.slabs1, K), dim3(256), lds1, st, K, N, M, Q, p.s.n_per_slab1, z, mu,
                        s, gamma, alpha, g1, part1);

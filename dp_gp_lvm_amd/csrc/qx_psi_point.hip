@@ -28,6 +28,7 @@
 // tiles are split over slabs only to fill the GPU when N K is small); a second launch adds the slabs in slab order and splits
 // the columns into tr and quad.  No atomics: the same inputs give the same bits.
 #include "internal.h"
+#include "qx_tile.h"
 
 #define PW_TILE 32
 #define PW_NP 64            // test points per workgroup: 4 waves x 16 MFMA rows
@@ -37,14 +38,6 @@
 #define PW_TARGET_WGS 512   // (256-thread workgroups: QP_TARGET_WGS / 2 of qx_psi.hip)
 
 namespace {
-
-// tile index -> (I, J), I <= J, row-major over the upper block triangle (as qp_tile_ij)
-__device__ __forceinline__ void pw_tile_ij(int idx, int T, int &I, int &J) {
-    int i = 0;
-    while (idx >= T - i) { idx -= T - i; ++i; }
-    I = i;
-    J = i + idx;
-}
 
 template <int CT, bool QREG>
 __global__ __launch_bounds__(256) void pw_kernel(int K, int G, int J, int N, int M, int Q, int T, int nchunks, int nct_plan,
@@ -70,7 +63,7 @@ __global__ __launch_bounds__(256) void pw_kernel(int K, int G, int J, int N, int
     const int nct = min(nct_plan, tiles16 - chunk * nct_plan), col0 = 16 * chunk * nct_plan;
     const int n0 = nt * PW_NP;
     const double *zk = z + (size_t)k * M * Q, *gk = gamma + (size_t)k * Q;
-    const double *rk = r + (size_t)k * M * J;
+    const double *rk = r + (size_t)k * M * J, *zf = zfac ? zfac + (size_t)k * M * M : nullptr;
     const double al = alpha[k];
     for (int e = t; e < PW_NP * Q; e += 256) {
         const int i = e / Q, q = e % Q;
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(256) void pw_kernel(int K, int G, int J, int N, int
     const int tile_lo = slab * tiles_per_slab, tile_hi = min(T * (T + 1) / 2, tile_lo + tiles_per_slab);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
         int I, Jt;
-        pw_tile_ij(tile, T, I, Jt);
+        dpgp_tile_ij(tile, T, I, Jt);
         const bool diag = I == Jt;
         const int m0 = I * PW_TILE, c0 = Jt * PW_TILE;
         const int nr = min(PW_TILE, M - m0), nc = min(PW_TILE, M - c0);
@@ -125,18 +118,7 @@ __global__ __launch_bounds__(256) void pw_kernel(int K, int G, int J, int N, int
         for (int e = t; e < PW_TILE * PW_TILE; e += 256) {
             const int rr = e / PW_TILE, cc = e % PW_TILE, m = m0 + rr, mp = c0 + cc;
             double f = 0.0;
-            if (rr < nr && cc < nc && (!diag || cc >= rr)) {
-                if (zfac) {
-                    f = zfac[((size_t)k * M + m) * M + mp];
-                } else {
-                    double a = 0.0;
-                    for (int q = 0; q < Q; ++q) {
-                        const double d = zk[(size_t)m * Q + q] - zk[(size_t)mp * Q + q];
-                        a = fma(gm[q] * d, d, a);
-                    }
-                    f = al * al * exp(-0.25 * a);
-                }
-            }
+            if (rr < nr && cc < nc && (!diag || cc >= rr)) f = dpgp_pair_factor(zf, M, Q, m, mp, zk, gm, al);
             sF[rr * PW_FSTRIDE + cc] = f;
         }
         for (int rr = 0; rr < nr; ++rr) {
@@ -253,9 +235,7 @@ int pw_launch(const PwPlan &p, int K, int G, int J, int N, int M, int Q, const d
               const double *gamma, const double *alpha, const double *zfac, const double *c, const double *r, double *part,
               hipStream_t st) {
     const size_t lds = pw_lds(Q, CT);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(pw_kernel<CT, QREG>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(pw_kernel<CT, QREG>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((pw_kernel<CT, QREG>), dim3((unsigned)((long)p.ntn * p.nchunks * K), p.slabs), dim3(256), lds, st, K, G, J, N,
                        M, Q, p.T, p.nchunks, p.nct, p.ntn, p.tiles_per_slab, z, mu, s, gamma, alpha, zfac, c, r, part);
@@ -468,9 +448,7 @@ size_t pm_lds(int Q, const PmPlan &p) {
 
 template <typename KERNEL, typename... ARGS>
 int pm_launch(KERNEL kernel, unsigned grid, size_t lds, hipStream_t st, ARGS... args) {
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(kernel), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, args...);
     DPGP_LAUNCH_CHECK();

@@ -12,9 +12,9 @@
 // E1 = alpha prod_q (gamma_q s_nq + 1)^-1/2 exp(-1/2 sum_q gr1_q (mu_nq - z_mq)^2), (T0, T1_q, T2_q) = (a1 . E1) (1, z_mq, z_mq^2):
 //   d_mu_nq += -gr1_q (mu T0 - T1_q),      d_s_nq += 1/2 (-gr1_q T0 + gr1_q^2 (mu^2 T0 - 2 mu T1_q + T2_q))
 // mu and z are taken relative to the workgroup's first test point (only mu - z enters), the exponential is dpgp_exp2_tab, and for
-// Q <= 16 the exponent is expanded per (point, phase) as in pl_kernel (psi_latent_adjoint.hip): two FMAs per q and pair.
+// Q <= 16 the exponent is expanded per (point, phase) (DpgpPointExponent, qx_tile.h): two FMAs per q and pair.
 //
-// Layout (that of pw_kernel and pl_kernel).  Workgroup (block of 64 test points, chunk of <= 16 CT of the G + J columns [gt | gq],
+// Layout (that of pw_kernel and pl_kernel; the pieces common to pl_kernel and this kernel are the helpers of qx_tile.h).  Workgroup (block of 64 test points, chunk of <= 16 CT of the G + J columns [gt | gq],
 // slab of kernels k; slab of pair tiles), 256 threads = 4 waves; a wave owns 16 points.  The lane (point i = lane & 15, kk = lane >> 4)
 // keeps its point's adjoints of the chunk, columns kk + 4 st, in registers: they are the B operand of GEMM 1, which is run
 // TRANSPOSED, T^T [16 pairs x 16 points] = A [16 pairs x columns] B [columns x 16 points] on v_mfma_f64_16x16x4, A read from LDS.
@@ -26,8 +26,9 @@
 // the forward operator); L is linear in the adjoints, so the chunks' partial (d_mu, d_s) simply add.
 // A wave whose 16 points have all-zero adjoints in the chunk skips the phase behind one wave-uniform branch; a zero adjoint that is
 // not skipped gives T = 0 and multiplies finite numbers: exactly 0.0 either way.
-// The accumulators go to part[slab][2][N][Q]; a second launch adds the slabs in slab order.  No atomics: the same bits on every run.
+// The accumulators go to part[slab][2][N][Q]; a second launch (launch_point_adjoint_slab_sum) adds the slabs in slab order.  No atomics: the same bits on every run.
 #include "internal.h"
+#include "qx_tile.h"
 
 #define PA_TILE 32
 #define PA_NP 64            // test points per workgroup: 4 waves x 16 MFMA rows
@@ -44,14 +45,6 @@ struct PaArgs {
     const double *z, *mu, *s, *gamma, *alpha, *zfac, *c, *r, *h, *gq, *gt;
     double *part;
 };
-
-// tile index -> (I, J), I <= J, row-major over the upper block triangle (as pw_tile_ij)
-__device__ __forceinline__ void pa_tile_ij(int idx, int T, int &I, int &J) {
-    int i = 0;
-    while (idx >= T - i) { idx -= T - i; ++i; }
-    I = i;
-    J = i + idx;
-}
 
 template <int CT, int MT, bool QREG>
 __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
@@ -111,17 +104,7 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
                 const double g = gk[q];
                 sg[q * PA_NP + i] = n0 + i < N ? g / fma(k2 * g, a.s[(size_t)n0 * Q + e], 1.0) : 0.0;
             }
-            if (t < PA_NP) {
-                double v = 0.0;
-                const int n = n0 + t;
-                if (n < N) {
-                    const double *sn = a.s + (size_t)n * Q;
-                    double l = 0.0;
-                    for (int q = 0; q < Q; ++q) l += log(fma(k2 * gk[q], sn[q], 1.0));
-                    v = (p2 ? 1.0 : al) * exp(-0.5 * l);
-                }
-                sc[t] = v;
-            }
+            if (t < PA_NP) sc[t] = dpgp_point_prefactor(n0 + t, N, Q, gk, a.s, k2, p2 ? 1.0 : al);
             for (int q = t; q < Q; q += 256) gm[q] = gk[q];
             // the lane's adjoints of the chunk: column col0 + kk + 4 st (the B operand of GEMM 1)
             double breg[NB];
@@ -143,24 +126,15 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
             const bool on = wave_live && __any(nz);            // (wave-uniform)
             if (!__syncthreads_or(on)) continue;               // (a barrier: sg / sc / gm are visible.  Workgroup-uniform)
             const double c2 = sc[pi];
-            // Q <= 16: the exponent kexp sum_q g_q (mu_q - zbar_q)^2 as  e0 + sum_q zbar_q (pw_q zbar_q + pl_q): two FMAs per q and pair
-            double pl[QREG ? PA_QR : 1], pw[QREG ? PA_QR : 1], e0 = 0.0;
-            if constexpr (QREG) {
-#pragma unroll
-                for (int q = 0; q < PA_QR; ++q) {
-                    const double mq = q < Q ? smu[q * PA_NP + pi] : 0.0;
-                    pw[q] = q < Q ? kexp * sg[q * PA_NP + pi] : 0.0;
-                    pl[q] = -2.0 * pw[q] * mq;
-                    e0 = fma(pw[q] * mq, mq, e0);
-                }
-            }
+            DpgpPointExponent<QREG ? PA_QR : 1> ex;            // (Q <= 16: the expanded exponent, two FMAs per q and pair)
+            if constexpr (QREG) ex.setup(Q, kexp, smu, sg, PA_NP, pi);
             f64x4 acc[MT];
 #pragma unroll
             for (int ct = 0; ct < MT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
             const int t_lo = p2 ? tile_lo : 0, t_hi = p2 ? tile_hi : a.T;
             for (int tile = t_lo; tile < t_hi; ++tile) {
                 int I = tile, Jt = tile;
-                if (p2) pa_tile_ij(tile, a.T, I, Jt);
+                if (p2) dpgp_tile_ij(tile, a.T, I, Jt);
                 const bool diag = I == Jt;
                 const int m0 = I * PA_TILE, c0 = Jt * PA_TILE;
                 const int nr = min(PA_TILE, M - m0), nc = min(PA_TILE, M - c0);
@@ -173,16 +147,7 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
                         const int rr = e / PA_TILE, cc = e % PA_TILE, m = m0 + rr, mp = c0 + cc;
                         double f = 0.0;
                         if (rr < nr && cc < nc && (!diag || cc >= rr)) {
-                            if (zf) {
-                                f = zf[(size_t)m * M + mp];
-                            } else {
-                                double d2 = 0.0;
-                                for (int q = 0; q < Q; ++q) {
-                                    const double d = zk[(size_t)m * Q + q] - zk[(size_t)mp * Q + q];
-                                    d2 = fma(gm[q] * d, d, d2);
-                                }
-                                f = al * al * exp(-0.25 * d2);
-                            }
+                            f = dpgp_pair_factor(zf, M, Q, m, mp, zk, gm, al);
                             if (m != mp) f *= 2.0;
                         }
                         sF[rr * PA_FSTRIDE + cc] = f;
@@ -246,11 +211,9 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
                             if (st2 < s_lo || st2 >= s_hi) continue;           // (wave-uniform)
                             const int cc = 4 * st2 + kk;
                             const double *zq = zz + (size_t)cc * Q;
-                            double e = e0;
+                            double e = 0.0;
                             if constexpr (QREG) {
-#pragma unroll
-                                for (int q = 0; q < PA_QR; ++q)
-                                    if (q < Q) e = fma(zq[q], fma(pw[q], zq[q], pl[q]), e);
+                                e = ex.at(Q, zq);
                             } else {
                                 for (int q = 0; q < Q; ++q) {
                                     const double d = smu[q * PA_NP + pi] - zq[q];
@@ -269,14 +232,7 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
             }
             // the phase's moments -> its contribution to (d_mu, d_s)
             __syncthreads();                                   // (every wave is done with zc / zb / sF / sW / sA: sM lies over them)
-            if (on) {
-#pragma unroll
-                for (int ct = 0; ct < MT; ++ct) {
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr)
-                        sM[(wave * 16 + Mfma<double>::row(lane, rr)) * MS + 16 * ct + (lane & 15)] = acc[ct][rr];
-                }
-            }
+            if (on) dpgp_spill_moment_tiles(acc, MT, sM, MS, wave, lane);
             __syncthreads();
             if (on) {
                 const double *mrow = sM + pi * MS;
@@ -297,26 +253,7 @@ __global__ __launch_bounds__(256) void pa_kernel(const PaArgs a) {
     if (!pt_live) return;
     const int n = n0 + pi;
     const size_t slab = ((size_t)kslab * a.pslabs + pslab) * a.nchunks + chunk;
-    double *pb = a.part + slab * 2 * (size_t)N * Q;
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int q = kk + 4 * j;
-        if (q < Q) {
-            pb[(size_t)n * Q + q] = dmu[j];
-            pb[((size_t)N + n) * Q + q] = dsv[j];
-        }
-    }
-}
-
-// d_mu[n][q], d_s[n][q]: the slabs added in slab order
-__global__ __launch_bounds__(256) void pa_reduce_kernel(size_t nq, int slabs, const double *__restrict__ part, double *__restrict__ d_mu,
-                                                        double *__restrict__ d_s) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= 2 * nq) return;
-    double acc = 0.0;
-    for (int sl = 0; sl < slabs; ++sl) acc += part[(size_t)sl * 2 * nq + e];
-    if (e < nq) d_mu[e] = acc;
-    else d_s[e - nq] = acc;
+    dpgp_write_point_partials(a.part + slab * 2 * (size_t)N * Q, n, N, Q, kk, dmu, dsv);
 }
 
 struct PaPlan { int T, tiles, ntn, nchunks, nct, ct, mt, kslabs, k_per_slab, pslabs, tiles_per_slab; };
@@ -337,18 +274,9 @@ PaPlan pa_plan(int K, int G, int J, int N, int M, int Q) {
     p.ct = p.nct <= 2 ? 2 : 4;
     const int mt = dpgp_ceil_div(1 + 2 * Q, 16);               // all 1 + 2Q moment columns in one pass: 2, 3, 5 or 9 tiles
     p.mt = mt <= 2 ? 2 : mt <= 3 ? 3 : mt <= 5 ? 5 : 9;
-    // enough workgroups to fill the GPU: first by slabs of kernels (no work is repeated), then by slabs of pair tiles
-    const long base = (long)p.ntn * p.nchunks;
-    long ks = (PA_TARGET_WGS + base - 1) / base;
-    if (const int v = dpgp_env_plan("DPGP_PA_K_SLABS", 1, K)) ks = v;
-    ks = ks < 1 ? 1 : (ks > K ? K : ks);
-    p.k_per_slab = dpgp_ceil_div(K, (int)ks);
-    p.kslabs = dpgp_ceil_div(K, p.k_per_slab);
-    long ps = (PA_TARGET_WGS + base * p.kslabs - 1) / (base * p.kslabs);
-    if (const int v = dpgp_env_plan("DPGP_PA_PAIR_SLABS", 1, p.tiles)) ps = v;
-    ps = ps < 1 ? 1 : (ps > p.tiles ? p.tiles : ps);
-    p.tiles_per_slab = dpgp_ceil_div(p.tiles, (int)ps);
-    p.pslabs = dpgp_ceil_div(p.tiles, p.tiles_per_slab);
+    // slabs of kernels k, then of pair tiles
+    const DpgpSlabSplit sp = dpgp_slab_split((long)p.ntn * p.nchunks, PA_TARGET_WGS, K, p.tiles, "DPGP_PA_K_SLABS", "DPGP_PA_PAIR_SLABS");
+    p.kslabs = sp.outer_slabs; p.k_per_slab = sp.outer_per_slab; p.pslabs = sp.pair_slabs; p.tiles_per_slab = sp.tiles_per_slab;
     return p;
 }
 
@@ -371,9 +299,7 @@ bool pa_shape_ok(int K, int G, int J, int N, int M, int Q) {
 template <int CT, int MT, bool QREG> int pa_launch(const PaPlan &p, PaArgs a, hipStream_t st) {
     const size_t lds = pa_lds(a.Q, CT, MT);
     a.region = (int)(lds / sizeof(double) - pa_fixed(a.Q));
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(pa_kernel<CT, MT, QREG>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPGP_ERR_LAUNCH;
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(pa_kernel<CT, MT, QREG>), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL((pa_kernel<CT, MT, QREG>), dim3((unsigned)((long)p.ntn * p.nchunks * p.kslabs), p.pslabs), dim3(256), lds, st, a);
     DPGP_LAUNCH_CHECK();
@@ -431,10 +357,5 @@ extern "C" int dpgp_qx_psi_pointwise_adjoint_f64(int K, int G, int J, int N, int
     a.part = static_cast<double *>(ws);
     const int rc = p.ct == 2 ? pa_dispatch<2>(p, a, st) : pa_dispatch<4>(p, a, st);
     if (rc) return rc;
-    const size_t nq = (size_t)N * Q;
-    DPGP_PRELAUNCH();
-    hipLaunchKernelGGL(pa_reduce_kernel, dim3((unsigned)((2 * nq + 255) / 256)), dim3(256), 0, st, nq, p.kslabs * p.pslabs * p.nchunks,
-                       (const double *)a.part, d_mu, d_s);
-    DPGP_LAUNCH_CHECK();
-    return DPGP_OK;
+    return launch_point_adjoint_slab_sum((size_t)N * Q, p.kslabs * p.pslabs * p.nchunks, a.part, d_mu, d_s, st);
 }
