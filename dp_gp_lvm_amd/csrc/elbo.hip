@@ -979,11 +979,14 @@ __global__ void model_pack_kernel(const double *__restrict__ fhat, const double 
 //   blocks 1..nlb      : logits rows (thread = one mask group of output dims)
 //   remaining blocks   : x_mean, x_var_raw, x_u element-wise
 // ---------------------------------------------------------------------------------------------------------------
+// trigamma for x > 0: recurrence up to x >= 10, then the asymptotic series to x^-15 (first omitted term 3617/510 x^-17: 7e-17 at 10;
+// relative error < 1e-15 everywhere, tests/test_model_glue_refs.py; stopping at 6 and x^-9 left 1e-9 in d_g1_raw, d_g2_raw, d_w_raw)
 __device__ double trigamma_d(double x) {
     double r = 0.0;
-    while (x < 6.0) { r += 1.0 / (x * x); x += 1.0; }
+    while (x < 10.0) { r += 1.0 / (x * x); x += 1.0; }
     const double f = 1.0 / (x * x);
-    return r + 1.0 / x + 0.5 * f + (1.0 / x) * f * (1.0 / 6.0 - f * (1.0 / 30.0 - f * (1.0 / 42.0 - f * (1.0 / 30.0))));
+    return r + 1.0 / x + 0.5 * f + (1.0 / x) * f * (1.0 / 6.0 - f * (1.0 / 30.0 - f * (1.0 / 42.0 - f * (1.0 / 30.0 - f * (
+               5.0 / 66.0 - f * (691.0 / 2730.0 - f * (7.0 / 6.0)))))));
 }
 __device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
 
@@ -1031,6 +1034,21 @@ __global__ __launch_bounds__(256) void model_backward_kernel(
         } else {
             c1[t] = 0.0;
             c2inc[t] = 0.0;
+        }
+    }
+    // block 0 needs the trigammas of the same arguments at its very end.  One per thread (thread = (stick k, argument f), then w1), as
+    // prepare does for its digammas, and counted from the LAST thread down, so that at T <= 22 they sit in the wave furthest from the
+    // digamma threads and run beside them: each is a chain of up to ten dependent fp64 divisions, and behind the sums over D, three in a
+    // row per stick, they cost this launch 4 us of 52 at T = 8; one per thread there still 0.5 us
+    __shared__ double tg[3][PREP_MAX_T], tg_w;
+    if (blockIdx.x == 0) {
+        const int u = 255 - t;
+        if (u < 3 * (T - 1)) {
+            const int k = u / 3, f = u - 3 * k;
+            const double g1 = softplus_d(g1_raw[k]), g2 = softplus_d(g2_raw[k]);
+            tg[f][k] = trigamma_d(f == 0 ? g1 : (f == 1 ? g2 : g1 + g2));
+        } else if (u == 3 * (T - 1) && add_constants) {
+            tg_w = trigamma_d(softplus_d(w_raw[0]));
         }
     }
     __syncthreads();
@@ -1093,7 +1111,7 @@ __global__ __launch_bounds__(256) void model_backward_kernel(
             double stail = 0.0;
             for (int kk = k + 1; kk < T; ++kk) stail += sphi_s[kk];
             const double g1 = softplus_d(g1_raw[k]), g2 = softplus_d(g2_raw[k]);
-            const double t1 = trigamma_d(g1), t2 = trigamma_d(g2), t12 = trigamma_d(g1 + g2);
+            const double t1 = tg[0][k], t2 = tg[1][k], t12 = tg[2][k];
             double e1 = sphi * (t1 - t12) - stail * t12, e2 = -sphi * t12 + stail * (t2 - t12);
             if (add_constants) {
                 const double w1 = softplus_d(w_raw[0]), w2 = softplus_d(w_raw[1]), r = w1 / w2 - 1.0;
@@ -1106,7 +1124,7 @@ __global__ __launch_bounds__(256) void model_backward_kernel(
         if (t == 0) {
             double e1 = 0.0, e2 = 0.0;
             if (add_constants) {
-                const double w1 = softplus_d(w_raw[0]), w2 = softplus_d(w_raw[1]), tw = trigamma_d(w1), sc2 = c2cum[T];
+                const double w1 = softplus_d(w_raw[0]), w2 = softplus_d(w_raw[1]), tw = tg_w, sc2 = c2cum[T];
                 e1 = (T - 1.0) * tw + sc2 / w2 + (s1 - 1.0) * tw - s2 / w2 + 1.0 + (1.0 - w1) * tw;
                 e2 = -(T - 1.0) / w2 - (w1 / (w2 * w2)) * sc2 - (s1 - 1.0) / w2 + s2 * w1 / (w2 * w2) - 1.0 / w2;
             }
@@ -1121,6 +1139,14 @@ __global__ __launch_bounds__(256) void model_backward_kernel(
     if (r > r1) return;
     const int dlo = max(r * mask_size, d_offset) - d_offset, dhi = min((r + 1) * mask_size, d_offset + D) - d_offset;
     for (int k = 0; k < T; ++k) d_logits[(size_t)r * T + k] = 0.0;
+    // log phi from the logits, in the arithmetic of model_prepare_kernel: log of the stored phi is -inf where phi underflowed (logit
+    // spread above ~745) and 0 * inf made the row's gradient NaN; its limit, which this gives, is 0
+    const double *lr = logits + (size_t)r * T;
+    double mx = lr[0];
+    for (int k = 1; k < T; ++k) mx = fmax(mx, lr[k]);
+    double zsum = 0.0;
+    for (int k = 0; k < T; ++k) zsum += exp(lr[k] - mx);
+    const double lz = log(zsum);
     for (int d = dlo; d < dhi; ++d) {
         const double *ph = phi + (size_t)d * T;
         const double *dg = df_dgamma + (size_t)(df_dphi ? 0 : d) * Q;
@@ -1131,7 +1157,7 @@ __global__ __launch_bounds__(256) void model_backward_kernel(
             else
                 for (int q = 0; q < Q; ++q) mix += dg[q] * gat[k * Q + q];
             // d DP objective / d phi = -( [k < T-1] c1_k + sum_{k' < k} c2_k' - log phi - 1 )
-            return -mix - (c1[k] + c2cum[k] - log(ph[k]) - 1.0);
+            return -mix - (c1[k] + c2cum[k] - (lr[k] - mx - lz) - 1.0);
         };
         double sdot = 0.0;
         for (int k = 0; k < T; ++k) sdot += ph[k] * gk(k);
