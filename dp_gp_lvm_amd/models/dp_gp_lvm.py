@@ -724,6 +724,22 @@ def dp_gp_lvm(y_train,
                                      torch.zeros((k, 1), dtype=torch.int32, device=device))
         return marg, here, prior_unseen
 
+    def _column_marginals(cols):
+        """The output dims `cols` as the K = len(cols) kernels of a marginals._Marginals with one column and one pattern each
+        (every column is its own mixed kernel): only these kernels are gathered, never all D.  A column never observed in
+        training keeps c = 0 and r = 0: its posterior is its prior."""
+        z, gu, au, bu, c, r, here, _, _ = _frozen_columns(cols)
+        idx = torch.as_tensor(np.asarray(cols), device=device)
+        k, m = len(cols), z.shape[0]
+        f64 = lambda a: a.to(TORCH_DTYPE).contiguous()
+        g_all, a_all, b_all = f64(buf['gamma'][idx]), f64(buf['alpha'][:, 0][idx]), f64(buf['beta'][:, 0][idx])
+        c_all = torch.zeros((k, m, m), dtype=TORCH_DTYPE, device=device)
+        r_all = torch.zeros((k, m), dtype=TORCH_DTYPE, device=device)
+        if int(here.numel()):
+            c_all[here], r_all[here] = c, r
+        return _marginals._Marginals(z[None].expand(k, -1, -1), g_all, a_all, b_all, None, c_all[:, None], r_all[:, :, None],
+                                     torch.zeros((k, 1), dtype=torch.int32, device=device), all_seen=True)
+
     def _geometry_columns(columns):
         cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
         assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
@@ -1074,6 +1090,50 @@ def dp_gp_lvm(y_train,
             assert not split, 'magnification is not built for a model sharded over a process group'
             with torch.no_grad():
                 return _marginals.magnification(DP_GP_LVM.latent_metric(x, columns))
+
+        @staticmethod
+        def predictive_covariance(x, columns=None, noise=False):
+            """[len(columns) x N* x N*]: the joint posterior covariance of the noise-free functions of the output dims `columns`
+            (default: all D) at the DETERMINISTIC latent points x [N* x Q] (numpy or torch), every column under its own mixed
+            kernel,
+                cov_d(x, x') = alpha_d exp(-1/2 sum_q gamma_dq (x_q - x'_q)^2) - k_d(x)^T (K_d^-1 - P_d) k_d(x')
+            (models/marginals.py): one call of ops.ard_rbf_point_cov over K = len(columns) kernels; only the chosen columns'
+            kernels are formed.  Its diagonal plus 1/beta_d is predictive_marginals(x, 0)'s variance; noise=True adds 1/beta_d
+            on the diagonal.  A column never observed in training gets its prior gram.  Exactly symmetric.  The array is
+            J N*^2 doubles (here every column has its own matrix; in the other models columns of one (kernel, pattern) repeat the
+            same one).  Works on a model trained on complete data and on one trained with observed=.  fp64, torch.no_grad.  Not
+            built for a model sharded over a process group: AssertionError."""
+            assert not split, 'predictive_covariance is not built for a model sharded over a process group'
+            cols = _geometry_columns(columns)
+            xp = _marginals.points_arg(x, num_latent_dims, device)
+            evaluate()
+            with torch.no_grad():
+                marg = _column_marginals(cols)
+                cov = marg.covariance(xp)[:, 0]
+                return _marginals.with_noise(cov, 1.0 / marg.beta) if noise else cov
+
+        @staticmethod
+        def sample_functions(x, num_samples=1, columns=None, noise=False, jitter=_marginals.DEFAULT_SAMPLE_JITTER, seed=0,
+                             draws=None):
+            """[S x N* x len(columns)]: S joint draws of the output dims `columns` (default: all D) at the latent points x
+            [N* x Q]: mean + L_d xi with L_d L_d^T = predictive_covariance_d + jitter alpha_d I (+ 1/beta_d I with noise), xi
+            standard normal from a device torch.Generator seeded with `seed`, or given as `draws` [S x N* x len(columns)].  One
+            ops.potrf_batched call and one ops.matmul over the columns' kernels, whatever their number; one host read,
+            potrf's info at the end: FloatingPointError if a factorisation failed (raise `jitter` or set noise=True).  The
+            default jitter, 1e-6 alpha_d, is a choice, not a measurement: the gram of nearby points has its smallest eigenvalue
+            below rounding and the factorisation needs a shift well above eps N* lambda_max ~ 1e-12 alpha; 1e-6 alpha is far
+            above that and far below any 1/beta the models train to.  fp64, torch.no_grad.  Not built for a model sharded over a
+            process group: AssertionError."""
+            assert not split, 'sample_functions is not built for a model sharded over a process group'
+            cols = _geometry_columns(columns)
+            xp = _marginals.points_arg(x, num_latent_dims, device)
+            evaluate()
+            with torch.no_grad():
+                xi = _marginals.standard_draws(draws, num_samples, xp.shape[0], cols.size, _marginals.draw_generator(seed, device),
+                                               device)
+                f, info = _column_marginals(cols).sample(xp, xi.permute(2, 0, 1)[:, :, :, None], None, noise, jitter)
+                _marginals.raise_if_not_factorised(info)
+                return f[:, :, :, 0].permute(1, 2, 0).contiguous()
 
         @staticmethod
         def curve_energy(curve, columns=None, return_gradient=False):
@@ -1902,6 +1962,56 @@ def dp_gp_lvm_t(y_train,
             factorisation of G."""
             with torch.no_grad():
                 return _marginals.magnification(DP_GP_LVM_T.latent_metric(x, columns))
+
+        @staticmethod
+        def predictive_covariance(x, columns=None, noise=False):
+            """[len(columns) x N* x N*]: the covariance of the output dims `columns` (default: all D) at the DETERMINISTIC latent
+            points x [N* x Q] (numpy or torch) under the mixture over the atoms,
+                sum_t phi_td (cov_t,p(d) + m_td m_td^T) - m_d m_d^T
+            with cov_t,p the joint posterior covariance of the noise-free function under atom t and training row pattern p
+            (frozen_bound_t._MomentsT.covariance; one call of ops.ard_rbf_point_cov on the T atoms).  noise=True adds 1/beta_t to
+            every atom's diagonal; the diagonal is then predictive_marginals(x, 0)'s variance.  A column never observed in
+            training gets the mixture of the atoms' prior grams.  The array is J N*^2 doubles (and T times that while it is
+            formed); under one atom the columns of one pattern repeat the same matrix.  Works on a model trained on complete data
+            and on one trained with observed=.  fp64, torch.no_grad."""
+            cols = _columns_arg(columns)
+            with torch.no_grad():
+                return _moments().covariance(_marginals.points_arg(x, num_latent_dims, device), cols, noise)
+
+        @staticmethod
+        def sample_functions(x, num_samples=1, columns=None, noise=False, jitter=_marginals.DEFAULT_SAMPLE_JITTER, seed=0,
+                             draws=None, atoms=None):
+            """[S x N* x len(columns)]: S joint draws of the output dims `columns` (default: all D) at the latent points x
+            [N* x Q].  Every (sample, column) first draws its atom t from phi_:d (a device torch.Generator seeded with `seed`), or
+            takes it from `atoms` [S x len(columns)] (long), then draws from that atom's posterior: m_td + L xi with
+            L L^T = cov_t,p(d) + jitter alpha_t I (+ 1/beta_t I with noise), xi standard normal from the same generator, or
+            given as `draws` [S x N* x len(columns)].  One ops.potrf_batched call over the (atom, pattern) pairs and one
+            ops.matmul, whatever the number of columns; one host read, potrf's info at the end: FloatingPointError if a
+            factorisation failed (raise `jitter` or set noise=True).  The default jitter, 1e-6 alpha_t, is a choice, not a
+            measurement: the gram of nearby points has its smallest eigenvalue below rounding and the factorisation needs a
+            shift well above eps N* lambda_max ~ 1e-12 alpha; 1e-6 alpha is far above that and far below any 1/beta the models
+            train to.  fp64, torch.no_grad."""
+            cols = _columns_arg(columns)
+            with torch.no_grad():
+                xp = _marginals.points_arg(x, num_latent_dims, device)
+                gen = _marginals.draw_generator(seed, device)
+                if atoms is not None:
+                    at = np.asarray(atoms.detach().cpu() if torch.is_tensor(atoms) else atoms, dtype=np.int64)
+                    assert at.ndim == 2 and at.shape[1] == cols.numel() and at.min() >= 0 and at.max() < truncation_level, \
+                        'atoms must be [S x len(columns)] atom indices in [0, T)'
+                    atoms = torch.as_tensor(at, device=device)
+                mom = _moments()
+                if atoms is None:                                         # (the atoms first, then the normal draws: one stream)
+                    count = int(num_samples) if draws is None else len(draws)
+                    assert count >= 1, 'num_samples must be at least 1'
+                    phi = mom.phit.index_select(1, cols)
+                    atoms = torch.multinomial(phi.transpose(0, 1).contiguous(), count, replacement=True,
+                                              generator=gen).transpose(0, 1)
+                xi = _marginals.standard_draws(draws, atoms.shape[0], xp.shape[0], cols.numel(), gen, device)
+                assert atoms.shape[0] == xi.shape[0], 'atoms and draws must hold the same number of samples'
+                f, info = mom.sample(xp, xi, cols, atoms, noise, jitter)
+                _marginals.raise_if_not_factorised(info)
+                return f
 
         @staticmethod
         def curve_energy(curve, columns=None, return_gradient=False):

@@ -5,6 +5,7 @@ only q(X*) moves; the moments come from the per-point Psi2 contractions of ops.q
 """
 import math
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -87,8 +88,10 @@ class _MomentsT:
         self.r = lay.to_columns(r.reshape(t, lay.p, m, lay.dmax))                                  # [T, M, D]
         self.c = cm.reshape(t, lay.p, m, m).contiguous()
         pattern = torch.full((lay.d,), -1, dtype=torch.long, device=train.device)
+        self.pattern_host = np.full(lay.d, -1, dtype=np.int64)
         for i, (cols, _) in enumerate(lay.groups):
             pattern[torch.as_tensor(cols, device=train.device)] = i
+            self.pattern_host[np.asarray(cols, dtype=np.int64)] = i
         self.pattern = pattern                                                                     # [D]: p(d), -1 never observed
         self.z_t, self.zfac = c['z'], c['zfac']
         self.z, self.gat, self.aat, self.bat, self.phit = z, gat, aat, bat, phit
@@ -108,7 +111,32 @@ class _MomentsT:
     def _atoms(self):
         """The T atoms as the kernels of a marginals._Marginals: every atom sees all D columns, column d on its pattern p(d)."""
         gidx = self.pattern.to(torch.int32)[None].expand(self.r.shape[0], -1)
-        return _Marginals(self.z_t, self.gat, self.aat, self.bat, self.zfac, self.c, self.r, gidx)
+        return _Marginals(self.z_t, self.gat, self.aat, self.bat, self.zfac, self.c, self.r, gidx,
+                          gidx_host=np.broadcast_to(self.pattern_host, (self.r.shape[0], self.pattern_host.size)))
+
+    def covariance(self, x, cols, noise=False):
+        """[len(cols) x N* x N*]: the covariance of the mixture over the atoms of the columns' functions at the deterministic
+        latent points x,
+            sum_t phi_td (cov_t,p(d) + m_td m_td^T) - m_d m_d^T,     m_td = k_t(x)^T r_td [N*],   m_d = sum_t phi_td m_td
+        cov_t,p the joint posterior covariance under atom t and pattern p (marginals._Marginals.covariance on the T atoms: one
+        call of ops.ard_rbf_point_cov), with 1/beta_t on its diagonal when `noise`: mixture_moments' variance on the diagonal."""
+        atoms = self._atoms()
+        cov_t = atoms.covariance(x, cols)                                                          # [T, J, N*, N*]
+        if noise:
+            cov_t = cov_t + (1.0 / self.bat).reshape(-1, 1, 1, 1) * torch.eye(x.shape[0], dtype=TORCH_DTYPE, device=x.device)
+        mean_t = atoms.at(x, torch.zeros_like(x), cols)[0].transpose(1, 2)                         # [T, J, N*]
+        phi = self.phit.index_select(1, cols)                                                      # [T, J]
+        mean = torch.sum(phi[:, :, None] * mean_t, dim=0)                                          # [J, N*]
+        second = cov_t + mean_t[:, :, :, None] * mean_t[:, :, None, :]
+        return torch.sum(phi[:, :, None, None] * second, dim=0) - mean[:, :, None] * mean[:, None, :]
+
+    def sample(self, x, xi, cols, atoms, noise, jitter):
+        """(f [S x N* x J], info): f[s, :, j] = m_tj + L_t,p(j) xi[s, :, j] with t = atoms[s, j] [S x J] (long), the atom of
+        (sample, column).  The draws of every atom come from ONE marginals._Marginals.sample on the T atoms (one potrf_batched
+        over the (atom, pattern) pairs, one matmul); a gather keeps each (sample, column)'s own atom."""
+        f_t, info = self._atoms().sample(x, xi, cols, noise, jitter)                               # [T, S, N*, J]
+        s, n, j = f_t.shape[1], f_t.shape[2], f_t.shape[3]
+        return torch.gather(f_t, 0, atoms[None, :, None, :].expand(1, s, n, j))[0], info
 
     def jacobian(self, x, cols):
         """[N* x len(cols) x Q]: the mean of the mixture's Jacobian rows at the deterministic latent points x,

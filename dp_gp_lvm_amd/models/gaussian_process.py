@@ -606,6 +606,36 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
                                              num_iterations, learning_rate, init)
 
         @staticmethod
+        def predictive_covariance(x, columns=None, noise=False):
+            """[len(columns) x N* x N*]: the joint posterior covariance of the noise-free functions of the output dims `columns`
+            (default: all D) at the DETERMINISTIC latent points x [N* x Q] (numpy or torch),
+                cov_d(x, x') = alpha exp(-1/2 sum_q gamma_q (x_q - x'_q)^2) - k(x)^T (K_uu^-1 - P_p(d)) k(x')
+            (models/marginals.py; one call of ops.ard_rbf_point_cov): the off-diagonal that predictive_marginals leaves out.  Its
+            diagonal plus 1/beta is predictive_marginals(x, 0)'s variance; noise=True adds 1/beta on the diagonal.  A column never
+            observed in training gets the prior gram.  Exactly symmetric.  The array is J N*^2 doubles, and columns of one training
+            row pattern repeat the same matrix.  Works on a model trained on complete data and on one trained with observed=.
+            fp64, torch.no_grad."""
+            cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+            with torch.no_grad():
+                return _marginals.covariance_of(_train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_), cols, noise)
+
+        @staticmethod
+        def sample_functions(x, num_samples=1, columns=None, noise=False, jitter=_marginals.DEFAULT_SAMPLE_JITTER, seed=0,
+                             draws=None):
+            """[S x N* x len(columns)]: S joint draws of the output dims `columns` (default: all D) at the latent points x
+            [N* x Q]: mean + L xi with L L^T = predictive_covariance + jitter alpha I (+ 1/beta I with noise), xi standard normal
+            from a device torch.Generator seeded with `seed`, or given as `draws` [S x N* x len(columns)].  One
+            ops.potrf_batched call over the training row patterns and one ops.matmul, whatever the number of columns; one host
+            read, potrf's info at the end: FloatingPointError if a factorisation failed (raise `jitter` or set noise=True).
+            The default jitter, 1e-6 alpha, is a choice, not a measurement: the gram of nearby points has its smallest eigenvalue
+            below rounding and the factorisation needs a shift well above eps N* lambda_max ~ 1e-12 alpha; 1e-6 alpha is far
+            above that and far below any 1/beta the models train to.  fp64, torch.no_grad."""
+            cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+            with torch.no_grad():
+                return _marginals.samples_of(_train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_), cols, num_samples,
+                                             noise, jitter, seed, draws)
+
+        @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
                                  observed=None, marginal_variance=False):
             """y_test [N* x Do] holds the FIRST Do < D output dims of the test points (gaussian_process.py:405-538).  Returns
@@ -1111,6 +1141,39 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                 train, xp = _train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_)
                 out = [train[v].metric(xp)[0] for v in vs]
             return torch.sum(torch.stack(out), dim=0) if total else out
+
+        @staticmethod
+        def predictive_covariance(x, views=None, columns=None, noise=False):
+            """One array [len(columns[i]) x N* x N*] per view of `views` (default: all V, in order): the joint posterior covariance
+            of the view's noise-free functions at the deterministic latent points x [N* x Q], as
+            bayesian_gp_lvm.predictive_covariance with the view's own kernel.  columns: one list of the view's columns per entry
+            of `views` (default: all D_v).  noise=True adds 1/beta_v on the diagonal.  Each array is J N*^2 doubles, and columns
+            of one training row pattern repeat the same matrix."""
+            vs = _views_arg(views)
+            assert columns is None or len(columns) == len(vs), 'columns must hold one list per view of `views`'
+            with torch.no_grad():
+                train, xp = _train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_)
+                return [_marginals.covariance_of(
+                    train[v], xp, _marginals.columns_arg(None if columns is None else columns[i], num_dimensions[v], dev_), noise)
+                    for i, v in enumerate(vs)]
+
+        @staticmethod
+        def sample_functions(x, num_samples=1, views=None, columns=None, noise=False, jitter=_marginals.DEFAULT_SAMPLE_JITTER,
+                             seed=0, draws=None):
+            """One array [S x N* x len(columns[i])] per view of `views` (default: all V, in order): joint draws of the view's output
+            dims at the latent points x, as bayesian_gp_lvm.sample_functions (the default jitter and its reasons there).  Every
+            view draws from a generator seeded with `seed`; draws: one array [S x N* x len(columns[i])] per view.  The views are
+            independent given x."""
+            vs = _views_arg(views)
+            assert columns is None or len(columns) == len(vs), 'columns must hold one list per view of `views`'
+            assert draws is None or len(draws) == len(vs), 'draws must hold one array per view of `views`'
+            with torch.no_grad():
+                train, xp, infos = _train_marginals(), _marginals.points_arg(x, num_latent_dims, dev_), []
+                out = [_marginals.samples_of(
+                    train[v], xp, _marginals.columns_arg(None if columns is None else columns[i], num_dimensions[v], dev_),
+                    num_samples, noise, jitter, seed, None if draws is None else draws[i], infos) for i, v in enumerate(vs)]
+                _marginals.raise_if_not_factorised(torch.cat(infos))
+            return out
 
         @staticmethod
         def magnification(x, views=None):

@@ -16,6 +16,11 @@ The same training side gives the geometry of the map from latent space to data a
     mean m_d(x) = b(x)^T r_d [Q],     covariance Sigma_d(x) = alpha diag(gamma) - b(x)^T (K_uu^-1 - P_p(d)) b(x) [Q x Q]
 (d^2 k(x, x') / dx_q dx'_q' = alpha gamma_q delta_qq' at x' = x; the noise-free function: no 1/beta), and the expected metric over
 a set of columns is G(x) = sum_d (m_d m_d^T + Sigma_d); sqrt(det G) is the magnification factor.  _Marginals.jacobian / .metric.
+
+And the JOINT posterior of column d's noise-free function at several deterministic latent points: mean k(x)^T r_d and
+    cov_d(x, x') = alpha exp(-1/2 sum_q gamma_q (x_q - x'_q)^2) - k(x)^T (K_uu^-1 - P_p(d)) k(x')
+whose diagonal is var(n,d) at s = 0 less 1/beta: _Marginals.pattern_covariance / .covariance (ops.ard_rbf_point_cov, or the composed
+form where it is faster) and .sample (one batched Cholesky over the (kernel, pattern) pairs, one batched product).
 """
 import numpy as np
 import torch
@@ -29,8 +34,13 @@ class _Marginals:
     """K kernels' training side: z [K,M,Q], gamma [K,Q], alpha [K], beta [K], zfac [K,M,M] or None, c [K,G,M,M] = K_uu^-1 - P per
     pattern, r [K,M,D] the posterior weights per output column and gidx [K,D] (int32) each column's pattern, -1: never observed."""
 
-    def __init__(self, z, gamma, alpha, beta, zfac, c, r, gidx):
+    def __init__(self, z, gamma, alpha, beta, zfac, c, r, gidx, all_seen=False, gidx_host=None):
+        """all_seen: the caller knows (on the host) that no column has gidx < 0; pattern_covariance then adds no prior pattern.
+        gidx_host: gidx as a NumPy array, where the builder has it: pattern_covariance then runs only the patterns that the chosen
+        columns touch, planned on the host without reading the device."""
         self.z, self.gamma, self.alpha, self.beta = z.contiguous(), gamma.contiguous(), alpha.contiguous(), beta.contiguous()
+        self.all_seen = bool(all_seen)
+        self.gidx_host = None if gidx_host is None else np.asarray(gidx_host, dtype=np.int64).reshape(tuple(gidx.shape))
         self.zfac = None if zfac is None else zfac.contiguous()
         self.c, self.r, self.gidx = c.contiguous(), r.contiguous(), gidx.contiguous()
 
@@ -88,6 +98,75 @@ class _Marginals:
         w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0)
         return e + torch.sum(v * v * w, dim=1), dx, dv + 2.0 * v * w
 
+    def _patterns(self, cols):
+        """(c [K, G', M, M], slot [K, J] long): the patterns to evaluate and, per kernel and column, its place among them.  With
+        gidx_host (and host columns: columns_arg's .host) G' counts only the patterns that `cols` touch, in ascending order, plus
+        one with c = 0, whose covariance is the prior gram, if a chosen column was never observed in training (gidx < 0); planned
+        on the host, the places go to the device by a copy that nothing waits for.  Without it: all G patterns, plus the prior
+        pattern unless all_seen."""
+        k, g, m = self.c.shape[0], self.c.shape[1], self.c.shape[2]
+        zero = lambda: torch.zeros((k, 1, m, m), dtype=TORCH_DTYPE, device=self.c.device)
+        host = None if self.gidx_host is None else \
+            (self.gidx_host if cols is None else (None if getattr(cols, 'host', None) is None else self.gidx_host[:, cols.host]))
+        if host is not None:
+            used = np.unique(host[host >= 0])
+            prior = bool((host < 0).any()) or used.size == 0
+            place = np.full(g + 1, used.size, dtype=np.int64)                # (never observed: the prior pattern, last)
+            place[used] = np.arange(used.size)
+            c = self.c if used.size == g else self.c.index_select(1, torch.as_tensor(used, device=self.c.device))
+            c = torch.cat([c, zero()], dim=1) if prior else c
+            return c.contiguous(), torch.as_tensor(place[np.where(host < 0, g, host)], device=self.c.device)
+        gidx = self.gidx if cols is None else self.gidx.index_select(1, cols)
+        slot = gidx.to(torch.long)
+        if self.all_seen:
+            return self.c, slot
+        return torch.cat([self.c, zero()], dim=1), torch.where(slot < 0, torch.full_like(slot, g), slot)
+
+    def pattern_covariance(self, x, cols=None):
+        """(cov [K, G', N*, N*], slot [K, J]): the joint posterior covariance of the noise-free functions of every (kernel,
+        pattern that `cols` touch: _patterns) at the deterministic latent points x [N*, Q],
+            cov_kg(x, x') = alpha_k exp(-1/2 sum_q gamma_kq (x_q - x'_q)^2) - k_k(x)^T c[k, g] k_k(x'),
+        by ONE call of ops.ard_rbf_point_cov over the K kernels and their patterns (at many points by composed_covariance where
+        composed_is_faster's cost model says so); the last pattern may be the prior gram (c = 0: the operator's
+        quadratic form is then an exact 0).  Column cols[j] of kernel k has the matrix cov[k, slot[k, j]]; columns of
+        one (kernel, pattern) share it.  Exactly symmetric matrices; 1/beta does not enter."""
+        c, slot = self._patterns(cols)
+        if composed_is_faster(c.shape[0], c.shape[1], x.shape[0], c.shape[2]):
+            return composed_covariance(self.z, x.contiguous(), self.gamma, self.alpha, c), slot
+        return ops.ard_rbf_point_cov(self.z, x.contiguous(), self.gamma, self.alpha, c), slot
+
+    def covariance(self, x, cols=None):
+        """[K, J, N*, N*]: pattern_covariance's matrices laid out per column, cov[k, j] = the joint posterior covariance of
+        column cols[j] under kernel k at the points x (K J N*^2 doubles: columns of one pattern repeat the same matrix)."""
+        cov, slot = self.pattern_covariance(x, cols)
+        return cov[torch.arange(cov.shape[0], device=cov.device)[:, None], slot]
+
+    def sample(self, x, xi, cols=None, noise=False, jitter=1e-6):
+        """(f [K, S, N*, J], info): joint draws of the columns `cols` at the points x [N*, Q] from standard normal draws xi
+        [S, N*, J] (shared by the kernels) or [K, S, N*, J],
+            f[k, s, :, j] = mean_kj + L_k,g(j) xi[s, :, j],     L L^T = cov_kg + (jitter alpha_k (+ 1/beta_k with noise)) I
+        pattern_covariance's matrices are factorised by ONE ops.potrf_batched call over the K G' (kernel, pattern)
+        pairs, and ONE ops.matmul, batched over the pairs, applies every factor to all S J draw columns; a gather then keeps,
+        for column j, the product with its own pattern's factor.  This costs G' times the flops of a product grouped by
+        pattern and needs no knowledge of the groups on the host: the number of launches does not depend on the number of
+        columns, and nothing here synchronises.  info [K G'] is potrf's (non-zero: that matrix is not positive definite
+        at this jitter); reading it is the caller's."""
+        cov, slot = self.pattern_covariance(x, cols)
+        k, g1, n = cov.shape[0], cov.shape[1], cov.shape[2]
+        shift = jitter * self.alpha + (1.0 / self.beta.reshape(-1) if noise else 0.0)                 # [K]
+        cov = cov + shift[:, None, None, None] * torch.eye(n, dtype=TORCH_DTYPE, device=cov.device)
+        l, info = ops.potrf_batched(cov.reshape(k * g1, n, n))
+        s, j = xi.shape[-3], xi.shape[-1]
+        # the draws as [N*, S J] (one matrix for every pair) or [K G', N*, S J] against the factors l [K G', N*, N*]
+        rhs = xi.transpose(-3, -2).reshape(xi.shape[:-3] + (n, s * j))
+        if xi.dim() == 4:
+            rhs = rhs[:, None].expand(k, g1, n, s * j).reshape(k * g1, n, s * j)
+        prod = ops.matmul(torch.tril(l), rhs).reshape(k, g1, n, s, j)
+        pick = slot[:, None, None, None, :].expand(k, 1, n, s, j)
+        dev = torch.gather(prod, 1, pick)[:, 0]                                                       # [K, N*, S, J]
+        mean, _ = self.at(x, torch.zeros_like(x), cols)                                               # [K, N*, J]
+        return (mean[:, :, None, :] + dev).permute(0, 2, 1, 3).contiguous(), info
+
     def _metric_operands(self, cols, weights):
         """(P [K, M, M], n_k alpha_k diag(gamma_k) [K, Q, Q]) of metric's text."""
         r, gidx = self.r, self.gidx
@@ -103,10 +182,101 @@ class _Marginals:
         return p, (torch.sum(w, dim=1) * self.alpha)[:, None, None] * torch.diag_embed(self.gamma)
 
 
+# ---- the joint posterior at latent points: what the models' predictive_covariance / sample_functions share ---------------------
+DEFAULT_SAMPLE_JITTER = 1e-6
+"""sample_functions' default jitter, in units of the kernel's alpha.  A choice, not a measurement: the gram of nearby points has
+its smallest eigenvalue below rounding, and the Cholesky factorisation needs a shift well above eps N* lambda_max ~ 1e-12 alpha;
+1e-6 alpha is far above that and far below any 1/beta the models train to."""
+
+
+def composed_is_faster(k, g, n, m):
+    """The route of _Marginals.pattern_covariance: a cost model of the two forms in microseconds, fitted to the timings of
+    tools/time_point_cov.py on one MI355X, where it picks the faster form, or one within 20 % of it, at every
+    measured layout.
+      fused:     a workgroup per (kernel, pair of 32-point tiles), 256 at a time; each makes its features (about 18 us per block of
+                 64 inducing points) and runs one step per (pair of blocks, pattern) (about 9 us): the first product is repeated
+                 for every PAIR of point tiles, so the time grows with N*^2 M^2.
+      composed:  about 80 us of launches plus 18 us per kernel (one gram launch each), then 6.5 passes over the K G N*^2 doubles of
+                 the result at 3 TB/s."""
+    tiles, blocks = (n + 31) // 32, (m + 63) // 64
+    rounds = (k * tiles * (tiles + 1) // 2 + 255) // 256
+    fused = rounds * (18.0 * blocks + 9.0 * blocks * blocks * g)
+    composed = 80.0 + 18.0 * k + 6.5 * 8.0 * k * g * n * n / 3.0e6
+    return composed < fused
+
+
+def composed_covariance(z, x, gamma, alpha, c):
+    """ops.ard_rbf_point_cov's result [K, G, N, N] composed of the other operators: ops.ard_rbf_gram per kernel for the features
+    [K, N, M], two ops.matmul with the symmetric parts of c, ops.ard_rbf_gram for the prior term; the difference is symmetrised at
+    the end, (a + a^T) / 2, so that this route's result is exactly symmetric too.  Memory: K N M + 2 K G N^2 + K G N M doubles."""
+    k, g, m = c.shape[0], c.shape[1], c.shape[2]
+    n = x.shape[0]
+    feat = torch.stack([ops.ard_rbf_gram(x, z[i], gamma[i:i + 1], alpha[i:i + 1], alpha[i:i + 1])[0] for i in range(k)])
+    ct = (0.5 * (c + c.transpose(2, 3))).reshape(k * g, m, m)
+    fg = feat[:, None].expand(k, g, n, m).reshape(k * g, n, m) if g > 1 else feat
+    quad = ops.matmul(ops.matmul(fg, ct), fg.transpose(1, 2))                                     # [K G, N, N]
+    out = ops.ard_rbf_gram(x, None, gamma, alpha, alpha)[:, None] - quad.reshape(k, g, n, n)
+    return 0.5 * (out + out.transpose(2, 3))
+
+
+def with_noise(cov, inv_beta):
+    """cov [J, N*, N*] with inv_beta (one element, or [J]) added on the diagonals."""
+    eye = torch.eye(cov.shape[-1], dtype=TORCH_DTYPE, device=cov.device)
+    return cov + inv_beta.reshape(-1, 1, 1) * eye
+
+
+def draw_generator(seed, device):
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    return gen
+
+
+def standard_draws(draws, num_samples, n, j, gen, device):
+    """xi [S, N*, J]: standard normal draws from the device generator `gen`, or the caller's `draws` (numpy or torch)."""
+    if draws is None:
+        assert int(num_samples) >= 1, 'num_samples must be at least 1'
+        return torch.randn((int(num_samples), n, j), generator=gen, dtype=TORCH_DTYPE, device=device)
+    xi = draws.detach() if torch.is_tensor(draws) else torch.as_tensor(np.asarray(draws, dtype=np.float64))
+    xi = xi.to(device=device, dtype=TORCH_DTYPE).contiguous()
+    assert xi.dim() == 3 and xi.shape[0] >= 1 and tuple(xi.shape[1:]) == (n, j), 'draws must be [S x N* x len(columns)]'
+    return xi
+
+
+def raise_if_not_factorised(info):
+    """The one host read of sample_functions: potrf's info over every factorised matrix."""
+    bad = int(torch.count_nonzero(info))
+    if bad:
+        raise FloatingPointError('sample_functions: %d of %d covariance matrices are not positive definite in fp64 at this jitter; '
+                                 'raise `jitter` or set noise=True' % (bad, info.numel()))
+
+
+def covariance_of(marg, x, cols, noise):
+    """predictive_covariance of a one-kernel _Marginals: [J, N*, N*]."""
+    cov = marg.covariance(x, cols)[0]
+    return with_noise(cov, 1.0 / marg.beta) if noise else cov
+
+
+def samples_of(marg, x, cols, num_samples, noise, jitter, seed, draws, infos=None):
+    """sample_functions of a one-kernel _Marginals: [S, N*, J].  infos: a list that takes potrf's info in place of the host read
+    (the caller then reads them all at once with raise_if_not_factorised)."""
+    j = marg.gidx.shape[1] if cols is None else cols.numel()
+    xi = standard_draws(draws, num_samples, x.shape[0], j, draw_generator(seed, x.device), x.device)
+    f, info = marg.sample(x, xi, cols, noise, jitter)
+    if infos is None:
+        raise_if_not_factorised(info)
+    else:
+        infos.append(info)
+    return f[0]
+
+
 def columns_arg(columns, d, device):
+    """The output dims as a long tensor on the device; it carries its host copy as .host (a NumPy array), so that a caller can
+    plan on the host without reading the device (_Marginals._patterns)."""
     cols = np.arange(d) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
     assert cols.size >= 1 and cols.min() >= 0 and cols.max() < d, 'columns must be output dims in [0, D)'
-    return torch.as_tensor(cols, dtype=torch.long, device=device)
+    out = torch.as_tensor(cols, dtype=torch.long, device=device)
+    out.host = cols
+    return out
 
 
 def points_arg(x, q, device):
@@ -135,13 +305,15 @@ def one_kernel(c, y, beta, slots, columns, d):
     rb, cm = collapsed.posterior(take(c['r0']), take(c['kinv']), be, v)                      # per pattern [P, ...]
     r = torch.zeros((m, d), dtype=TORCH_DTYPE, device=device)
     gidx = torch.full((d,), -1, dtype=torch.int32, device=device)
+    gidx_host = np.full(d, -1, dtype=np.int64)
     for p, cols in enumerate(columns):
         ct = torch.as_tensor(np.asarray(cols), dtype=torch.long, device=device)
         r[:, ct] = rb[p, :, :len(cols)]
         gidx[ct] = p
+        gidx_host[np.asarray(cols, dtype=np.int64)] = p
     i0 = slots[0]
     return _Marginals(c['z'][i0:i0 + 1], c['gamma'][i0:i0 + 1], c['alpha'][i0:i0 + 1].reshape(1), be, c['zfac'][i0:i0 + 1],
-                      cm[None], r[None], gidx[None])
+                      cm[None], r[None], gidx[None], all_seen=bool((gidx_host >= 0).all()), gidx_host=gidx_host[None])
 
 
 def of_masked_bound(bound, z, mu, s, gamma, alpha, beta, d):

@@ -570,6 +570,44 @@ def ard_rbf_point_energy(z, x, v, gamma, alpha, p):
     return e, dx, dv
 
 
+def ard_rbf_point_cov(z, x, gamma, alpha, c):
+    """The joint posterior covariance at deterministic latent points (dpgp_ard_rbf_point_cov_f64): with the features
+    k_km(x_n) = alpha_k exp(-1/2 sum_q gamma_kq (x_nq - z_kmq)^2) of the kernels z [K,M,Q], gamma [K,Q], alpha [K] at the points
+    x [N,Q], returns
+        out [K,G,N,N] = alpha_k exp(-1/2 sum_q gamma_kq (x_iq - x_jq)^2) - sum_{m,m'} k_km(x_i) c[k,g,m,m'] k_km'(x_j)
+    c [K,G,M,M] with G >= 1 is any set of matrices; the result depends on their symmetric parts only and is exactly symmetric in
+    (i, j).  One launch, the features shared by the G patterns of a kernel, nothing of size N M in memory; fixed summation order,
+    the same bits on every run.  N <= 46340.  float64 tensors (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
+    args = (('z', z), ('x', x), ('gamma', gamma), ('alpha', alpha), ('c', c))
+    for nm, v in args:
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % nm)
+    if z.dim() != 3 or min(z.shape) < 1:
+        raise ValueError('z must be [K x M x Q], got %s' % (tuple(z.shape),))
+    k, m, q = z.shape
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != q:
+        raise ValueError('x must be [N x Q] with Q = %d, got %s' % (q, tuple(x.shape)))
+    if tuple(gamma.shape) != (k, q):
+        raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
+    if alpha.numel() != k:
+        raise ValueError('alpha must be [K], got %s' % (tuple(alpha.shape),))
+    if c.dim() != 4 or c.shape[0] != k or c.shape[1] < 1 or c.shape[2] != m or c.shape[3] != m:
+        raise ValueError('c must be [K x G x M x M] with G >= 1, got %s' % (tuple(c.shape),))
+    for nm, v in args:
+        if not v.is_cuda or v.device != z.device:
+            raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
+    z, x, gamma, alpha, c = z.contiguous(), x.contiguous(), gamma.contiguous(), alpha.reshape(-1).contiguous(), c.contiguous()
+    g, n = c.shape[1], x.shape[0]
+    out = torch.empty((k, g, n, n), dtype=torch.float64, device=z.device)
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_point_cov_workspace_bytes(k, g, n, m, q)
+    ws = _ws(wsb, z.device)
+    _lib.check(l.dpgp_ard_rbf_point_cov_f64(k, g, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
+                                            c.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb, _stream()),
+               'dpgp_ard_rbf_point_cov_f64')
+    return out
+
+
 def ard_rbf_diag(n, alpha, beta, include_noise=False, include_jitter=False, jitter=1e-8):
     """Kernel.covariance_diag -> [B,N]  (rbf_kernel.py:96-116)."""
     dt = _dtype_of(alpha)

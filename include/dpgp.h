@@ -323,6 +323,33 @@ int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const double *z, c
                                   const double *gamma, const double *alpha, const double *p, double *e, double *dx, double *dv,
                                   void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Joint posterior covariance at deterministic latent points (csrc/ard_rbf_point_cov.hip): the off-diagonal that the per-point
+ *      operators above leave out.  Kernels z[K][M][Q], gamma[K][Q], alpha[K] and points x[N][Q] as for the metric operator;
+ *      c[K][G][M][M]: G matrices per kernel (one per training row pattern), any matrices.  With k_km as above,
+ *        out[k][g][i][j] = alpha_k exp(-1/2 sum_q gamma_kq (x_iq - x_jq)^2) - sum_{m,m'} k_km(x_i) c[k][g][m][m'] k_km'(x_j)
+ *      out[K][G][N][N].  Rules:
+ *      - both products run on v_mfma_f64_16x16x4, the exponentials are dpgp_exp2;
+ *      - c enters through its symmetric part (c + c^T) / 2 only, symmetrised as its 64 x 64 tiles are staged;
+ *      - the result is EXACTLY symmetric: only tile pairs J <= I (tiles of 32 points) are evaluated, an entry (i, j) with
+ *        i > j is computed once and stored to both places;
+ *      - the G patterns of a kernel share the features: the number of exponentials does not depend on G (a workgroup makes
+ *        the features of a block of 64 inducing points at its 64 points once per pair of blocks, for all patterns);
+ *      - nothing of size N M, K N M or K G N M is written to memory; c is streamed in tiles and the features in blocks: no
+ *        limit on M from the LDS;
+ *      - no atomics, the order of every sum is fixed by (M, Q): the same bits on every run; kernel k's results do not depend
+ *        on K, G or the other kernels and patterns; entry (i, j) depends neither on N, nor on the places of i and j in x,
+ *        nor on which of the two comes first;
+ *      - points far from every z give the prior term alone: every product with the exact zeros of dpgp_exp2 is 0, no NaN.
+ *      1 <= K, G, M;  1 <= N <= 46340 (N N fits 31 bits);  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, G -2, N -3, M -4, Q -5, z -6, x -7, gamma -8,
+ *      alpha -9, c -10, out -11, ws -12, ws_bytes too small -13.
+ *   ws: the results are written from registers, so the query (a host function) returns a token 256 bytes (never more) for a
+ *      shape in range and 0 for one out of range; the pair (ws, ws_bytes) keeps the calling convention of the other point
+ *      operators. */
+size_t dpgp_ard_rbf_point_cov_workspace_bytes(int K, int G, int N, int M, int Q);
+int dpgp_ard_rbf_point_cov_f64(int K, int G, int N, int M, int Q, const double *z, const double *x, const double *gamma,
+                               const double *alpha, const double *c, double *out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Latent adjoint of B kernels that share inducing inputs AND q(X*) (csrc/psi_latent_adjoint.hip): the frozen over-D model at
  *      test time.  z[M][Q], q(X*) = (mu[N][Q], s[N][Q]: variances), gamma[B][Q], alpha[B]; y[N][ldy]: zero-filled data, column b
  *      for kernel b; w[B][N]: weights of the test points (NULL = all ones; any finite reals); stage-A adjoints g_v[B][M] and
