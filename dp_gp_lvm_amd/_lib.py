@@ -97,6 +97,9 @@ SIGNATURES = {
     'dpgp_ard_rbf_point_jacobian_f64': (_i, [_i] * 5 + [_vp] * 6 + [_vp, _sz, _vp]),
     'dpgp_ard_rbf_point_energy_workspace_bytes': (_sz, [_i] * 4),
     'dpgp_ard_rbf_point_energy_f64': (_i, [_i] * 4 + [_vp] * 9 + [_vp, _sz, _vp]),
+    'dpgp_ard_rbf_point_christoffel_workspace_bytes': (_sz, [_i] * 4),
+    'dpgp_ard_rbf_point_christoffel_f64': (_i, [_i] * 4 + [_vp] * 8 + [_vp, _sz, _vp]),
+    'dpgp_geodesic_accel_f64': (_i, [_i] * 3 + [_vp] * 7 + [_vp]),
     'dpgp_ard_rbf_point_cov_workspace_bytes': (_sz, [_i] * 5),
     'dpgp_ard_rbf_point_cov_f64': (_i, [_i] * 5 + [_vp] * 6 + [_vp, _sz, _vp]),
     'dpgp_psi_latent_adjoint_workspace_bytes': (_sz, [_i] * 4),

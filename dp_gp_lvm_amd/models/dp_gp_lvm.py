@@ -760,6 +760,20 @@ def dp_gp_lvm(y_train,
             prior = torch.cat([prior, prior_unseen[None]])
         return lambda x, v: marg.curve_terms(x, v, p, prior)
 
+    def _geodesic_terms(columns, name):
+        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms."""
+        assert not split, '%s is not built for a model sharded over a process group' % name
+        cols = _geometry_columns(columns)
+        evaluate()
+        with torch.no_grad():
+            marg, _, prior_unseen = _latent_geometry(cols)
+            if marg is None:
+                weight = torch.diagonal(prior_unseen).contiguous()
+                return lambda x, v: _geodesic.prior_accel(v, weight)
+            p, prior = marg._metric_operands(None, None)
+            prior = torch.cat([prior, prior_unseen[None]])
+        return lambda x, v: marg.geodesic_terms(x, v, p, prior)
+
     def _assembled_marginals(cols, xt, st_):
         """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
         into a zero-filled [2 x N* x len(cols)] buffer, one sum all-reduce completes it; every rank returns the same (mean, var).
@@ -1162,6 +1176,30 @@ def dp_gp_lvm(y_train,
             AssertionError."""
             return _geodesic.latent_geodesic(_curve_terms(columns, 'latent_geodesic'), x_from, x_to, num_latent_dims, device,
                                              num_segments, num_iterations, learning_rate, init)
+
+        @staticmethod
+        def geodesic_acceleration(x, v, columns=None):
+            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
+            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), Gamma the Christoffel symbols of
+            the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
+            ops.ard_rbf_point_christoffel over K = len(columns) kernels and one of ops.geodesic_accel, which sums them, per
+            block of points; the training side is built once per call.  fp64, torch.no_grad.  Not built for a model sharded
+            over a process group: AssertionError."""
+            return _geodesic.geodesic_acceleration(_geodesic_terms(columns, 'geodesic_acceleration'), x, v, num_latent_dims,
+                                                   device)
+
+        @staticmethod
+        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
+            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
+            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
+            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
+            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
+            velocities, in the same shape.  With the columns of one discovered group: where that group's manifold takes a
+            motion.  A stage is one call of ops.ard_rbf_point_christoffel and one of ops.geodesic_accel plus element-wise work;
+            the training side is built once per call; one host read at the end: FloatingPointError if the metric failed to factor
+            at any stage.  fp64, torch.no_grad.  Not built for a model sharded over a process group: AssertionError."""
+            return _geodesic.exp_map(_geodesic_terms(columns, 'latent_exp_map'), x, v, num_latent_dims, device, num_steps,
+                                     return_velocity)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1802,6 +1840,14 @@ def dp_gp_lvm_t(y_train,
             p, prior = mom.curve_operands(cols)
         return lambda x, v: mom.curve_terms(x, v, p, prior)
 
+    def _geodesic_terms(columns):
+        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms."""
+        cols = _columns_arg(columns)
+        with torch.no_grad():
+            mom = _moments()
+            p, prior = mom.curve_operands(cols)
+        return lambda x, v: mom.geodesic_terms(x, v, p, prior)
+
     class DP_GP_LVM_T(Trainable):
         """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
@@ -2037,6 +2083,27 @@ def dp_gp_lvm_t(y_train,
             ops.ard_rbf_point_energy plus element-wise work.  fp64."""
             return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, device, num_segments,
                                              num_iterations, learning_rate, init)
+
+        @staticmethod
+        def geodesic_acceleration(x, v, columns=None):
+            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
+            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), the weights phi included; Gamma
+            the Christoffel symbols of the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
+            ops.ard_rbf_point_christoffel on the T atoms and one of ops.geodesic_accel, which sums them; the training side is
+            built once per call.  fp64, torch.no_grad."""
+            return _geodesic.geodesic_acceleration(_geodesic_terms(columns), x, v, num_latent_dims, device)
+
+        @staticmethod
+        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
+            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
+            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
+            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
+            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
+            velocities, in the same shape.  With the columns of one discovered group: where that group's manifold takes a
+            motion.  A stage is one call of ops.ard_rbf_point_christoffel on the T atoms and one of ops.geodesic_accel plus
+            element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
+            metric failed to factor at any stage.  fp64, torch.no_grad."""
+            return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, device, num_steps, return_velocity)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

@@ -159,3 +159,8 @@ class _MomentsT:
     def curve_terms(self, x, v, p, prior):
         """marginals._Marginals.curve_terms on the T atoms, (p, prior) from curve_operands."""
         return self._curve_atoms.curve_terms(x, v, p, prior)
+
+    def geodesic_terms(self, x, v, p, prior):
+        """marginals._Marginals.geodesic_terms on the T atoms, (p, prior) from curve_operands: the acceleration under metric's
+        G, phi included."""
+        return self._curve_atoms.geodesic_terms(x, v, p, prior)

@@ -515,6 +515,14 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             p, prior = marg._metric_operands(cols, None)
         return lambda x, v: marg.curve_terms(x, v, p, prior)
 
+    def _geodesic_terms(columns):
+        """The acceleration of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+        cols = _marginals.columns_arg(columns, num_dimensions, dev_)
+        with torch.no_grad():
+            marg = _train_marginals()
+            p, prior = marg._metric_operands(cols, None)
+        return lambda x, v: marg.geodesic_terms(x, v, p, prior)
+
     class BayesianGPLVM(Trainable):
         """Accessors as in the reference (gaussian_process.py:276-340), and its two prediction methods (:329-538) with the same
         keywords and return tuples as dp_gp_lvm's, plus test_latent_gradients / optimise_test_latents / prediction_terms.
@@ -604,6 +612,26 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             is one call of ops.ard_rbf_point_energy plus element-wise work.  fp64."""
             return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, dev_, num_segments,
                                              num_iterations, learning_rate, init)
+
+        @staticmethod
+        def geodesic_acceleration(x, v, columns=None):
+            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
+            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), Gamma the Christoffel symbols of
+            the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
+            ops.ard_rbf_point_christoffel and one of ops.geodesic_accel; the training side is built once per call.  fp64,
+            torch.no_grad."""
+            return _geodesic.geodesic_acceleration(_geodesic_terms(columns), x, v, num_latent_dims, dev_)
+
+        @staticmethod
+        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
+            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
+            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
+            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
+            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
+            velocities, in the same shape.  A stage is one call of ops.ard_rbf_point_christoffel and one of ops.geodesic_accel
+            plus element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
+            metric failed to factor at any stage.  fp64, torch.no_grad."""
+            return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, dev_, num_steps, return_velocity)
 
         @staticmethod
         def predictive_covariance(x, columns=None, noise=False):
@@ -1080,6 +1108,18 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         each = [lambda x, v, marg=train[vv], pair=pair: marg.curve_terms(x, v, *pair) for vv, pair in zip(vs, pairs)]
         return [_geodesic.sum_terms(each)] if total else each
 
+    def _geodesic_terms(views, total):
+        """The accelerations of models/geodesic.py of every view of `views` (one entry: under their summed metric, with total: the
+        views' slabs go to one factorisation), formed once."""
+        vs = _views_arg(views)
+        with torch.no_grad():
+            train = _train_marginals()
+            pairs = [train[v]._metric_operands(None, None) for v in vs]
+        if total:
+            return [_marginals.geodesic_terms([(train[vv], pair[0]) for vv, pair in zip(vs, pairs)],
+                                              torch.cat([pair[1] for pair in pairs]))]
+        return [_marginals.geodesic_terms([(train[vv], pair[0])], pair[1]) for vv, pair in zip(vs, pairs)]
+
     class ManifoldRelevanceDetermination(Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
         test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
@@ -1203,6 +1243,24 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             summed metric.  The training side of all views is built once per call."""
             out = [_geodesic.latent_geodesic(t, x_from, x_to, num_latent_dims, dev_, num_segments, num_iterations, learning_rate,
                                              init) for t in _curve_terms(views, total)]
+            return out[0] if total else out
+
+        @staticmethod
+        def geodesic_acceleration(x, v, views=None, total=False):
+            """One acceleration a [N* x Q] (or [Q]) per view of `views` (default: all V, in order), as
+            bayesian_gp_lvm.geodesic_acceleration under the view's latent_metric; total=True: one result, under the summed
+            metric latent_metric(., views, total=True).  The training side of all views is built once per call."""
+            out = [_geodesic.geodesic_acceleration(t, x, v, num_latent_dims, dev_) for t in _geodesic_terms(views, total)]
+            return out[0] if total else out
+
+        @staticmethod
+        def latent_exp_map(x, v, num_steps=64, views=None, total=False, return_velocity=False):
+            """One curve [C x num_steps+1 x Q] (or [num_steps+1 x Q]; with return_velocity one pair (curve, velocities)) per view
+            of `views`: the view's own exponential map, as bayesian_gp_lvm.latent_exp_map under the view's latent_metric;
+            total=True: one result, under the summed metric (a stage is then one ops.ard_rbf_point_christoffel call per view and
+            one ops.geodesic_accel).  The training side of all views is built once per call."""
+            out = [_geodesic.exp_map(t, x, v, num_latent_dims, dev_, num_steps, return_velocity)
+                   for t in _geodesic_terms(views, total)]
             return out[0] if total else out
 
         @staticmethod

@@ -11,6 +11,11 @@ v_i = c_{i+1} - c_i, and with e_i = v_i^T G(x_i) v_i
 discrete geodesic.  Everything here works on `terms`, a callable (x [N,Q], v [N,Q]) -> (e [N], dx [N,Q], dv [N,Q]) that a model
 builds ONCE per call from its training side (marginals._Marginals.curve_terms on ops.ard_rbf_point_energy): C curves are one
 call with N = C S, and an iteration of latent_geodesic is one call plus element-wise work.  fp64, no autograd.
+
+The initial-value side: a geodesic obeys G x'' = -Gamma(x, x'), Gamma the Christoffel symbols of the first kind contracted twice
+with the velocity.  exp_map integrates (x', v') = (v, -G^-1 Gamma) over t in [0, 1] by the classical Runge-Kutta scheme on `accel`,
+a callable (x [N,Q], v [N,Q]) -> (a [N,Q], speed [N], info [N]) that a model builds ONCE per call
+(marginals.geodesic_terms on ops.ard_rbf_point_christoffel and ops.geodesic_accel): C curves are one batch, a stage is one call.
 """
 import numpy as np
 import torch
@@ -142,3 +147,62 @@ def latent_geodesic(terms, x_from, x_to, q, device, num_segments=32, num_iterati
                 c[:, 1:-1] = inner.detach()
         keep(terms(*segments(c))[0])
         return best, length(best_e, n), best_energy
+
+
+def prior_accel(v, weight):
+    """accel's triple under a constant diagonal metric diag(weight [Q]): straight lines, (0, sum_q weight_q v_q^2, 0)."""
+    return torch.zeros_like(v), torch.sum(v * v * weight, dim=1), torch.zeros(v.shape[0], dtype=torch.int32, device=v.device)
+
+
+def geodesic_acceleration(accel, x, v, q, device):
+    """a [N* x Q] (or [Q] for one point): x'' of the geodesics through x with the velocities v ([N* x Q] or [Q])."""
+    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
+    xs, vs = ends_arg(x, q, device, 'x'), ends_arg(v, q, device, 'v')
+    assert xs.shape == vs.shape, 'x and v must have the same shape'
+    with torch.no_grad():
+        a = accel(xs, vs)[0]
+    return a[0] if single else a
+
+
+def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False):
+    """curve [C x S+1 x Q] (one curve [S+1 x Q] for x, v [Q]), S = num_steps: the exponential map of v at x, the classical RK4
+    solution of (x', v') = (v, accel(x, v)) on t in [0, 1] at step 1 / S, all C curves in one batch; row 0 holds the bits of x.
+    With return_velocity also the velocities in the same shape.  Four calls of accel per step plus element-wise work; nothing is
+    read on the host until ONE read of the accumulated info at the end: FloatingPointError if the metric failed to factor at
+    any stage of any curve."""
+    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
+    xs, vs = ends_arg(x, q, device, 'x'), ends_arg(v, q, device, 'v')
+    assert xs.shape == vs.shape, 'x and v must have the same shape'
+    num_steps = int(num_steps)
+    assert num_steps >= 1, 'num_steps >= 1'
+    c, h = xs.shape[0], 1.0 / num_steps
+    with torch.no_grad():
+        curve = torch.empty((c, num_steps + 1, q), dtype=xs.dtype, device=xs.device)
+        vel = torch.empty_like(curve)
+        bad = torch.zeros(c, dtype=torch.int32, device=xs.device)
+
+        def f(xx, vv):
+            nonlocal bad
+            a, _, info = accel(xx, vv)
+            bad = bad + (info != 0).to(torch.int32)
+            return a
+
+        curve[:, 0], vel[:, 0] = xs, vs
+        for s in range(num_steps):
+            k1x, k1v = vs, f(xs, vs)
+            k2x = vs + (0.5 * h) * k1v
+            k2v = f(xs + (0.5 * h) * k1x, k2x)
+            k3x = vs + (0.5 * h) * k2v
+            k3v = f(xs + (0.5 * h) * k2x, k3x)
+            k4x = vs + h * k3v
+            k4v = f(xs + h * k3x, k4x)
+            xs = xs + (h / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x)
+            vs = vs + (h / 6.0) * (k1v + 2.0 * k2v + 2.0 * k3v + k4v)
+            curve[:, s + 1], vel[:, s + 1] = xs, vs
+        failed = int(torch.count_nonzero(bad))
+        if failed:
+            raise FloatingPointError('latent_exp_map: the metric failed to factor (not positive definite in fp64) along %d of %d '
+                                     'curves' % (failed, c))
+    if single:
+        curve, vel = curve[0], vel[0]
+    return (curve, vel) if return_velocity else curve

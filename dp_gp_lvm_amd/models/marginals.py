@@ -98,6 +98,13 @@ class _Marginals:
         w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0)
         return e + torch.sum(v * v * w, dim=1), dx, dv + 2.0 * v * w
 
+    def geodesic_terms(self, x, v, p, prior):
+        """(a [N*, Q], speed [N*], info [N*] int32): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the
+        points x [N*, Q] with the velocities v [N*, Q] under metric_total's G, speed = v^T G v, and the factorisation's info (0, or
+        the failing pivot: a is then NaN at that point).  (p, prior) as for curve_terms.  ONE call of
+        ops.ard_rbf_point_christoffel and ONE of ops.geodesic_accel per block of points (geodesic_terms below)."""
+        return geodesic_terms([(self, p)], prior)(x, v)
+
     def _patterns(self, cols):
         """(c [K, G', M, M], slot [K, J] long): the patterns to evaluate and, per kernel and column, its place among them.  With
         gidx_host (and host columns: columns_arg's .host) G' counts only the patterns that `cols` touch, in ascending order, plus
@@ -180,6 +187,31 @@ class _Marginals:
         counts = torch.sum(hit.to(TORCH_DTYPE) * w[:, :, None], dim=1)                              # [K, G]
         ops.matmul(counts[:, None, :].contiguous(), self.c.reshape(k, g, m * m), out=p.view(k, 1, m * m), alpha=-1.0, beta=1.0)
         return p, (torch.sum(w, dim=1) * self.alpha)[:, None, None] * torch.diag_embed(self.gamma)
+
+
+# ---- the geodesic equation: what the models' geodesic_acceleration / latent_exp_map share ----------------------------------------
+def geodesic_terms(parts, prior):
+    """The callable (x [N, Q], v [N, Q]) -> (a [N, Q], speed [N], info [N]) of models/geodesic.py under the SUM of the metrics of
+    `parts`, a list of (_Marginals, P [K, M, M]) pairs (_metric_operands' P; MRD's summed metric has one pair per view), plus
+    the constant diagonal metrics `prior` [*, Q, Q] (only the diagonals are read).  With G = G0 + sum_k b_k^T P_k b_k the geodesic
+    obeys G x'' = -sum_k Gamma_k: one call of ops.ard_rbf_point_christoffel per pair gives the slabs (g_k, Gamma_k), one call of
+    ops.geodesic_accel sums them, adds G0, factorises and solves.  Blocks of at most 2^25 result entries, as curve_terms; a
+    point's bits do not depend on its block."""
+    q = parts[0][0].z.shape[2]
+    k = sum(marg.z.shape[0] for marg, _ in parts)
+    w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0).contiguous()
+    step = max(1, (1 << 25) // (k * (q * q + q)))
+
+    def terms(x, v):
+        x, v = x.contiguous(), v.contiguous()
+        blocks = []
+        for i in range(0, x.shape[0], step):
+            xb, vb = x[i:i + step], v[i:i + step]
+            slabs = [ops.ard_rbf_point_christoffel(marg.z, xb, vb, marg.gamma, marg.alpha, p) for marg, p in parts]
+            g, gam = slabs[0] if len(slabs) == 1 else (torch.cat([s[0] for s in slabs]), torch.cat([s[1] for s in slabs]))
+            blocks.append(ops.geodesic_accel(g, gam, w, vb))
+        return tuple(bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
+    return terms
 
 
 # ---- the joint posterior at latent points: what the models' predictive_covariance / sample_functions share ---------------------

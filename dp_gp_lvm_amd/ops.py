@@ -487,10 +487,11 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     return d_mu, d_s
 
 
-def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None):
-    """The checks of the three operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
+def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None):
+    """The checks of the four operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
     (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M] or r [K,M,J], `what` its wording); dirs: the
-    directions v [N,Q] of ard_rbf_point_energy (a one-element tuple), checked in their place after x."""
+    directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), checked in their place after x;
+    max_q: an operator's own limit on Q (ValueError, after the shapes)."""
     args = (('z', z), ('x', x)) + (() if dirs is None else (('v', dirs[0]),)) + (('gamma', gamma), ('alpha', alpha), (name, a))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
@@ -508,6 +509,8 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None):
         raise ValueError('alpha must be [K], got %s' % (tuple(alpha.shape),))
     if a.dim() != 3 or a.shape[0] != k or a.shape[1] != m or a.shape[2] < 1 or (name == 'p' and a.shape[2] != m):
         raise ValueError('%s must be %s, got %s' % (name, what, tuple(a.shape)))
+    if max_q is not None and q > max_q:
+        raise ValueError('z must have Q <= %d, got Q = %d' % (max_q, q))
     for nm, v in args:
         if not v.is_cuda or v.device != z.device:
             raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
@@ -568,6 +571,65 @@ def ard_rbf_point_energy(z, x, v, gamma, alpha, p):
                                                alpha.data_ptr(), p.data_ptr(), e.data_ptr(), dx.data_ptr(), dv.data_ptr(),
                                                ws.data_ptr(), wsb, _stream()), 'dpgp_ard_rbf_point_energy_f64')
     return e, dx, dv
+
+
+def ard_rbf_point_christoffel(z, x, v, gamma, alpha, p):
+    """The metric of ard_rbf_point_metric and its contracted Christoffel symbol along the velocities v [N,Q] at the points x [N,Q]
+    (dpgp_ard_rbf_point_christoffel_f64): with b as there, k_km the kernel values and
+        d_knm = v_n^T (d^2 k_km / dx dx)(x_n) v_n = k_km(x_n) [(sum_q gamma_kq (x_nq - z_kmq) v_nq)^2 - sum_q gamma_kq v_nq^2]
+    returns (g, gam),
+        g [K,N,Q,Q] = sum_{m,m'} p[k,m,m'] b_kmq(x_n) b_km'q'(x_n)           exactly ard_rbf_point_metric's quantity
+        gam [K,N,Q] = sum_{m,m'} b_kmq(x_n) p[k,m,m'] d_knm'
+    p [K,M,M] is used as given (not symmetrised).  For a SYMMETRIC p, gam is the Christoffel symbol of the first kind of g
+    contracted twice with v, gam = (D_v g) v - 1/2 grad_x (v^T g v), so that a geodesic of G = G0 + sum_k g_k with constant G0
+    obeys G x'' = -sum_k gam_k; for a non-symmetric p it is the sum above and no more.  One launch, nothing of size N M in
+    memory; fixed summation order, the same bits on every run.  Q <= 63 (ValueError).  float64 tensors (TypeError) of these
+    shapes (ValueError) on one GPU (RuntimeError)."""
+    z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]', dirs=(v,), max_q=63)
+    v = v.contiguous()
+    g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
+    gam = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
+    l = _lib.lib()
+    wsb = l.dpgp_ard_rbf_point_christoffel_workspace_bytes(k, n, m, q)
+    ws = _ws(wsb, z.device)
+    _lib.check(l.dpgp_ard_rbf_point_christoffel_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), v.data_ptr(), gamma.data_ptr(),
+                                                    alpha.data_ptr(), p.data_ptr(), g.data_ptr(), gam.data_ptr(), ws.data_ptr(),
+                                                    wsb, _stream()), 'dpgp_ard_rbf_point_christoffel_f64')
+    return g, gam
+
+
+def geodesic_accel(g, gam, prior, v):
+    """The acceleration of the geodesic equation from ard_rbf_point_christoffel's pair (dpgp_geodesic_accel_f64): per point, with
+    G_n = sum_k g[k,n] + diag(prior) (k ascending), returns (a, speed, info),
+        a [N,Q] = -G_n^-1 sum_k gam[k,n],     speed [N] = v_n^T G_n v_n,     info [N] int32
+    by one Cholesky factorisation per point (the lower triangle of G_n is read) in one launch.  info[n] = 0, or the 1-based index
+    of the first pivot that is not positive: a[n, :] is then NaN and the other points are unaffected.  g [K,N,Q,Q], gam [K,N,Q],
+    prior [Q], v [N,Q] with Q <= 64.  No atomics, nothing read on the host, the same bits on every run.  float64 tensors
+    (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
+    args = (('g', g), ('gam', gam), ('prior', prior), ('v', v))
+    for nm, t in args:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % nm)
+    if g.dim() != 4 or min(g.shape) < 1 or g.shape[2] != g.shape[3] or g.shape[3] > 64:
+        raise ValueError('g must be [K x N x Q x Q] with Q <= 64, got %s' % (tuple(g.shape),))
+    k, n, q = g.shape[0], g.shape[1], g.shape[2]
+    if tuple(gam.shape) != (k, n, q):
+        raise ValueError('gam must be [K x N x Q] as g, got %s' % (tuple(gam.shape),))
+    if tuple(prior.shape) != (q,):
+        raise ValueError('prior must be [Q], got %s' % (tuple(prior.shape),))
+    if tuple(v.shape) != (n, q):
+        raise ValueError('v must be [N x Q], got %s' % (tuple(v.shape),))
+    for nm, t in args:
+        if not t.is_cuda or t.device != g.device:
+            raise RuntimeError('%s must live on the GPU of g: dp_gp_lvm_amd runs its operators in HIP only' % nm)
+    g, gam, prior, v = g.contiguous(), gam.contiguous(), prior.contiguous(), v.contiguous()
+    a = torch.empty((n, q), dtype=torch.float64, device=g.device)
+    speed = torch.empty((n,), dtype=torch.float64, device=g.device)
+    info = torch.empty((n,), dtype=torch.int32, device=g.device)
+    _lib.check(_lib.lib().dpgp_geodesic_accel_f64(k, n, q, g.data_ptr(), gam.data_ptr(), prior.data_ptr(), v.data_ptr(),
+                                                  a.data_ptr(), speed.data_ptr(), info.data_ptr(), _stream()),
+               'dpgp_geodesic_accel_f64')
+    return a, speed, info
 
 
 def ard_rbf_point_cov(z, x, gamma, alpha, c):

@@ -323,6 +323,37 @@ int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const double *z, c
                                   const double *gamma, const double *alpha, const double *p, double *e, double *dx, double *dv,
                                   void *ws, size_t ws_bytes, void *stream);
 
+/* ---- The geodesic equation at deterministic latent points (csrc/ard_rbf_point_christoffel.hip): what one stage of an integrator
+ *      of x'' = -G(x)^-1 Gamma(x, x') needs.  Kernels, points x[N][Q] and p[K][M][M] as for the metric operator above; velocities
+ *      v[N][Q], shared by the kernels.  With k_km and b_kmq as above and
+ *        a_knm = sum_q gamma_kq (x_nq - z_kmq) v_nq,   d_knm = k_km(x_n) (a_knm^2 - sum_q gamma_kq v_nq^2) = v_n^T (d2 k_km / dx dx) v_n
+ *      the first operator gives
+ *        g[K][N][Q][Q] = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)         (exactly the metric operator's quantity)
+ *        gam[K][N][Q]  = sum_{m,m'} b_kmq(x_n) p[k][m][m'] d_knm'
+ *      p is used as given; for a symmetric p, gam is the Christoffel symbol of the first kind of g contracted twice with v,
+ *      (D_v g) v - 1/2 grad_x (v^T g v).  One launch: the metric kernel's two products on the fp64 matrix pipe with the feature
+ *      block of a point widened to [b_.1 .. b_.Q, d] (W = Q + 1 columns, ceil(W / 16) column tiles); p is streamed in 64 x 64
+ *      tiles.  Nothing of size N M is written to memory; no atomics, the order of every sum is fixed by (M, Q): the same bits on
+ *      every run; a point's results depend neither on N, nor on its place in x, nor on K.  Points far from every z give exact
+ *      zeros.  1 <= K, N, M;  1 <= Q <= 63.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, N -2, M -3, Q -4, z -5, x -6, v -7, gamma -8,
+ *      alpha -9, p -10, g -11, gam -12, ws -13, ws_bytes too small -14.
+ *   ws: the results are written from the accumulators, so the query (a host function) returns a token 256 bytes for a shape in
+ *      range and 0 for one out of range; the pair (ws, ws_bytes) keeps the calling convention of the other point operators.
+ *      The finishing operator takes g[K][N][Q][Q], gam[K][N][Q], prior[Q] (a constant diagonal metric) and v[N][Q] and gives, per
+ *      point, with G = sum_k g[k][n] + diag(prior) (k ascending),
+ *        speed[N] = v_n^T G v_n,     a[N][Q] = -G^-1 sum_k gam[k][n]            by a Cholesky factorisation of G (lower triangle read)
+ *        info[N]  = 0, or the 1-based index of the first pivot that is not positive: a[n][:] is then NaN; other points are unaffected
+ *      One launch, a workgroup per point; no atomics, no workspace, nothing read on the host, the same bits on every run.
+ *      1 <= K, N;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, in this order:  K -1, N -2, Q -3, g -4, gam -5, prior -6, v -7, a -8, speed -9, info -10. */
+size_t dpgp_ard_rbf_point_christoffel_workspace_bytes(int K, int N, int M, int Q);
+int dpgp_ard_rbf_point_christoffel_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *v,
+                                       const double *gamma, const double *alpha, const double *p, double *g, double *gam,
+                                       void *ws, size_t ws_bytes, void *stream);
+int dpgp_geodesic_accel_f64(int K, int N, int Q, const double *g, const double *gam, const double *prior, const double *v,
+                            double *a, double *speed, int *info, void *stream);
+
 /* ---- Joint posterior covariance at deterministic latent points (csrc/ard_rbf_point_cov.hip): the off-diagonal that the per-point
  *      operators above leave out.  Kernels z[K][M][Q], gamma[K][Q], alpha[K] and points x[N][Q] as for the metric operator;
  *      c[K][G][M][M]: G matrices per kernel (one per training row pattern), any matrices.  With k_km as above,
