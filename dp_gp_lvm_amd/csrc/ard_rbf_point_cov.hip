@@ -31,10 +31,10 @@
 // LDS: 8 (3 64 FS + 64 PS + Q) = 156672 + 8 Q bytes (one workgroup per CU).  FS = 80: the two rows (kk, kk + 1) that a half
 // wave reads for an A or B operand lie 80 doubles = 160 banks apart, i.e. on disjoint halves of the 64 banks; PS = 66 as
 // the sibling operators' tile of p (lanes (i, kk) of a half wave on 32 distinct bank pairs).
-#include "internal.h"
+#include "point_tile.h"
 
-#define PC_MS 64            // inducing points per block
-#define PC_PS 66            // row stride of the c tile
+#define PC_MS DPGP_POINT_MS // inducing points per block
+#define PC_PS DPGP_POINT_PS // row stride of the c tile
 #define PC_FS 80            // row stride of the feature and U arrays
 #define PC_NP 32            // points per tile
 #define PC_MAX_N 46340      // N N fits 31 bits
@@ -182,18 +182,14 @@ long pc_pairs(int N) {
 // K, G, N, M >= 1, 1 <= Q <= 64, N N within 31 bits, and sizes that the 32-bit grid and the int indices of the kernel hold
 bool pc_shape_ok(int K, int G, int N, int M, int Q) {
     if (K < 1 || G < 1 || N < 1 || M < 1 || Q < 1 || Q > DPGP_QX_PSI_MAX_Q) return false;
-    if (N > PC_MAX_N || M > 0x3fffffff) return false;
+    if (N > PC_MAX_N || M > DPGP_POINT_MAX_N) return false;
     return (long)K * pc_pairs(N) <= 0x7fffffffL;
 }
 
 }  // namespace
 
-// The results are written from registers and the operator needs no scratch memory; the query and the (ws, ws_bytes) pair are
-// there so that every point operator is called the same way.  DPGP_POINT_COV_WS bytes for a shape in range, 0 outside.
-#define DPGP_POINT_COV_WS 256
-
 extern "C" size_t dpgp_ard_rbf_point_cov_workspace_bytes(int K, int G, int N, int M, int Q) {
-    return pc_shape_ok(K, G, N, M, Q) ? DPGP_POINT_COV_WS : 0;
+    return pc_shape_ok(K, G, N, M, Q) ? DPGP_POINT_WS : 0;
 }
 
 extern "C" int dpgp_ard_rbf_point_cov_f64(int K, int G, int N, int M, int Q, const double *z, const double *x,

@@ -26,13 +26,12 @@
 // every matrix step, so its bits depend neither on N, nor on its place in the tile, nor on K or the other kernels.  Far-away
 // points: dpgp_exp2 gives k = 0 exactly, then c = w = 0 and every product with them is 0.
 // LDS: 8 (16 Q + 16 Q + Q + 64 Q + 64 48 + 64 66) = 776 Q + 58368 bytes: 64.6 KiB at Q = 10 (two workgroups per CU), 105.5 KiB at Q = 64.
-#include "internal.h"
+#include "point_tile.h"
 
-#define PE_MS 64            // rows of W per slab = inner indices per chunk
-#define PE_PS 66            // row stride of the p tile in LDS (mt_kernel's MT_PS: lanes (i, kk) of a half wave on 32 distinct bank pairs)
+#define PE_MS DPGP_POINT_MS // rows of W per slab = inner indices per chunk
+#define PE_PS DPGP_POINT_PS // row stride of the p tile in LDS
 #define PE_NP 16            // points per workgroup
 #define PE_CS 48            // row stride of the (c | k | a) rows: the 2 rows of a half wave's B operand on disjoint bank halves
-#define PE_MAX_N 0x3fffffff
 
 namespace {
 
@@ -177,13 +176,6 @@ size_t pe_lds(int Q) {
     return sizeof(double) * ((size_t)2 * PE_NP * Q + Q + (size_t)PE_MS * Q + PE_MS * PE_CS + PE_MS * PE_PS);
 }
 
-// K, N, M >= 1, 1 <= Q <= 64, and sizes that the 32-bit grid and the int indices of the kernel hold
-bool pe_shape_ok(int K, int N, int M, int Q) {
-    if (K < 1 || N < 1 || M < 1 || Q < 1 || Q > DPGP_QX_PSI_MAX_Q) return false;
-    if (N > PE_MAX_N || M > PE_MAX_N) return false;
-    return (long)K * dpgp_ceil_div(N, PE_NP) <= 0x7fffffffL;
-}
-
 template <int QT>
 int pe_launch(int K, int N, int M, int Q, const double *z, const double *x, const double *v, const double *gamma,
               const double *alpha, const double *p, double *e, double *dx, double *dv, hipStream_t st) {
@@ -199,12 +191,8 @@ int pe_launch(int K, int N, int M, int Q, const double *z, const double *x, cons
 
 }  // namespace
 
-// The results are written from registers and the operator needs no scratch memory; the query and the (ws, ws_bytes) pair are
-// there so that every point operator is called the same way.  DPGP_POINT_ENERGY_WS bytes for a shape in range, 0 outside.
-#define DPGP_POINT_ENERGY_WS 256
-
 extern "C" size_t dpgp_ard_rbf_point_energy_workspace_bytes(int K, int N, int M, int Q) {
-    return pe_shape_ok(K, N, M, Q) ? DPGP_POINT_ENERGY_WS : 0;
+    return dpgp_point_shape_ok(K, N, M, Q, M, DPGP_QX_PSI_MAX_Q, PE_NP) ? DPGP_POINT_WS : 0;
 }
 
 extern "C" int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *v,
@@ -227,9 +215,7 @@ extern "C" int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const d
     const size_t need = dpgp_ard_rbf_point_energy_workspace_bytes(K, N, M, Q);
     if (need == 0 || ws_bytes < need) return -15;              // (need == 0: a shape past what the launch grid holds)
     const hipStream_t st = (hipStream_t)stream;
-    const int qt = dpgp_ceil_div(Q, 16);
-    return qt == 1   ? pe_launch<1>(K, N, M, Q, z, x, v, gamma, alpha, p, e, dx, dv, st)
-           : qt == 2 ? pe_launch<2>(K, N, M, Q, z, x, v, gamma, alpha, p, e, dx, dv, st)
-           : qt == 3 ? pe_launch<3>(K, N, M, Q, z, x, v, gamma, alpha, p, e, dx, dv, st)
-                     : pe_launch<4>(K, N, M, Q, z, x, v, gamma, alpha, p, e, dx, dv, st);
+    return dpgp_dispatch_qt(dpgp_ceil_div(Q, 16), [&](auto qt) {
+        return pe_launch<decltype(qt)::value>(K, N, M, Q, z, x, v, gamma, alpha, p, e, dx, dv, st);
+    });
 }

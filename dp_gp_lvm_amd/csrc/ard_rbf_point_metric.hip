@@ -1,15 +1,25 @@
-// Latent-space metric and predictive Jacobian of K ARD-RBF kernels at DETERMINISTIC latent points x [N][Q].  With
+// Latent-space metric, predictive Jacobian and contracted Christoffel symbol of K ARD-RBF kernels at DETERMINISTIC latent points
+// x [N][Q].  With
 //   k_km(x_n)  = alpha_k exp(-1/2 sum_q gamma_kq (x_nq - z_kmq)^2)
 //   b_kmq(x_n) = d k_km / d x_q = -gamma_kq (x_nq - z_kmq) k_km(x_n)                    the derivative features [M x Q] of point n
-// the two operators are
-//   metric:    g[k][n][q][q']  = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)           p [K][M][M], used as given (not symmetrised)
-//   jacobian:  jac[k][n][j][q] = sum_m b_kmq(x_n) r[k][m][j]                             r [K][M][J]
+// the three operators are
+//   metric:      g[k][n][q][q']  = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)         p [K][M][M], used as given (not symmetrised)
+//   jacobian:    jac[k][n][j][q] = sum_m b_kmq(x_n) r[k][m][j]                           r [K][M][J]
+//   christoffel: g as the metric's, and with velocities v [N][Q],
+//                  a_knm = sum_q gamma_kq (x_nq - z_kmq) v_nq
+//                  d_knm = v_n^T (d^2 k_km / dx dx)(x_n) v_n = k_km(x_n) (a_knm^2 - sum_q gamma_kq v_nq^2)
+//                gam[k][n][q]    = sum_{m,m'} b_kmq(x_n) p[k][m][m'] d_knm'
+//                For symmetric p, gam is the Christoffel symbol of the first kind of g contracted twice with v,
+//                  gam = (D_v g) v - 1/2 grad_x (v^T g v):    the (Hv)^T p c terms of the two parts cancel, H the Hessian features.
+// ONE kernel, mt_kernel<QT, MODE>, does all three; what exists in one mode only sits behind `if constexpr`.
 // The features B [M x (points, q)] are never stored to memory: a workgroup makes them on the fly, 64 inducing points at a time,
 // into LDS, one exponential per (k, n, m) and per slab of 64 rows of the left operand.
 //
-// Layout.  Workgroup (kernel k, tile of NP points), 256 threads = 4 waves.  With QT = ceil(Q / 16) a point owns QT column tiles of 16
-// (its q padded to 16 QT), NP = 8, 2, 1, 1 points for QT = 1 .. 4, CT = NP QT column tiles in all.  Both operators are the product
-//   U [R x (point, q)] = A [R x M] B [M x (point, q)]          metric: A = p_k, R = M;   jacobian: A = r_k^T, R = J
+// Layout.  Workgroup (kernel k, tile of NP points), 256 threads = 4 waves.  A point's feature block is W columns wide: W = Q, and
+// W = Q + 1 for christoffel, whose block is F = [b_.1 .. b_.Q, d].  With QT = ceil(W / 16) a point owns QT column tiles of 16
+// (its columns padded to 16 QT), NP = 8, 2, 1, 1 points for QT = 1 .. 4, CT = NP QT column tiles in all; for Q <= 15 the d column
+// sits in the padding that the metric carries anyway.  All three operators are the product
+//   U [R x (point, q)] = A [R x M] B [M x (point, q)]          metric, christoffel: A = p_k, R = M;   jacobian: A = r_k^T, R = J
 // on v_mfma_f64_16x16x4 (Mfma<double>): the rows of A go in slabs of 64, wave w owns rows 16 w .. 16 w + 15 of the slab and the CT
 // accumulators of its row tile; the inner index m' goes in chunks of 64: per chunk the z rows [64][Q], the exponentials
 // [64][NP], the features sB [64][16 CT (+ pad)] and the A tile sP [64][64 (+ pad)] are staged in LDS, then every wave runs the
@@ -22,44 +32,60 @@
 //             the chunks of a slab are walked in the rotated order slab + 1, .., nch - 1, 0, .., slab: the slab's own chunk comes
 //             last and its features are the ones in LDS when U is complete.  Each wave keeps NP QT^2 result tiles over all slabs;
 //             at the end the four waves' tiles are added in wave order through LDS and stored.
-// The order of every sum is fixed by (M, Q) alone: no atomics, no workspace, the same bits on every run, and a kernel's results
-// do not depend on K or on the other kernels.  Far-away points: dpgp_exp2 gives exact zeros, every product with them is 0.
-// LDS: 8 (NP Q + Q + 64 Q + 64 NP + 64 66 + 64 BS) bytes, BS = 16 CT + 16 (+ 16 for odd CT): 120.4 KiB at Q = 16, 109.5 KiB at Q = 64.
-#include "internal.h"
+//   christoffel: the same with F in the place of B: F^T p F holds g in its leading Q x Q block and gam in the first Q rows of its
+//             last column.  An entry of g is summed in the metric's order whether or not the d column costs a tile: the same bits.
+// The order of every sum is fixed by (M, Q) alone: no atomics, no workspace, the same bits on every run; a point's results depend
+// neither on N, nor on its place in x, nor on K or the other kernels.  Far-away points: dpgp_exp2 gives exact zeros, every product
+// with them is 0.  1 <= Q <= 64; christoffel 1 <= Q <= 63 (W <= 64).
+// LDS: 8 (NP Q + Q + 64 Q + 64 NP + 64 66 + 64 BS) bytes, BS = 16 CT + 16 (+ 16 for odd CT): 120.4 KiB at Q = 16, 109.5 KiB at Q = 64;
+// christoffel 8 (2 NP Q + Q + 64 Q + 128 NP + 64 66 + 64 BS): 122.5 KiB at Q = 15, 107.0 KiB at Q = 63.
+#include "point_tile.h"
 
-#define MT_MS 64            // rows of A per slab = inner indices per chunk
-#define MT_PS 66            // row stride of the A tile in LDS: lanes (i, kk) of a half wave fall on 32 distinct bank pairs
-#define MT_MAX_N 0x3fffffff
+#define MT_MS DPGP_POINT_MS
+#define MT_PS DPGP_POINT_PS
+#define MT_CHRISTOFFEL_MAX_Q 63
 
 namespace {
+
+enum MtMode { MT_METRIC, MT_JACOBIAN, MT_CHRISTOFFEL };
 
 template <int QT> struct MtCfg {
     static constexpr int NP = QT == 1 ? 8 : QT == 2 ? 2 : 1;   // points per workgroup
     static constexpr int CT = NP * QT;                         // column tiles of 16
-    static constexpr int NG = NP * QT * QT;                    // result tiles of the metric per wave
+    static constexpr int NG = NP * QT * QT;                    // result tiles of the second product per wave
     static constexpr int BS = 16 * CT + (CT % 2 ? 32 : 16);    // row stride of sB: the 2 rows of a half wave on disjoint bank halves
 };
 
-template <int QT, bool JAC>
+// a: p [K][M][M] (R = M) or r [K][M][R];  out: g or jac;  vel, out2: the velocities and gam of christoffel, unused otherwise
+template <int QT, MtMode MODE>
 __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int ntn, const double *__restrict__ z,
                                                  const double *__restrict__ x, const double *__restrict__ gamma,
                                                  const double *__restrict__ alpha, const double *__restrict__ a,
-                                                 double *__restrict__ out) {
+                                                 double *__restrict__ out, const double *__restrict__ vel,
+                                                 double *__restrict__ out2) {
+    constexpr bool JAC = MODE == MT_JACOBIAN, CHR = MODE == MT_CHRISTOFFEL;
     constexpr int NP = MtCfg<QT>::NP, CT = MtCfg<QT>::CT, NG = MtCfg<QT>::NG, BS = MtCfg<QT>::BS;
     static_assert(NG * 256 <= MT_MS * BS, "the waves' result tiles are added in the feature buffer");
+    // sv and sd exist for christoffel only; elsewhere they take no room and are never touched
     extern __shared__ __align__(16) unsigned char smem_raw[];
     double *sx = reinterpret_cast<double *>(smem_raw);      // [NP][Q]   the points, 0 past N
-    double *sg = sx + (size_t)NP * Q;                        // [Q]       gamma_k
+    double *sv = sx + (CHR ? (size_t)NP * Q : 0);            // [NP][Q]   the velocities, 0 past N
+    double *sg = sv + (size_t)NP * Q;                        // [Q]       gamma_k
     double *sz = sg + Q;                                     // [64][Q]   z rows of the chunk, 0 past M
     double *sk = sz + (size_t)MT_MS * Q;                     // [64][NP]  k_km'(x_n), 0 past M or N
-    double *sP = sk + MT_MS * NP;                            // [64][PS]  A tile (slab rows x chunk indices), 0 out of range
-    double *sB = sP + MT_MS * MT_PS;                         // [64][BS]  features of the chunk, 0 in the padding
+    double *sd = sk + (CHR ? MT_MS * NP : 0);                // [64][NP]  d_knm', 0 past M or N
+    double *sP = sd + MT_MS * NP;                            // [64][PS]  A tile (slab rows x chunk indices), 0 out of range
+    double *sB = sP + MT_MS * MT_PS;                         // [64][BS]  features [b (| d)] of the chunk, 0 in the padding
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kk = lane >> 4;
     const int nt = blockIdx.x % ntn, k = blockIdx.x / ntn, n0 = nt * NP;
     const double *zk = z + (size_t)k * M * Q, *gk = gamma + (size_t)k * Q;
     const double *ak = a + (size_t)k * M * R;
     const double al = alpha[k];
-    for (int e = t; e < NP * Q; e += 256) sx[e] = n0 + e / Q < N ? x[(size_t)n0 * Q + e] : 0.0;
+    for (int e = t; e < NP * Q; e += 256) {
+        const bool in = n0 + e / Q < N;
+        sx[e] = in ? x[(size_t)n0 * Q + e] : 0.0;
+        if constexpr (CHR) sv[e] = in ? vel[(size_t)n0 * Q + e] : 0.0;
+    }
     for (int q = t; q < Q; q += 256) sg[q] = gk[q];
     const int nch = (M + MT_MS - 1) / MT_MS, nrs = (R + MT_MS - 1) / MT_MS;
     f64x4 G[JAC ? 1 : NG];
@@ -72,7 +98,7 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
         for (int ci = 0; ci < nch; ++ci) {
-            const int mc = JAC ? ci : (rs + 1 + ci) % nch;     // metric: the slab's own chunk last (R = M: nrs = nch)
+            const int mc = JAC ? ci : (rs + 1 + ci) % nch;     // second product: the slab's own chunk last (R = M: nrs = nch)
             const int c0 = mc * MT_MS, nc = min(MT_MS, M - c0);
             __syncthreads();                                   // (the points are staged; the previous chunk is consumed)
             for (int e = t; e < MT_MS * Q; e += 256) sz[e] = e / Q < nc ? zk[(size_t)c0 * Q + e] : 0.0;
@@ -86,22 +112,31 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
             __syncthreads();
             for (int e = t; e < MT_MS * NP; e += 256) {
                 const int rr = e / NP, i = e % NP;
-                double v = 0.0;
+                double v = 0.0, dv = 0.0;
                 if (rr < nc && n0 + i < N) {
-                    double ex = 0.0;
+                    double ex = 0.0, av = 0.0, s2 = 0.0;
                     for (int q = 0; q < Q; ++q) {
                         const double d = sx[i * Q + q] - sz[rr * Q + q];
                         ex = fma(-0.5 * DPGP_LOG2E * sg[q] * d, d, ex);
+                        if constexpr (CHR) {
+                            const double gv = sg[q] * sv[i * Q + q];
+                            av = fma(gv, d, av);
+                            s2 = fma(gv, sv[i * Q + q], s2);
+                        }
                     }
                     v = al * dpgp_exp2(ex);
+                    if constexpr (CHR) dv = v * (av * av - s2);
                 }
                 sk[e] = v;
+                if constexpr (CHR) sd[e] = dv;
             }
             __syncthreads();
             for (int e = t; e < MT_MS * BS; e += 256) {
                 const int rr = e / BS, col = e % BS, ct = col >> 4, i = ct / QT, q = ((ct % QT) << 4) + (col & 15);
                 double v = 0.0;
                 if (ct < CT && q < Q) v = -sg[q] * (sx[i * Q + q] - sz[rr * Q + q]) * sk[rr * NP + i];
+                if constexpr (CHR)
+                    if (ct < CT && q == Q) v = sd[rr * NP + i];
                 sB[e] = v;
             }
             __syncthreads();
@@ -126,7 +161,7 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
                 }
             }
         } else {
-            // g_n += B_n^T U_n over the wave's 16 rows: sB holds the slab's own features (the chunk walked last)
+            // G_n += B_n^T U_n over the wave's 16 rows: sB holds the slab's own features (the chunk walked last)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double *brow = sB + (16 * wave + 4 * r + kk) * BS + li;
@@ -158,60 +193,60 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
                 }
         }
         __syncthreads();
-        const int qq = Q * Q;
-        for (int e = t; e < NP * qq; e += 256) {
-            const int i = e / qq, rem = e % qq, q = rem / Q, qp = rem % Q;
+        // entry (row q, column c) of a point's product: tile (q >> 4, c >> 4), register (q & 15) >> 2, lane ((q & 3) << 4) | (c & 15).
+        // A point's Q Q entries of g; christoffel: then its gam, the first Q rows of column Q
+        const int qq = Q * Q, per = CHR ? qq + Q : qq;
+        for (int e = t; e < NP * per; e += 256) {
+            const int i = e / per, rem = e % per;
+            int q = rem / Q, c = rem % Q;
+            if constexpr (CHR)
+                if (rem >= qq) q = rem - qq, c = Q;
             if (n0 + i >= N) continue;
-            const int g = (i * QT + (q >> 4)) * QT + (qp >> 4), row = q & 15, col = qp & 15;
-            out[((size_t)k * N + n0 + i) * qq + rem] = sG[(g * 4 + (row >> 2)) * 64 + (((row & 3) << 4) | col)];
+            const int g = (i * QT + (q >> 4)) * QT + (c >> 4), row = q & 15, col = c & 15;
+            const double val = sG[(g * 4 + (row >> 2)) * 64 + (((row & 3) << 4) | col)];
+            if (CHR && rem >= qq) out2[((size_t)k * N + n0 + i) * Q + q] = val;
+            else out[((size_t)k * N + n0 + i) * qq + rem] = val;
         }
     }
 }
 
-size_t mt_lds(int Q, int np, int bs) {
-    return sizeof(double) * ((size_t)np * Q + Q + (size_t)MT_MS * Q + MT_MS * np + MT_MS * MT_PS + (size_t)MT_MS * bs);
+// the tile count of a point's columns, and what follows from it
+template <MtMode MODE> int mt_qt(int Q) { return dpgp_ceil_div(Q + (MODE == MT_CHRISTOFFEL), 16); }
+
+template <MtMode MODE> size_t mt_lds(int Q, int np, int bs) {
+    constexpr int V = MODE == MT_CHRISTOFFEL ? 2 : 1;          // (x | v) and (k | d)
+    return sizeof(double) * ((size_t)V * np * Q + Q + (size_t)MT_MS * Q + V * MT_MS * np + MT_MS * MT_PS + (size_t)MT_MS * bs);
 }
 
-int mt_points(int Q) { const int qt = dpgp_ceil_div(Q, 16); return qt == 1 ? 8 : qt == 2 ? 2 : 1; }
-
-// K, N, M, R >= 1, 1 <= Q <= 64, and sizes that the 32-bit grid and the int indices of the kernel hold
-bool mt_shape_ok(int K, int N, int M, int Q, int R) {
-    if (K < 1 || N < 1 || M < 1 || R < 1 || Q < 1 || Q > DPGP_QX_PSI_MAX_Q) return false;
-    if (N > MT_MAX_N || M > MT_MAX_N || R > MT_MAX_N) return false;
-    return (long)K * dpgp_ceil_div(N, mt_points(Q)) <= 0x7fffffffL;
+// K, N, M, R >= 1, 1 <= Q <= 64 (christoffel: 63), and sizes that the 32-bit grid and the int indices of the kernel hold
+template <MtMode MODE> bool mt_shape_ok(int K, int N, int M, int Q, int R) {
+    constexpr int max_q = MODE == MT_CHRISTOFFEL ? MT_CHRISTOFFEL_MAX_Q : DPGP_QX_PSI_MAX_Q;
+    if (Q < 1 || Q > max_q) return false;                      // (before Q goes into a tile count)
+    const int np = dpgp_dispatch_qt(mt_qt<MODE>(Q), [](auto qt) { return MtCfg<decltype(qt)::value>::NP; });
+    return dpgp_point_shape_ok(K, N, M, Q, R, max_q, np);
 }
 
-template <int QT, bool JAC>
+template <MtMode MODE>
 int mt_launch(int K, int N, int M, int Q, int R, const double *z, const double *x, const double *gamma, const double *alpha,
-              const double *a, double *out, hipStream_t st) {
-    const int ntn = dpgp_ceil_div(N, MtCfg<QT>::NP);
-    const size_t lds = mt_lds(Q, MtCfg<QT>::NP, MtCfg<QT>::BS);
-    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(mt_kernel<QT, JAC>), lds)) return DPGP_ERR_LAUNCH;
-    DPGP_PRELAUNCH();
-    hipLaunchKernelGGL((mt_kernel<QT, JAC>), dim3((unsigned)((long)K * ntn)), dim3(256), lds, st, N, M, Q, R, ntn, z, x, gamma,
-                       alpha, a, out);
-    DPGP_LAUNCH_CHECK();
-    return DPGP_OK;
-}
-
-template <bool JAC>
-int mt_dispatch(int K, int N, int M, int Q, int R, const double *z, const double *x, const double *gamma, const double *alpha,
-                const double *a, double *out, hipStream_t st) {
-    const int qt = dpgp_ceil_div(Q, 16);
-    return qt == 1   ? mt_launch<1, JAC>(K, N, M, Q, R, z, x, gamma, alpha, a, out, st)
-           : qt == 2 ? mt_launch<2, JAC>(K, N, M, Q, R, z, x, gamma, alpha, a, out, st)
-           : qt == 3 ? mt_launch<3, JAC>(K, N, M, Q, R, z, x, gamma, alpha, a, out, st)
-                     : mt_launch<4, JAC>(K, N, M, Q, R, z, x, gamma, alpha, a, out, st);
+              const double *a, double *out, const double *vel, double *out2, hipStream_t st) {
+    return dpgp_dispatch_qt(mt_qt<MODE>(Q), [&](auto qt) {
+        using Cfg = MtCfg<decltype(qt)::value>;
+        const auto kernel = mt_kernel<decltype(qt)::value, MODE>;
+        const int ntn = dpgp_ceil_div(N, Cfg::NP);
+        const size_t lds = mt_lds<MODE>(Q, Cfg::NP, Cfg::BS);
+        if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(kernel), lds)) return DPGP_ERR_LAUNCH;
+        DPGP_PRELAUNCH();
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((long)K * ntn)), dim3(256), lds, st, N, M, Q, R, ntn, z, x, gamma, alpha, a, out,
+                           vel, out2);
+        DPGP_LAUNCH_CHECK();
+        return DPGP_OK;
+    });
 }
 
 }  // namespace
 
-// The operators write their results from the accumulators and need no scratch memory; the query and the (ws, ws_bytes) pair
-// are there so that every point operator is called the same way.  DPGP_POINT_METRIC_WS bytes for a shape in range, 0 outside.
-#define DPGP_POINT_METRIC_WS 256
-
 extern "C" size_t dpgp_ard_rbf_point_metric_workspace_bytes(int K, int N, int M, int Q) {
-    return mt_shape_ok(K, N, M, Q, M) ? DPGP_POINT_METRIC_WS : 0;
+    return mt_shape_ok<MT_METRIC>(K, N, M, Q, M) ? DPGP_POINT_WS : 0;
 }
 
 extern "C" int dpgp_ard_rbf_point_metric_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *gamma,
@@ -230,11 +265,11 @@ extern "C" int dpgp_ard_rbf_point_metric_f64(int K, int N, int M, int Q, const d
     if (!ws) return -11;
     const size_t need = dpgp_ard_rbf_point_metric_workspace_bytes(K, N, M, Q);
     if (need == 0 || ws_bytes < need) return -12;              // (need == 0: a shape past what the launch grid holds)
-    return mt_dispatch<false>(K, N, M, Q, M, z, x, gamma, alpha, p, g, (hipStream_t)stream);
+    return mt_launch<MT_METRIC>(K, N, M, Q, M, z, x, gamma, alpha, p, g, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t dpgp_ard_rbf_point_jacobian_workspace_bytes(int K, int J, int N, int M, int Q) {
-    return mt_shape_ok(K, N, M, Q, J) ? DPGP_POINT_METRIC_WS : 0;
+    return mt_shape_ok<MT_JACOBIAN>(K, N, M, Q, J) ? DPGP_POINT_WS : 0;
 }
 
 extern "C" int dpgp_ard_rbf_point_jacobian_f64(int K, int J, int N, int M, int Q, const double *z, const double *x,
@@ -254,5 +289,30 @@ extern "C" int dpgp_ard_rbf_point_jacobian_f64(int K, int J, int N, int M, int Q
     if (!ws) return -12;
     const size_t need = dpgp_ard_rbf_point_jacobian_workspace_bytes(K, J, N, M, Q);
     if (need == 0 || ws_bytes < need) return -13;
-    return mt_dispatch<true>(K, N, M, Q, J, z, x, gamma, alpha, r, jac, (hipStream_t)stream);
+    return mt_launch<MT_JACOBIAN>(K, N, M, Q, J, z, x, gamma, alpha, r, jac, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" size_t dpgp_ard_rbf_point_christoffel_workspace_bytes(int K, int N, int M, int Q) {
+    return mt_shape_ok<MT_CHRISTOFFEL>(K, N, M, Q, M) ? DPGP_POINT_WS : 0;
+}
+
+extern "C" int dpgp_ard_rbf_point_christoffel_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *v,
+                                                  const double *gamma, const double *alpha, const double *p, double *g,
+                                                  double *gam, void *ws, size_t ws_bytes, void *stream) {
+    if (K < 1) return -1;
+    if (N < 1) return -2;
+    if (M < 1) return -3;
+    if (Q < 1 || Q > MT_CHRISTOFFEL_MAX_Q) return -4;
+    if (!z) return -5;
+    if (!x) return -6;
+    if (!v) return -7;
+    if (!gamma) return -8;
+    if (!alpha) return -9;
+    if (!p) return -10;
+    if (!g) return -11;
+    if (!gam) return -12;
+    if (!ws) return -13;
+    const size_t need = dpgp_ard_rbf_point_christoffel_workspace_bytes(K, N, M, Q);
+    if (need == 0 || ws_bytes < need) return -14;              // (need == 0: a shape past what the launch grid holds)
+    return mt_launch<MT_CHRISTOFFEL>(K, N, M, Q, M, z, x, gamma, alpha, p, g, v, gam, (hipStream_t)stream);
 }

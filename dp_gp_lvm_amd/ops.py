@@ -488,10 +488,10 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
 
 
 def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None):
-    """The checks of the four operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
-    (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M] or r [K,M,J], `what` its wording); dirs: the
-    directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), checked in their place after x;
-    max_q: an operator's own limit on Q (ValueError, after the shapes)."""
+    """The checks of the five point operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
+    (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M], r [K,M,J] or c [K,G,M,M], `what` its wording);
+    dirs: the directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), checked in their place
+    after x; max_q: an operator's own limit on Q (ValueError, after the shapes)."""
     args = (('z', z), ('x', x)) + (() if dirs is None else (('v', dirs[0]),)) + (('gamma', gamma), ('alpha', alpha), (name, a))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
@@ -507,7 +507,11 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None)
         raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
     if alpha.numel() != k:
         raise ValueError('alpha must be [K], got %s' % (tuple(alpha.shape),))
-    if a.dim() != 3 or a.shape[0] != k or a.shape[1] != m or a.shape[2] < 1 or (name == 'p' and a.shape[2] != m):
+    if name == 'c':
+        bad = a.dim() != 4 or a.shape[0] != k or a.shape[1] < 1 or a.shape[2] != m or a.shape[3] != m
+    else:
+        bad = a.dim() != 3 or a.shape[0] != k or a.shape[1] != m or a.shape[2] < 1 or (name == 'p' and a.shape[2] != m)
+    if bad:
         raise ValueError('%s must be %s, got %s' % (name, what, tuple(a.shape)))
     if max_q is not None and q > max_q:
         raise ValueError('z must have Q <= %d, got Q = %d' % (max_q, q))
@@ -515,6 +519,15 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None)
         if not v.is_cuda or v.device != z.device:
             raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
     return z.contiguous(), x.contiguous(), gamma.contiguous(), alpha.reshape(-1).contiguous(), a.contiguous(), k, x.shape[0], m, q
+
+
+def _point_call(op, dims, ins, outs):
+    """dpgp_ard_rbf_point_<op>_f64(*dims, *ins, *outs, ws, ws_bytes, stream) with the workspace that its query asks for."""
+    l = _lib.lib()
+    wsb = getattr(l, 'dpgp_ard_rbf_point_%s_workspace_bytes' % op)(*dims)
+    ws = _ws(wsb, ins[0].device)
+    fn = 'dpgp_ard_rbf_point_%s_f64' % op
+    _lib.check(getattr(l, fn)(*dims, *(t.data_ptr() for t in ins + outs), ws.data_ptr(), wsb, _stream()), fn)
 
 
 def ard_rbf_point_metric(z, x, gamma, alpha, p):
@@ -527,12 +540,7 @@ def ard_rbf_point_metric(z, x, gamma, alpha, p):
     (RuntimeError)."""
     z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]')
     g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
-    l = _lib.lib()
-    wsb = l.dpgp_ard_rbf_point_metric_workspace_bytes(k, n, m, q)
-    ws = _ws(wsb, z.device)
-    _lib.check(l.dpgp_ard_rbf_point_metric_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
-                                               p.data_ptr(), g.data_ptr(), ws.data_ptr(), wsb, _stream()),
-               'dpgp_ard_rbf_point_metric_f64')
+    _point_call('metric', (k, n, m, q), (z, x, gamma, alpha, p), (g,))
     return g
 
 
@@ -543,12 +551,7 @@ def ard_rbf_point_jacobian(z, x, gamma, alpha, r):
     z, x, gamma, alpha, r, k, n, m, q = _point_metric_args(z, x, gamma, alpha, r, 'r', '[K x M x J] with J >= 1')
     j = r.shape[2]
     jac = torch.empty((k, n, j, q), dtype=torch.float64, device=z.device)
-    l = _lib.lib()
-    wsb = l.dpgp_ard_rbf_point_jacobian_workspace_bytes(k, j, n, m, q)
-    ws = _ws(wsb, z.device)
-    _lib.check(l.dpgp_ard_rbf_point_jacobian_f64(k, j, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
-                                                 r.data_ptr(), jac.data_ptr(), ws.data_ptr(), wsb, _stream()),
-               'dpgp_ard_rbf_point_jacobian_f64')
+    _point_call('jacobian', (k, j, n, m, q), (z, x, gamma, alpha, r), (jac,))
     return jac
 
 
@@ -564,12 +567,7 @@ def ard_rbf_point_energy(z, x, v, gamma, alpha, p):
     e = torch.empty((k, n), dtype=torch.float64, device=z.device)
     dx = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
     dv = torch.empty_like(dx)
-    l = _lib.lib()
-    wsb = l.dpgp_ard_rbf_point_energy_workspace_bytes(k, n, m, q)
-    ws = _ws(wsb, z.device)
-    _lib.check(l.dpgp_ard_rbf_point_energy_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), v.data_ptr(), gamma.data_ptr(),
-                                               alpha.data_ptr(), p.data_ptr(), e.data_ptr(), dx.data_ptr(), dv.data_ptr(),
-                                               ws.data_ptr(), wsb, _stream()), 'dpgp_ard_rbf_point_energy_f64')
+    _point_call('energy', (k, n, m, q), (z, x, v, gamma, alpha, p), (e, dx, dv))
     return e, dx, dv
 
 
@@ -589,12 +587,7 @@ def ard_rbf_point_christoffel(z, x, v, gamma, alpha, p):
     v = v.contiguous()
     g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
     gam = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
-    l = _lib.lib()
-    wsb = l.dpgp_ard_rbf_point_christoffel_workspace_bytes(k, n, m, q)
-    ws = _ws(wsb, z.device)
-    _lib.check(l.dpgp_ard_rbf_point_christoffel_f64(k, n, m, q, z.data_ptr(), x.data_ptr(), v.data_ptr(), gamma.data_ptr(),
-                                                    alpha.data_ptr(), p.data_ptr(), g.data_ptr(), gam.data_ptr(), ws.data_ptr(),
-                                                    wsb, _stream()), 'dpgp_ard_rbf_point_christoffel_f64')
+    _point_call('christoffel', (k, n, m, q), (z, x, v, gamma, alpha, p), (g, gam))
     return g, gam
 
 
@@ -640,33 +633,10 @@ def ard_rbf_point_cov(z, x, gamma, alpha, c):
     c [K,G,M,M] with G >= 1 is any set of matrices; the result depends on their symmetric parts only and is exactly symmetric in
     (i, j).  One launch, the features shared by the G patterns of a kernel, nothing of size N M in memory; fixed summation order,
     the same bits on every run.  N <= 46340.  float64 tensors (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
-    args = (('z', z), ('x', x), ('gamma', gamma), ('alpha', alpha), ('c', c))
-    for nm, v in args:
-        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
-            raise TypeError('%s must be a float64 torch.Tensor' % nm)
-    if z.dim() != 3 or min(z.shape) < 1:
-        raise ValueError('z must be [K x M x Q], got %s' % (tuple(z.shape),))
-    k, m, q = z.shape
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != q:
-        raise ValueError('x must be [N x Q] with Q = %d, got %s' % (q, tuple(x.shape)))
-    if tuple(gamma.shape) != (k, q):
-        raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
-    if alpha.numel() != k:
-        raise ValueError('alpha must be [K], got %s' % (tuple(alpha.shape),))
-    if c.dim() != 4 or c.shape[0] != k or c.shape[1] < 1 or c.shape[2] != m or c.shape[3] != m:
-        raise ValueError('c must be [K x G x M x M] with G >= 1, got %s' % (tuple(c.shape),))
-    for nm, v in args:
-        if not v.is_cuda or v.device != z.device:
-            raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
-    z, x, gamma, alpha, c = z.contiguous(), x.contiguous(), gamma.contiguous(), alpha.reshape(-1).contiguous(), c.contiguous()
-    g, n = c.shape[1], x.shape[0]
+    z, x, gamma, alpha, c, k, n, m, q = _point_metric_args(z, x, gamma, alpha, c, 'c', '[K x G x M x M] with G >= 1')
+    g = c.shape[1]
     out = torch.empty((k, g, n, n), dtype=torch.float64, device=z.device)
-    l = _lib.lib()
-    wsb = l.dpgp_ard_rbf_point_cov_workspace_bytes(k, g, n, m, q)
-    ws = _ws(wsb, z.device)
-    _lib.check(l.dpgp_ard_rbf_point_cov_f64(k, g, n, m, q, z.data_ptr(), x.data_ptr(), gamma.data_ptr(), alpha.data_ptr(),
-                                            c.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb, _stream()),
-               'dpgp_ard_rbf_point_cov_f64')
+    _point_call('cov', (k, g, n, m, q), (z, x, gamma, alpha, c), (out,))
     return out
 
 

@@ -323,9 +323,9 @@ int dpgp_ard_rbf_point_energy_f64(int K, int N, int M, int Q, const double *z, c
                                   const double *gamma, const double *alpha, const double *p, double *e, double *dx, double *dv,
                                   void *ws, size_t ws_bytes, void *stream);
 
-/* ---- The geodesic equation at deterministic latent points (csrc/ard_rbf_point_christoffel.hip): what one stage of an integrator
- *      of x'' = -G(x)^-1 Gamma(x, x') needs.  Kernels, points x[N][Q] and p[K][M][M] as for the metric operator above; velocities
- *      v[N][Q], shared by the kernels.  With k_km and b_kmq as above and
+/* ---- The geodesic equation at deterministic latent points (csrc/ard_rbf_point_metric.hip, csrc/geodesic_accel.hip): what one
+ *      stage of an integrator of x'' = -G(x)^-1 Gamma(x, x') needs.  Kernels, points x[N][Q] and p[K][M][M] as for the metric
+ *      operator above; velocities v[N][Q], shared by the kernels.  With k_km and b_kmq as above and
  *        a_knm = sum_q gamma_kq (x_nq - z_kmq) v_nq,   d_knm = k_km(x_n) (a_knm^2 - sum_q gamma_kq v_nq^2) = v_n^T (d2 k_km / dx dx) v_n
  *      the first operator gives
  *        g[K][N][Q][Q] = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)         (exactly the metric operator's quantity)

@@ -1,5 +1,5 @@
-"""GPU tests of ops.ard_rbf_point_christoffel and ops.geodesic_accel (csrc/ard_rbf_point_christoffel.hip) against the np.longdouble
-references and the case tables of tests/test_point_christoffel_refs.py: random indefinite NON-symmetric p, z, x, v ~ N(0, 1) /
+"""GPU tests of ops.ard_rbf_point_christoffel (csrc/ard_rbf_point_metric.hip) and ops.geodesic_accel (csrc/geodesic_accel.hip)
+against the np.longdouble references and the case tables of tests/test_point_christoffel_refs.py: random indefinite NON-symmetric p, z, x, v ~ N(0, 1) /
 sqrt(Q), gamma in [0.2, 3].  Tolerances: 1e-12 relative to the sum of the absolute values of each entry's terms for g and gam (the
 sibling operators' bound); 1e-9 of max |a| for the acceleration, on matrices whose condition number the CPU file bounds by 1e4
 (the backward error of a Cholesky solve, a few Q eps cond = 63 * 1.1e-16 * 1e4 * small ~ 1e-10 at the worst case here)."""
@@ -52,12 +52,17 @@ def test_operator_against_the_longdouble_reference(i):
 
 @pytest.mark.parametrize('i', range(11), ids=[case_id(c) for c in CASES[:11]])
 def test_g_is_the_metric_operator(i):
+    """g within the tolerance of the metric operator's result, and equal to it bit for bit.  The equality holds by construction:
+    both operators are instantiations of one kernel (csrc/ard_rbf_point_metric.hip), the feature and exponent expressions are
+    the same source lines, and the summation order of an entry does not depend on the tile count QT, so it holds whether or not
+    the d column costs a tile (Q = 15 against Q = 16 in the case table)."""
     inp, ref = case(i)
     g, _ = run(inp)
     want = ops.ard_rbf_point_metric(dev(inp['z']), dev(inp['x']), dev(inp['gamma']), dev(inp['alpha']), dev(inp['p']))
     ratio = float(np.max(np.abs((g - want).cpu().numpy()) / np.asarray(ref['g_den'], dtype=np.float64)))
     print('%s: |g - metric operator| %.2e of sum |terms|' % (case_id(CASES[i]), ratio))
     assert ratio <= TOL
+    assert torch.equal(g, want)
 
 
 @pytest.mark.parametrize('i', [BASE, WIDE], ids=lambda i: case_id(CASES[i]))

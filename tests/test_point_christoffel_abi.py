@@ -1,8 +1,8 @@
-"""CPU tests (no GPU) of the C ABI of the geodesic-equation operators (include/dpgp.h, csrc/ard_rbf_point_christoffel.hip) and of the
-argument checks of their ops front-ends: the entry points are exported and bound, bad arguments come back with their negative
-codes in argument order and before anything is launched (every device pointer here is a dummy: a launch would fault), the
-workspace query is 0 for a shape out of range (Q = 64 included: the feature block is Q + 1 wide) and holds nothing of size N M, and
-ops raises TypeError / ValueError / RuntimeError as documented."""
+"""CPU tests (no GPU) of the C ABI of the geodesic-equation operators (include/dpgp.h, csrc/ard_rbf_point_metric.hip,
+csrc/geodesic_accel.hip) and of the argument checks of their ops front-ends: the entry points are exported and bound, bad
+arguments come back with their negative codes in argument order and before anything is launched (every device pointer here
+is a dummy: a launch would fault), the workspace query is 0 for a shape out of range (Q = 64 included: the feature block is
+Q + 1 wide) and holds nothing of size N M, and ops raises TypeError / ValueError / RuntimeError as documented."""
 import ctypes
 import os
 import re

@@ -1,5 +1,5 @@
 """CPU tests (no GPU) of the references that pin ops.ard_rbf_point_christoffel / ops.geodesic_accel
-(csrc/ard_rbf_point_christoffel.hip) and latent_exp_map (models/geodesic.exp_map): NumPy restatements in np.longdouble, a NumPy RK4
+(csrc/ard_rbf_point_metric.hip, csrc/geodesic_accel.hip) and latent_exp_map (models/geodesic.exp_map): NumPy restatements in np.longdouble, a NumPy RK4
 restatement of the integrator, the case tables that tests/test_gpu_point_christoffel.py and tests/test_gpu_latent_exp_map.py run,
 and checks of the references themselves.
 
