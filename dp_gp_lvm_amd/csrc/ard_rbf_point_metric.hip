@@ -1,8 +1,8 @@
-// Latent-space metric, predictive Jacobian and contracted Christoffel symbol of K ARD-RBF kernels at DETERMINISTIC latent points
-// x [N][Q].  With
+// Latent-space metric, predictive Jacobian, contracted Christoffel symbol and its tangent of K ARD-RBF kernels at DETERMINISTIC
+// latent points x [N][Q].  With
 //   k_km(x_n)  = alpha_k exp(-1/2 sum_q gamma_kq (x_nq - z_kmq)^2)
 //   b_kmq(x_n) = d k_km / d x_q = -gamma_kq (x_nq - z_kmq) k_km(x_n)                    the derivative features [M x Q] of point n
-// the three operators are
+// the four operators are
 //   metric:      g[k][n][q][q']  = sum_{m,m'} p[k][m][m'] b_kmq(x_n) b_km'q'(x_n)         p [K][M][M], used as given (not symmetrised)
 //   jacobian:    jac[k][n][j][q] = sum_m b_kmq(x_n) r[k][m][j]                           r [K][M][J]
 //   christoffel: g as the metric's, and with velocities v [N][Q],
@@ -11,7 +11,12 @@
 //                gam[k][n][q]    = sum_{m,m'} b_kmq(x_n) p[k][m][m'] d_knm'
 //                For symmetric p, gam is the Christoffel symbol of the first kind of g contracted twice with v,
 //                  gam = (D_v g) v - 1/2 grad_x (v^T g v):    the (Hv)^T p c terms of the two parts cancel, H the Hessian features.
-// ONE kernel, mt_kernel<QT, MODE>, does all three; what exists in one mode only sits behind `if constexpr`.
+//   tangent:     g and gam as christoffel's (the same bits), and their derivatives along a direction (dx, dv) [N][Q] of (x, v):
+//                with u_q = gamma_kq (x_nq - z_kmq), s = sum_q gamma_kq v_nq^2,
+//                  e = sum_q u_q dx_q,   f = sum_q u_q dv_q,   c1 = sum_q gamma_kq dx_q v_q,   c2 = sum_q gamma_kq v_q dv_q
+//                  db_q = k (e u_q - gamma_kq dx_q),           dd = k (-e (a^2 - s) + 2 a (c1 + f) - 2 c2)
+//                dg[k][n][q][q'] = (dB^T p B + B^T p dB)_qq',    dgam[k][n][q] = (dB^T p d + B^T p dd)_q
+// ONE kernel, mt_kernel<QT, MODE>, does all four; what exists in one mode only sits behind `if constexpr`.
 // The features B [M x (points, q)] are never stored to memory: a workgroup makes them on the fly, 64 inducing points at a time,
 // into LDS, one exponential per (k, n, m) and per slab of 64 rows of the left operand.
 //
@@ -34,20 +39,33 @@
 //             at the end the four waves' tiles are added in wave order through LDS and stored.
 //   christoffel: the same with F in the place of B: F^T p F holds g in its leading Q x Q block and gam in the first Q rows of its
 //             last column.  An entry of g is summed in the metric's order whether or not the d column costs a tile: the same bits.
+//   tangent:  the same with F = [B | d | dB | dd], W = 2 Q + 2: all four results are entries of F^T p F, g and gam where
+//             christoffel has them, dg = (rows 0 .. Q-1, columns Q+1 .. 2Q) + (rows Q+1 .. 2Q, columns 0 .. Q-1), dgam = (rows
+//             Q+1 .. 2Q, column Q) + (rows 0 .. Q-1, column 2Q+1).  The result tiles inside the (dB | dd)^T p (dB | dd) block are
+//             read by nothing and are not formed (QT = 2: one of four, QT = 3: one of nine, QT = 4: four of sixteen).  Q <= 31.
 // The order of every sum is fixed by (M, Q) alone: no atomics, no workspace, the same bits on every run; a point's results depend
 // neither on N, nor on its place in x, nor on K or the other kernels.  Far-away points: dpgp_exp2 gives exact zeros, every product
-// with them is 0.  1 <= Q <= 64; christoffel 1 <= Q <= 63 (W <= 64).
+// with them is 0.  1 <= Q <= 64; christoffel 1 <= Q <= 63, tangent 1 <= Q <= 31 (W <= 64).
 // LDS: 8 (NP Q + Q + 64 Q + 64 NP + 64 66 + 64 BS) bytes, BS = 16 CT + 16 (+ 16 for odd CT): 120.4 KiB at Q = 16, 109.5 KiB at Q = 64;
-// christoffel 8 (2 NP Q + Q + 64 Q + 128 NP + 64 66 + 64 BS): 122.5 KiB at Q = 15, 107.0 KiB at Q = 63.
+// christoffel 8 (2 NP Q + Q + 64 Q + 128 NP + 64 66 + 64 BS): 122.5 KiB at Q = 15, 107.0 KiB at Q = 63;
+// tangent 8 (4 NP Q + Q + 64 Q + 256 NP + 64 66 + 64 BS): 126.3 KiB at Q = 7, 85.6 KiB at Q = 15, 87.4 KiB at Q = 23, 91.7 KiB at Q = 31.
 #include "point_tile.h"
 
 #define MT_MS DPGP_POINT_MS
 #define MT_PS DPGP_POINT_PS
 #define MT_CHRISTOFFEL_MAX_Q 63
 
+#define MT_TANGENT_MAX_Q 31
+
 namespace {
 
-enum MtMode { MT_METRIC, MT_JACOBIAN, MT_CHRISTOFFEL };
+enum MtMode { MT_METRIC, MT_JACOBIAN, MT_CHRISTOFFEL, MT_TANGENT };
+
+// what the tangent mode takes beyond the family's arguments: the direction (dx, dv) [N][Q] of the state (x, v) and the two results
+struct MtTan {
+    const double *dx, *dv;
+    double *dg, *dgam;
+};
 
 template <int QT> struct MtCfg {
     static constexpr int NP = QT == 1 ? 8 : QT == 2 ? 2 : 1;   // points per workgroup
@@ -56,35 +74,54 @@ template <int QT> struct MtCfg {
     static constexpr int BS = 16 * CT + (CT % 2 ? 32 : 16);    // row stride of sB: the 2 rows of a half wave on disjoint bank halves
 };
 
-// a: p [K][M][M] (R = M) or r [K][M][R];  out: g or jac;  vel, out2: the velocities and gam of christoffel, unused otherwise
-template <int QT, MtMode MODE>
+__device__ __forceinline__ const MtTan &mt_only(const MtTan &a) { return a; }
+
+// tangent: result tile (qi, qj) of a point's product lies in the (db | dd)^T p (db | dd) block, which no output reads:
+// Q + 1 <= 8 QT, so it does as soon as both tile indices reach QT / 2 (QT = 2: the lower-right tile, QT = 4: the lower-right four)
+__device__ __forceinline__ constexpr bool mt_tan_unread(int qt, int qi, int qj) { return 2 * qi >= qt && 2 * qj >= qt; }
+
+// a: p [K][M][M] (R = M) or r [K][M][R];  out: g or jac;  vel, out2: the velocities and gam of christoffel and tangent, unused
+// otherwise;  tan: ONE MtTan in the tangent mode, nothing in the others (their kernel arguments are the ones they always had)
+template <int QT, MtMode MODE, class... TAN_ARGS>
 __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int ntn, const double *__restrict__ z,
                                                  const double *__restrict__ x, const double *__restrict__ gamma,
                                                  const double *__restrict__ alpha, const double *__restrict__ a,
                                                  double *__restrict__ out, const double *__restrict__ vel,
-                                                 double *__restrict__ out2) {
-    constexpr bool JAC = MODE == MT_JACOBIAN, CHR = MODE == MT_CHRISTOFFEL;
+                                                 double *__restrict__ out2, TAN_ARGS... tan) {
+    constexpr bool JAC = MODE == MT_JACOBIAN, TAN = MODE == MT_TANGENT, CHR = MODE == MT_CHRISTOFFEL || TAN;
+    static_assert(sizeof...(TAN_ARGS) == (TAN ? 1 : 0), "MtTan goes with the tangent mode alone");
     constexpr int NP = MtCfg<QT>::NP, CT = MtCfg<QT>::CT, NG = MtCfg<QT>::NG, BS = MtCfg<QT>::BS;
     static_assert(NG * 256 <= MT_MS * BS, "the waves' result tiles are added in the feature buffer");
-    // sv and sd exist for christoffel only; elsewhere they take no room and are never touched
+    // sv and sd exist for christoffel and tangent only, sdx, sdv, se and sdd for tangent only; elsewhere they take no room and
+    // are never touched
     extern __shared__ __align__(16) unsigned char smem_raw[];
     double *sx = reinterpret_cast<double *>(smem_raw);      // [NP][Q]   the points, 0 past N
     double *sv = sx + (CHR ? (size_t)NP * Q : 0);            // [NP][Q]   the velocities, 0 past N
-    double *sg = sv + (size_t)NP * Q;                        // [Q]       gamma_k
+    double *sdx = sv + (TAN ? (size_t)NP * Q : 0);           // [NP][Q]   the direction's dx, 0 past N
+    double *sdv = sdx + (TAN ? (size_t)NP * Q : 0);          // [NP][Q]   the direction's dv, 0 past N
+    double *sg = sdv + (size_t)NP * Q;                       // [Q]       gamma_k
     double *sz = sg + Q;                                     // [64][Q]   z rows of the chunk, 0 past M
     double *sk = sz + (size_t)MT_MS * Q;                     // [64][NP]  k_km'(x_n), 0 past M or N
     double *sd = sk + (CHR ? MT_MS * NP : 0);                // [64][NP]  d_knm', 0 past M or N
-    double *sP = sd + MT_MS * NP;                            // [64][PS]  A tile (slab rows x chunk indices), 0 out of range
-    double *sB = sP + MT_MS * MT_PS;                         // [64][BS]  features [b (| d)] of the chunk, 0 in the padding
+    double *se = sd + (TAN ? MT_MS * NP : 0);                // [64][NP]  e_knm' = sum_q gamma_kq (x_nq - z_km'q) dx_nq
+    double *sdd = se + (TAN ? MT_MS * NP : 0);               // [64][NP]  the tangent of d_knm', 0 past M or N
+    double *sP = sdd + MT_MS * NP;                           // [64][PS]  A tile (slab rows x chunk indices), 0 out of range
+    double *sB = sP + MT_MS * MT_PS;                         // [64][BS]  features [b (| d (| db | dd))] of the chunk, 0 in the padding
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kk = lane >> 4;
     const int nt = blockIdx.x % ntn, k = blockIdx.x / ntn, n0 = nt * NP;
     const double *zk = z + (size_t)k * M * Q, *gk = gamma + (size_t)k * Q;
     const double *ak = a + (size_t)k * M * R;
     const double al = alpha[k];
+    MtTan ta{};
+    if constexpr (TAN) ta = mt_only(tan...);
     for (int e = t; e < NP * Q; e += 256) {
         const bool in = n0 + e / Q < N;
         sx[e] = in ? x[(size_t)n0 * Q + e] : 0.0;
         if constexpr (CHR) sv[e] = in ? vel[(size_t)n0 * Q + e] : 0.0;
+        if constexpr (TAN) {
+            sdx[e] = in ? ta.dx[(size_t)n0 * Q + e] : 0.0;
+            sdv[e] = in ? ta.dv[(size_t)n0 * Q + e] : 0.0;
+        }
     }
     for (int q = t; q < Q; q += 256) sg[q] = gk[q];
     const int nch = (M + MT_MS - 1) / MT_MS, nrs = (R + MT_MS - 1) / MT_MS;
@@ -112,9 +149,9 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
             __syncthreads();
             for (int e = t; e < MT_MS * NP; e += 256) {
                 const int rr = e / NP, i = e % NP;
-                double v = 0.0, dv = 0.0;
+                double v = 0.0, dv = 0.0, ev = 0.0, ddv = 0.0;
                 if (rr < nc && n0 + i < N) {
-                    double ex = 0.0, av = 0.0, s2 = 0.0;
+                    double ex = 0.0, av = 0.0, s2 = 0.0, fv = 0.0, c1 = 0.0, c2 = 0.0;
                     for (int q = 0; q < Q; ++q) {
                         const double d = sx[i * Q + q] - sz[rr * Q + q];
                         ex = fma(-0.5 * DPGP_LOG2E * sg[q] * d, d, ex);
@@ -122,13 +159,22 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
                             const double gv = sg[q] * sv[i * Q + q];
                             av = fma(gv, d, av);
                             s2 = fma(gv, sv[i * Q + q], s2);
+                            if constexpr (TAN) {
+                                const double u = sg[q] * d;
+                                ev = fma(u, sdx[i * Q + q], ev);
+                                fv = fma(u, sdv[i * Q + q], fv);
+                                c1 = fma(gv, sdx[i * Q + q], c1);
+                                c2 = fma(gv, sdv[i * Q + q], c2);
+                            }
                         }
                     }
                     v = al * dpgp_exp2(ex);
                     if constexpr (CHR) dv = v * (av * av - s2);
+                    if constexpr (TAN) ddv = v * (2.0 * av * (c1 + fv) - ev * (av * av - s2) - 2.0 * c2);
                 }
                 sk[e] = v;
                 if constexpr (CHR) sd[e] = dv;
+                if constexpr (TAN) se[e] = ev, sdd[e] = ddv;
             }
             __syncthreads();
             for (int e = t; e < MT_MS * BS; e += 256) {
@@ -137,6 +183,14 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
                 if (ct < CT && q < Q) v = -sg[q] * (sx[i * Q + q] - sz[rr * Q + q]) * sk[rr * NP + i];
                 if constexpr (CHR)
                     if (ct < CT && q == Q) v = sd[rr * NP + i];
+                if constexpr (TAN) {
+                    // db_q = k (e u_q - gamma_q dx_q) in columns Q + 1 .. 2 Q, dd in column 2 Q + 1
+                    if (ct < CT && q > Q && q <= 2 * Q) {
+                        const int r = q - Q - 1;
+                        v = sk[rr * NP + i] * (se[rr * NP + i] * (sg[r] * (sx[i * Q + r] - sz[rr * Q + r])) - sg[r] * sdx[i * Q + r]);
+                    }
+                    if (ct < CT && q == 2 * Q + 1) v = sdd[rr * NP + i];
+                }
                 sB[e] = v;
             }
             __syncthreads();
@@ -172,6 +226,8 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
                         const double bv = brow[16 * (i * QT + qi)];
 #pragma unroll
                         for (int qj = 0; qj < QT; ++qj) {
+                            if constexpr (TAN)
+                                if (mt_tan_unread(QT, qi, qj)) continue;
                             const int g = (i * QT + qi) * QT + qj;
                             G[g] = Mfma<double>::mma(bv, acc[i * QT + qj][r], G[g]);
                         }
@@ -185,59 +241,90 @@ __global__ __launch_bounds__(256) void mt_kernel(int N, int M, int Q, int R, int
             __syncthreads();                                       // (w = 0: every wave is done with the features)
             if (wave != w) continue;
 #pragma unroll
-            for (int g = 0; g < NG; ++g)
+            for (int g = 0; g < NG; ++g) {
+                if constexpr (TAN)
+                    if (mt_tan_unread(QT, (g / QT) % QT, g % QT)) continue;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = (g * 4 + r) * 64 + lane;
                     sG[o] = w == 0 ? G[g][r] : sG[o] + G[g][r];
                 }
+            }
         }
         __syncthreads();
         // entry (row q, column c) of a point's product: tile (q >> 4, c >> 4), register (q & 15) >> 2, lane ((q & 3) << 4) | (c & 15).
         // A point's Q Q entries of g; christoffel: then its gam, the first Q rows of column Q
-        const int qq = Q * Q, per = CHR ? qq + Q : qq;
-        for (int e = t; e < NP * per; e += 256) {
-            const int i = e / per, rem = e % per;
-            int q = rem / Q, c = rem % Q;
-            if constexpr (CHR)
-                if (rem >= qq) q = rem - qq, c = Q;
-            if (n0 + i >= N) continue;
-            const int g = (i * QT + (q >> 4)) * QT + (c >> 4), row = q & 15, col = c & 15;
-            const double val = sG[(g * 4 + (row >> 2)) * 64 + (((row & 3) << 4) | col)];
-            if (CHR && rem >= qq) out2[((size_t)k * N + n0 + i) * Q + q] = val;
-            else out[((size_t)k * N + n0 + i) * qq + rem] = val;
+        const int qq = Q * Q, per = TAN ? 2 * (qq + Q) : CHR ? qq + Q : qq;
+        if constexpr (TAN) {
+            // then dg = (rows 0 .. Q - 1, columns Q + 1 .. 2 Q) + (rows Q + 1 .. 2 Q, columns 0 .. Q - 1) and
+            // dgam = (rows Q + 1 .. 2 Q, column Q) + (rows 0 .. Q - 1, column 2 Q + 1)
+            for (int e = t; e < NP * per; e += 256) {
+                const int i = e / per, rem = e % per;
+                if (n0 + i >= N) continue;
+                const auto entry = [&](int q, int c) {
+                    const int g = (i * QT + (q >> 4)) * QT + (c >> 4), row = q & 15, col = c & 15;
+                    return sG[(g * 4 + (row >> 2)) * 64 + (((row & 3) << 4) | col)];
+                };
+                const size_t pt = (size_t)k * N + n0 + i;
+                if (rem < qq) out[pt * qq + rem] = entry(rem / Q, rem % Q);
+                else if (rem < qq + Q) out2[pt * Q + rem - qq] = entry(rem - qq, Q);
+                else if (rem < 2 * qq + Q) {
+                    const int r = rem - qq - Q, q = r / Q, c = r % Q;
+                    ta.dg[pt * qq + r] = entry(q, Q + 1 + c) + entry(Q + 1 + q, c);
+                } else {
+                    const int q = rem - 2 * qq - Q;
+                    ta.dgam[pt * Q + q] = entry(Q + 1 + q, Q) + entry(q, 2 * Q + 1);
+                }
+            }
+        } else {
+            for (int e = t; e < NP * per; e += 256) {
+                const int i = e / per, rem = e % per;
+                int q = rem / Q, c = rem % Q;
+                if constexpr (CHR)
+                    if (rem >= qq) q = rem - qq, c = Q;
+                if (n0 + i >= N) continue;
+                const int g = (i * QT + (q >> 4)) * QT + (c >> 4), row = q & 15, col = c & 15;
+                const double val = sG[(g * 4 + (row >> 2)) * 64 + (((row & 3) << 4) | col)];
+                if (CHR && rem >= qq) out2[((size_t)k * N + n0 + i) * Q + q] = val;
+                else out[((size_t)k * N + n0 + i) * qq + rem] = val;
+            }
         }
     }
 }
 
-// the tile count of a point's columns, and what follows from it
-template <MtMode MODE> int mt_qt(int Q) { return dpgp_ceil_div(Q + (MODE == MT_CHRISTOFFEL), 16); }
+// the tile count of a point's columns, and what follows from it: W = Q, Q + 1 (christoffel), 2 Q + 2 (tangent)
+template <MtMode MODE> int mt_qt(int Q) {
+    return dpgp_ceil_div(MODE == MT_TANGENT ? 2 * Q + 2 : Q + (MODE == MT_CHRISTOFFEL), 16);
+}
 
 template <MtMode MODE> size_t mt_lds(int Q, int np, int bs) {
-    constexpr int V = MODE == MT_CHRISTOFFEL ? 2 : 1;          // (x | v) and (k | d)
+    constexpr int V = MODE == MT_TANGENT ? 4 : MODE == MT_CHRISTOFFEL ? 2 : 1;   // (x | v | dx | dv) and (k | d | e | dd)
     return sizeof(double) * ((size_t)V * np * Q + Q + (size_t)MT_MS * Q + V * MT_MS * np + MT_MS * MT_PS + (size_t)MT_MS * bs);
 }
 
-// K, N, M, R >= 1, 1 <= Q <= 64 (christoffel: 63), and sizes that the 32-bit grid and the int indices of the kernel hold
+// K, N, M, R >= 1, 1 <= Q <= 64 (christoffel: 63, tangent: 31), and sizes that the 32-bit grid and the int indices of the kernel hold
 template <MtMode MODE> bool mt_shape_ok(int K, int N, int M, int Q, int R) {
-    constexpr int max_q = MODE == MT_CHRISTOFFEL ? MT_CHRISTOFFEL_MAX_Q : DPGP_QX_PSI_MAX_Q;
+    constexpr int max_q = MODE == MT_TANGENT ? MT_TANGENT_MAX_Q : MODE == MT_CHRISTOFFEL ? MT_CHRISTOFFEL_MAX_Q : DPGP_QX_PSI_MAX_Q;
     if (Q < 1 || Q > max_q) return false;                      // (before Q goes into a tile count)
     const int np = dpgp_dispatch_qt(mt_qt<MODE>(Q), [](auto qt) { return MtCfg<decltype(qt)::value>::NP; });
     return dpgp_point_shape_ok(K, N, M, Q, R, max_q, np);
 }
 
-template <MtMode MODE>
+// tan: the tangent mode's MtTan, nothing otherwise
+template <MtMode MODE, class... TAN_ARGS>
 int mt_launch(int K, int N, int M, int Q, int R, const double *z, const double *x, const double *gamma, const double *alpha,
-              const double *a, double *out, const double *vel, double *out2, hipStream_t st) {
+              const double *a, double *out, const double *vel, double *out2, hipStream_t st, TAN_ARGS... tan) {
     return dpgp_dispatch_qt(mt_qt<MODE>(Q), [&](auto qt) {
         using Cfg = MtCfg<decltype(qt)::value>;
-        const auto kernel = mt_kernel<decltype(qt)::value, MODE>;
+        void (*const kernel)(int, int, int, int, int, const double *, const double *, const double *, const double *,
+                             const double *, double *, const double *, double *, TAN_ARGS...) =
+            mt_kernel<decltype(qt)::value, MODE, TAN_ARGS...>;
         const int ntn = dpgp_ceil_div(N, Cfg::NP);
         const size_t lds = mt_lds<MODE>(Q, Cfg::NP, Cfg::BS);
         if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(kernel), lds)) return DPGP_ERR_LAUNCH;
         DPGP_PRELAUNCH();
         hipLaunchKernelGGL(kernel, dim3((unsigned)((long)K * ntn)), dim3(256), lds, st, N, M, Q, R, ntn, z, x, gamma, alpha, a, out,
-                           vel, out2);
+                           vel, out2, tan...);
         DPGP_LAUNCH_CHECK();
         return DPGP_OK;
     });
@@ -315,4 +402,35 @@ extern "C" int dpgp_ard_rbf_point_christoffel_f64(int K, int N, int M, int Q, co
     const size_t need = dpgp_ard_rbf_point_christoffel_workspace_bytes(K, N, M, Q);
     if (need == 0 || ws_bytes < need) return -14;              // (need == 0: a shape past what the launch grid holds)
     return mt_launch<MT_CHRISTOFFEL>(K, N, M, Q, M, z, x, gamma, alpha, p, g, v, gam, (hipStream_t)stream);
+}
+
+extern "C" size_t dpgp_ard_rbf_point_christoffel_tangent_workspace_bytes(int K, int N, int M, int Q) {
+    return mt_shape_ok<MT_TANGENT>(K, N, M, Q, M) ? DPGP_POINT_WS : 0;
+}
+
+extern "C" int dpgp_ard_rbf_point_christoffel_tangent_f64(int K, int N, int M, int Q, const double *z, const double *x,
+                                                          const double *v, const double *dx, const double *dv,
+                                                          const double *gamma, const double *alpha, const double *p, double *g,
+                                                          double *gam, double *dg, double *dgam, void *ws, size_t ws_bytes,
+                                                          void *stream) {
+    if (K < 1) return -1;
+    if (N < 1) return -2;
+    if (M < 1) return -3;
+    if (Q < 1 || Q > MT_TANGENT_MAX_Q) return -4;
+    if (!z) return -5;
+    if (!x) return -6;
+    if (!v) return -7;
+    if (!dx) return -8;
+    if (!dv) return -9;
+    if (!gamma) return -10;
+    if (!alpha) return -11;
+    if (!p) return -12;
+    if (!g) return -13;
+    if (!gam) return -14;
+    if (!dg) return -15;
+    if (!dgam) return -16;
+    if (!ws) return -17;
+    const size_t need = dpgp_ard_rbf_point_christoffel_tangent_workspace_bytes(K, N, M, Q);
+    if (need == 0 || ws_bytes < need) return -18;              // (need == 0: a shape past what the launch grid holds)
+    return mt_launch<MT_TANGENT>(K, N, M, Q, M, z, x, gamma, alpha, p, g, v, gam, (hipStream_t)stream, MtTan{dx, dv, dg, dgam});
 }

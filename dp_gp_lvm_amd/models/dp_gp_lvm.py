@@ -760,8 +760,9 @@ def dp_gp_lvm(y_train,
             prior = torch.cat([prior, prior_unseen[None]])
         return lambda x, v: marg.curve_terms(x, v, p, prior)
 
-    def _geodesic_terms(columns, name):
-        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms."""
+    def _geodesic_terms(columns, name, tangent=False):
+        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms;
+        tangent: with its derivative along a direction (marginals.geodesic_tangent_terms)."""
         assert not split, '%s is not built for a model sharded over a process group' % name
         cols = _geometry_columns(columns)
         evaluate()
@@ -769,9 +770,13 @@ def dp_gp_lvm(y_train,
             marg, _, prior_unseen = _latent_geometry(cols)
             if marg is None:
                 weight = torch.diagonal(prior_unseen).contiguous()
+                if tangent:
+                    return lambda x, v, dx, dv: _geodesic.prior_accel_tangent(v, weight)
                 return lambda x, v: _geodesic.prior_accel(v, weight)
             p, prior = marg._metric_operands(None, None)
             prior = torch.cat([prior, prior_unseen[None]])
+        if tangent:
+            return lambda x, v, dx, dv: marg.geodesic_tangent_terms(x, v, dx, dv, p, prior)
         return lambda x, v: marg.geodesic_terms(x, v, p, prior)
 
     def _assembled_marginals(cols, xt, st_):
@@ -1200,6 +1205,36 @@ def dp_gp_lvm(y_train,
             at any stage.  fp64, torch.no_grad.  Not built for a model sharded over a process group: AssertionError."""
             return _geodesic.exp_map(_geodesic_terms(columns, 'latent_exp_map'), x, v, num_latent_dims, device, num_steps,
                                      return_velocity)
+
+        @staticmethod
+        def geodesic_deviation(x, v, dx, dv, columns=None):
+            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
+            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
+            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
+            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad.
+            Not built for a model sharded over a process group: AssertionError."""
+            return _geodesic.geodesic_deviation(_geodesic_terms(columns, 'geodesic_deviation', True), x, v, dx, dv, num_latent_dims, device)
+
+        @staticmethod
+        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
+            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
+            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
+            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
+            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
+            any stage.  Q <= 31.  fp64, torch.no_grad.
+            Not built for a model sharded over a process group: AssertionError."""
+            return _geodesic.exp_map_tangent(_geodesic_terms(columns, 'latent_exp_map_tangent', True), x, v, dx, dv, num_latent_dims, device, num_steps, return_velocity)
+
+        @staticmethod
+        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
+            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
+            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
+            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
+            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
+            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
+            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad.
+            Not built for a model sharded over a process group: AssertionError."""
+            return _geodesic.log_map(_geodesic_terms(columns, 'latent_log_map', True), x_from, x_to, num_latent_dims, device, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1840,12 +1875,15 @@ def dp_gp_lvm_t(y_train,
             p, prior = mom.curve_operands(cols)
         return lambda x, v: mom.curve_terms(x, v, p, prior)
 
-    def _geodesic_terms(columns):
-        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms."""
+    def _geodesic_terms(columns, tangent=False):
+        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms;
+        tangent: with its derivative along a direction (marginals.geodesic_tangent_terms)."""
         cols = _columns_arg(columns)
         with torch.no_grad():
             mom = _moments()
             p, prior = mom.curve_operands(cols)
+        if tangent:
+            return lambda x, v, dx, dv: mom.geodesic_tangent_terms(x, v, dx, dv, p, prior)
         return lambda x, v: mom.geodesic_terms(x, v, p, prior)
 
     class DP_GP_LVM_T(Trainable):
@@ -2104,6 +2142,33 @@ def dp_gp_lvm_t(y_train,
             element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
             metric failed to factor at any stage.  fp64, torch.no_grad."""
             return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, device, num_steps, return_velocity)
+
+        @staticmethod
+        def geodesic_deviation(x, v, dx, dv, columns=None):
+            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
+            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
+            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
+            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.geodesic_deviation(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, device)
+
+        @staticmethod
+        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
+            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
+            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
+            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
+            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
+            any stage.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.exp_map_tangent(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, device, num_steps, return_velocity)
+
+        @staticmethod
+        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
+            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
+            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
+            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
+            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
+            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
+            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.log_map(_geodesic_terms(columns, True), x_from, x_to, num_latent_dims, device, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

@@ -164,3 +164,7 @@ class _MomentsT:
         """marginals._Marginals.geodesic_terms on the T atoms, (p, prior) from curve_operands: the acceleration under metric's
         G, phi included."""
         return self._curve_atoms.geodesic_terms(x, v, p, prior)
+
+    def geodesic_tangent_terms(self, x, v, dx, dv, p, prior):
+        """marginals._Marginals.geodesic_tangent_terms on the T atoms, (p, prior) from curve_operands."""
+        return self._curve_atoms.geodesic_tangent_terms(x, v, dx, dv, p, prior)

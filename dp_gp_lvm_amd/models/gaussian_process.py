@@ -515,12 +515,15 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             p, prior = marg._metric_operands(cols, None)
         return lambda x, v: marg.curve_terms(x, v, p, prior)
 
-    def _geodesic_terms(columns):
-        """The acceleration of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+    def _geodesic_terms(columns, tangent=False):
+        """The acceleration of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once;
+        tangent: the acceleration with its derivative along a direction (marginals.geodesic_tangent_terms)."""
         cols = _marginals.columns_arg(columns, num_dimensions, dev_)
         with torch.no_grad():
             marg = _train_marginals()
             p, prior = marg._metric_operands(cols, None)
+        if tangent:
+            return lambda x, v, dx, dv: marg.geodesic_tangent_terms(x, v, dx, dv, p, prior)
         return lambda x, v: marg.geodesic_terms(x, v, p, prior)
 
     class BayesianGPLVM(Trainable):
@@ -632,6 +635,33 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             plus element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
             metric failed to factor at any stage.  fp64, torch.no_grad."""
             return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, dev_, num_steps, return_velocity)
+
+        @staticmethod
+        def geodesic_deviation(x, v, dx, dv, columns=None):
+            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
+            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
+            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
+            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.geodesic_deviation(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, dev_)
+
+        @staticmethod
+        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
+            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
+            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
+            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
+            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
+            any stage.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.exp_map_tangent(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, dev_, num_steps, return_velocity)
+
+        @staticmethod
+        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
+            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
+            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
+            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
+            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
+            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
+            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad."""
+            return _geodesic.log_map(_geodesic_terms(columns, True), x_from, x_to, num_latent_dims, dev_, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predictive_covariance(x, columns=None, noise=False):
@@ -1108,17 +1138,18 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         each = [lambda x, v, marg=train[vv], pair=pair: marg.curve_terms(x, v, *pair) for vv, pair in zip(vs, pairs)]
         return [_geodesic.sum_terms(each)] if total else each
 
-    def _geodesic_terms(views, total):
+    def _geodesic_terms(views, total, tangent=False):
         """The accelerations of models/geodesic.py of every view of `views` (one entry: under their summed metric, with total: the
-        views' slabs go to one factorisation), formed once."""
+        views' slabs go to one factorisation), formed once; tangent: with their derivatives along a direction
+        (marginals.geodesic_tangent_terms)."""
         vs = _views_arg(views)
         with torch.no_grad():
             train = _train_marginals()
             pairs = [train[v]._metric_operands(None, None) for v in vs]
+        make = _marginals.geodesic_tangent_terms if tangent else _marginals.geodesic_terms
         if total:
-            return [_marginals.geodesic_terms([(train[vv], pair[0]) for vv, pair in zip(vs, pairs)],
-                                              torch.cat([pair[1] for pair in pairs]))]
-        return [_marginals.geodesic_terms([(train[vv], pair[0])], pair[1]) for vv, pair in zip(vs, pairs)]
+            return [make([(train[vv], pair[0]) for vv, pair in zip(vs, pairs)], torch.cat([pair[1] for pair in pairs]))]
+        return [make([(train[vv], pair[0])], pair[1]) for vv, pair in zip(vs, pairs)]
 
     class ManifoldRelevanceDetermination(Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
@@ -1261,6 +1292,32 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             one ops.geodesic_accel).  The training side of all views is built once per call."""
             out = [_geodesic.exp_map(t, x, v, num_latent_dims, dev_, num_steps, return_velocity)
                    for t in _geodesic_terms(views, total)]
+            return out[0] if total else out
+
+        @staticmethod
+        def geodesic_deviation(x, v, dx, dv, views=None, total=False):
+            """One pair (a, da) per view of `views` (default: all V, in order), as bayesian_gp_lvm.geodesic_deviation under the
+            view's latent_metric; total=True: one pair, under the summed metric.  The training side of all views is built once
+            per call."""
+            out = [_geodesic.geodesic_deviation(t, x, v, dx, dv, num_latent_dims, dev_) for t in _geodesic_terms(views, total, True)]
+            return out[0] if total else out
+
+        @staticmethod
+        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, views=None, total=False, return_velocity=False):
+            """One result (curve, dcurve[, velocity, dvelocity]) per view of `views`, as bayesian_gp_lvm.latent_exp_map_tangent
+            under the view's latent_metric; total=True: one result, under the summed metric (a stage is then one
+            ops.ard_rbf_point_christoffel_tangent call per view and one ops.geodesic_accel_tangent)."""
+            out = [_geodesic.exp_map_tangent(t, x, v, dx, dv, num_latent_dims, dev_, num_steps, return_velocity)
+                   for t in _geodesic_terms(views, total, True)]
+            return out[0] if total else out
+
+        @staticmethod
+        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, views=None, total=False, init=None):
+            """One result (v, distance, curve, residual) per view of `views`: the view's own logarithm map, as
+            bayesian_gp_lvm.latent_log_map under the view's latent_metric; total=True: one result, under the summed metric.
+            The training side of all views is built once per call."""
+            out = [_geodesic.log_map(t, x_from, x_to, num_latent_dims, dev_, num_steps, max_iterations, tol, init)
+                   for t in _geodesic_terms(views, total, True)]
             return out[0] if total else out
 
         @staticmethod

@@ -16,6 +16,11 @@ The initial-value side: a geodesic obeys G x'' = -Gamma(x, x'), Gamma the Christ
 with the velocity.  exp_map integrates (x', v') = (v, -G^-1 Gamma) over t in [0, 1] by the classical Runge-Kutta scheme on `accel`,
 a callable (x [N,Q], v [N,Q]) -> (a [N,Q], speed [N], info [N]) that a model builds ONCE per call
 (marginals.geodesic_terms on ops.ard_rbf_point_christoffel and ops.geodesic_accel): C curves are one batch, a stage is one call.
+
+Its tangent and its inverse: exp_map_tangent integrates the tangent-linear equation beside the curve (a discrete Jacobi field, the
+exact derivative of exp_map's discrete map) on `accel_tangent`, a callable (x, v, dx, dv [N,Q]) -> (a, da [N,Q], speed [N], info [N])
+(marginals.geodesic_tangent_terms on ops.ard_rbf_point_christoffel_tangent and ops.geodesic_accel_tangent), and log_map is Newton
+shooting on it: one batched tangent shot over C Q rows per iteration.
 """
 import numpy as np
 import torch
@@ -154,6 +159,12 @@ def prior_accel(v, weight):
     return torch.zeros_like(v), torch.sum(v * v * weight, dim=1), torch.zeros(v.shape[0], dtype=torch.int32, device=v.device)
 
 
+def prior_accel_tangent(v, weight):
+    """accel_tangent's four under a constant diagonal metric: prior_accel's triple with da = 0 in second place."""
+    a, speed, info = prior_accel(v, weight)
+    return a, torch.zeros_like(v), speed, info
+
+
 def geodesic_acceleration(accel, x, v, q, device):
     """a [N* x Q] (or [Q] for one point): x'' of the geodesics through x with the velocities v ([N* x Q] or [Q])."""
     single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
@@ -206,3 +217,154 @@ def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False):
     if single:
         curve, vel = curve[0], vel[0]
     return (curve, vel) if return_velocity else curve
+
+
+# ---- the tangent of the initial-value side: Jacobi fields, and the logarithm map by Newton shooting ------------------------------
+def geodesic_deviation(accel_tangent, x, v, dx, dv, q, device):
+    """(a, da) [N* x Q] (or [Q] for one point): geodesic_acceleration's a with its bits, and its derivative along the direction
+    (dx, dv) of the state (x, v), the right-hand side of the Jacobi equation.  accel_tangent: a callable
+    (x, v, dx, dv [N,Q]) -> (a, da [N,Q], speed [N], info [N]) that a model builds ONCE per call (marginals.geodesic_tangent_terms)."""
+    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
+    xs = ends_arg(x, q, device, 'x')
+    vs, dxs, dvs = (ends_arg(t, q, device, nm) for t, nm in ((v, 'v'), (dx, 'dx'), (dv, 'dv')))
+    assert xs.shape == vs.shape == dxs.shape == dvs.shape, 'x, v, dx and dv must have the same shape'
+    with torch.no_grad():
+        a, da = accel_tangent(xs, vs, dxs, dvs)[:2]
+    return (a[0], da[0]) if single else (a, da)
+
+
+def _rk4_tangent(accel_tangent, xs, vs, dxs, dvs, num_steps):
+    """(curve, vel, dcurve, dvel [C x S+1 x Q], bad [C] int32, speed [C]): exp_map's steps on (x, v), with its bits, and their exact
+    derivative on (dx, dv): every stage is differentiated by the chain rule, d k_x = dv_stage, d k_v = da.  bad counts the stages
+    whose metric failed to factor; speed is v^T G(x) v at the start.  Nothing is read on the host."""
+    c, q, h = xs.shape[0], xs.shape[1], 1.0 / num_steps
+    curve = torch.empty((c, num_steps + 1, q), dtype=xs.dtype, device=xs.device)
+    vel, dcurve, dvel = torch.empty_like(curve), torch.empty_like(curve), torch.empty_like(curve)
+    bad = torch.zeros(c, dtype=torch.int32, device=xs.device)
+    speed0 = None
+
+    def f(xx, vv, dxx, dvv):
+        nonlocal bad, speed0
+        a, da, speed, info = accel_tangent(xx, vv, dxx, dvv)
+        bad = bad + (info != 0).to(torch.int32)
+        if speed0 is None:
+            speed0 = speed
+        return a, da
+
+    curve[:, 0], vel[:, 0], dcurve[:, 0], dvel[:, 0] = xs, vs, dxs, dvs
+    for s in range(num_steps):
+        k1x, d1x = vs, dvs
+        k1v, d1v = f(xs, vs, dxs, dvs)
+        k2x, d2x = vs + (0.5 * h) * k1v, dvs + (0.5 * h) * d1v
+        k2v, d2v = f(xs + (0.5 * h) * k1x, k2x, dxs + (0.5 * h) * d1x, d2x)
+        k3x, d3x = vs + (0.5 * h) * k2v, dvs + (0.5 * h) * d2v
+        k3v, d3v = f(xs + (0.5 * h) * k2x, k3x, dxs + (0.5 * h) * d2x, d3x)
+        k4x, d4x = vs + h * k3v, dvs + h * d3v
+        k4v, d4v = f(xs + h * k3x, k4x, dxs + h * d3x, d4x)
+        xs = xs + (h / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x)
+        vs = vs + (h / 6.0) * (k1v + 2.0 * k2v + 2.0 * k3v + k4v)
+        dxs = dxs + (h / 6.0) * (d1x + 2.0 * d2x + 2.0 * d3x + d4x)
+        dvs = dvs + (h / 6.0) * (d1v + 2.0 * d2v + 2.0 * d3v + d4v)
+        curve[:, s + 1], vel[:, s + 1], dcurve[:, s + 1], dvel[:, s + 1] = xs, vs, dxs, dvs
+    return curve, vel, dcurve, dvel, bad, speed0
+
+
+def exp_map_tangent(accel_tangent, x, v, dx, dv, q, device, num_steps=64, return_velocity=False):
+    """(curve, dcurve) [C x S+1 x Q] (single curves [S+1 x Q] for x, v, dx, dv [Q]): exp_map's curve, with its bits, and the
+    tangent-linear classical RK4 solution started at (dx, dv): the EXACT derivative of exp_map's discrete map along that direction
+    of (x, v), a discrete Jacobi field.  With return_velocity (curve, dcurve, velocity, dvelocity).  Four calls of accel_tangent
+    per step plus element-wise work; the stages' info is accumulated on the device and read ONCE at the end:
+    FloatingPointError if the metric failed to factor at any stage of any curve."""
+    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
+    xs = ends_arg(x, q, device, 'x')
+    vs, dxs, dvs = (ends_arg(t, q, device, nm) for t, nm in ((v, 'v'), (dx, 'dx'), (dv, 'dv')))
+    assert xs.shape == vs.shape == dxs.shape == dvs.shape, 'x, v, dx and dv must have the same shape'
+    num_steps = int(num_steps)
+    assert num_steps >= 1, 'num_steps >= 1'
+    with torch.no_grad():
+        curve, vel, dcurve, dvel, bad, _ = _rk4_tangent(accel_tangent, xs, vs, dxs, dvs, num_steps)
+        failed = int(torch.count_nonzero(bad))
+        if failed:
+            raise FloatingPointError('latent_exp_map_tangent: the metric failed to factor (not positive definite in fp64) along '
+                                     '%d of %d curves' % (failed, xs.shape[0]))
+    out = (curve, dcurve, vel, dvel) if return_velocity else (curve, dcurve)
+    return tuple(t[0] for t in out) if single else out
+
+
+def _small_solve(a, b):
+    """a^-1 b of the matrices a [C x Q x Q] and vectors b [C x Q] by Gauss-Jordan elimination with partial pivoting in
+    element-wise device work: nothing is read on the host, and a system's bits do not depend on the batch it is in."""
+    c, q = b.shape
+    w = torch.cat([a, b[:, :, None]], dim=2).clone()
+    rows = torch.arange(c, device=b.device)
+    for j in range(q):
+        piv = torch.argmax(torch.abs(w[:, j:, j]), dim=1) + j
+        top, other = w[rows, piv], w[:, j].clone()
+        w[rows, piv] = other
+        w[:, j] = top / top[:, j:j + 1]
+        fac = w[:, :, j:j + 1].clone()
+        fac[:, j] = 0.0
+        w = w - fac * w[:, j:j + 1, :]
+    return w[:, :, q].contiguous()
+
+
+def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations=20, tol=1e-10, init=None):
+    """(v [C x Q], distance [C], curve [C x S+1 x Q], residual [C]) (unbatched shapes for one pair): the logarithm map of x_to at
+    x_from, the initial velocity whose exp_map at num_steps steps ends in x_to, by Newton shooting on the discrete map; distance =
+    sqrt(v^T G(x_from) v), curve = exp_map(x_from, v), residual = |curve end - x_to|.
+
+    From v = init [C x Q], or x_to - x_from.  An iteration is ONE batched shot of _rk4_tangent over C Q rows: row (c, r) carries
+    dx = 0, dv = e_r, so that the rows' end tangents are the columns of J_c = d end / d v, and row (c, 0) supplies the end itself.
+    With r_c = end_c - x_to_c the shot JUDGES the velocity it was fired with: the first one is taken as it is; a later one is
+    accepted if its residual is smaller than the last accepted one's and every stage factored (lambda_c <- min(1, 2 lambda_c)),
+    otherwise rejected (v_c goes back to the accepted velocity, lambda_c <- lambda_c / 2).  Then v_c - lambda_c J_c^-1 r_c of the
+    accepted iterate is proposed.  A curve that has met the stop test is frozen while the others go on, so a pair's result does
+    not depend on the batch it is in.  The accepted iterate is the best one met, so the result is never worse than the start.  At most
+    max_iterations proposals are made and judged (1 + max_iterations shots); the loop ends early once every accepted residual is
+    <= tol max(1, |x_to|).  ONE host read per iteration, of that test.  A curve whose residual stays above it is reported through
+    `residual`, not raised; FloatingPointError only if the very first shot fails to factor.  The base features are recomputed for
+    each of the Q directions."""
+    single = (x_from.dim() if torch.is_tensor(x_from) else np.asarray(x_from).ndim) == 1
+    a, b = ends_arg(x_from, q, device, 'x_from'), ends_arg(x_to, q, device, 'x_to')
+    assert a.shape == b.shape, 'x_from and x_to must have the same shape'
+    num_steps, max_iterations = int(num_steps), int(max_iterations)
+    assert num_steps >= 1 and max_iterations >= 0, 'num_steps >= 1 and max_iterations >= 0'
+    c = a.shape[0]
+    with torch.no_grad():
+        v = (b - a) if init is None else ends_arg(init, q, device, 'init').clone()
+        assert v.shape == a.shape, 'init must have the shape of x_from'
+        bound = tol * torch.clamp(torch.linalg.vector_norm(b, dim=1), min=1.0)
+        rep = lambda t: t[:, None, :].expand(c, q, q).reshape(c * q, q).contiguous()
+        xs, zero = rep(a), torch.zeros((c * q, q), dtype=a.dtype, device=a.device)
+        unit = torch.eye(q, dtype=a.dtype, device=a.device).repeat(c, 1)
+        lam = torch.ones(c, dtype=a.dtype, device=a.device)
+        best = None                                           # (v, residual, step, curve, speed) of the accepted iterate
+        for it in range(max_iterations + 1):
+            curve, _, dcurve, _, bad, speed = _rk4_tangent(accel_tangent, xs, rep(v), zero, unit, num_steps)
+            base = curve.reshape(c, q, num_steps + 1, q)[:, 0]
+            res = base[:, -1] - b
+            norm = torch.linalg.vector_norm(res, dim=1)
+            good = torch.sum(bad.reshape(c, q), dim=1) == 0
+            jac = dcurve.reshape(c, q, num_steps + 1, q)[:, :, -1].transpose(1, 2)           # [C, end component, direction]
+            step = _small_solve(jac, res)
+            if best is None:
+                ok = good
+                best = [v, norm, step, base, speed.reshape(c, q)[:, 0]]
+            else:
+                ok = good & (norm < best[1]) & ~conv
+                new = (v, norm, step, base, speed.reshape(c, q)[:, 0])
+                best = [torch.where(ok.reshape((c,) + (1,) * (o.dim() - 1)), n, o) for n, o in zip(new, best)]
+                lam = torch.where(ok, torch.clamp(2.0 * lam, max=1.0), 0.5 * lam)
+            conv = best[1] <= bound
+            done, failed = torch.stack([torch.all(conv), torch.any(~ok)]).tolist()
+            if it == 0 and failed:
+                raise FloatingPointError('latent_log_map: the metric failed to factor (not positive definite in fp64) along the '
+                                         'first shot of %d of %d curves' % (int(torch.count_nonzero(~ok)), c))
+            if done:
+                break
+            v = torch.where(conv[:, None], best[0], best[0] - lam[:, None] * best[2])
+        v, norm, _, curve, speed = best
+        dist = torch.sqrt(torch.clamp(speed, min=0.0))
+    if single:
+        return v[0], dist[0], curve[0], norm[0]
+    return v, dist, curve.contiguous(), norm

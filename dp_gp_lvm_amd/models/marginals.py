@@ -105,6 +105,12 @@ class _Marginals:
         ops.ard_rbf_point_christoffel and ONE of ops.geodesic_accel per block of points (geodesic_terms below)."""
         return geodesic_terms([(self, p)], prior)(x, v)
 
+    def geodesic_tangent_terms(self, x, v, dx, dv, p, prior):
+        """(a, da [N*, Q], speed [N*], info [N*] int32): geodesic_terms' triple, with its bits, and the derivative da of the
+        acceleration along the direction (dx, dv) [N*, Q] of the state (x, v).  ONE call of ops.ard_rbf_point_christoffel_tangent
+        and ONE of ops.geodesic_accel_tangent per block of points (geodesic_tangent_terms below)."""
+        return geodesic_tangent_terms([(self, p)], prior)(x, v, dx, dv)
+
     def _patterns(self, cols):
         """(c [K, G', M, M], slot [K, J] long): the patterns to evaluate and, per kernel and column, its place among them.  With
         gidx_host (and host columns: columns_arg's .host) G' counts only the patterns that `cols` touch, in ascending order, plus
@@ -210,6 +216,29 @@ def geodesic_terms(parts, prior):
             slabs = [ops.ard_rbf_point_christoffel(marg.z, xb, vb, marg.gamma, marg.alpha, p) for marg, p in parts]
             g, gam = slabs[0] if len(slabs) == 1 else (torch.cat([s[0] for s in slabs]), torch.cat([s[1] for s in slabs]))
             blocks.append(ops.geodesic_accel(g, gam, w, vb))
+        return tuple(bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
+    return terms
+
+
+def geodesic_tangent_terms(parts, prior):
+    """The callable (x, v, dx, dv [N, Q]) -> (a [N, Q], da [N, Q], speed [N], info [N]) of models/geodesic.py: geodesic_terms'
+    triple with its bits, and da, the derivative of the acceleration along the direction (dx, dv) of the state (x, v).  One call
+    of ops.ard_rbf_point_christoffel_tangent per pair gives the slabs (g_k, Gamma_k, dg_k, dGamma_k), one call of
+    ops.geodesic_accel_tangent sums them and solves twice with one factor.  Blocks and the concatenation of the pairs' slabs as
+    geodesic_terms (twice the entries per point, so half its points per block); a point's bits do not depend on its block."""
+    q = parts[0][0].z.shape[2]
+    k = sum(marg.z.shape[0] for marg, _ in parts)
+    w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0).contiguous()
+    step = max(1, (1 << 25) // (2 * k * (q * q + q)))
+
+    def terms(x, v, dx, dv):
+        x, v, dx, dv = x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()
+        blocks = []
+        for i in range(0, x.shape[0], step):
+            xb, vb, dxb, dvb = x[i:i + step], v[i:i + step], dx[i:i + step], dv[i:i + step]
+            slabs = [ops.ard_rbf_point_christoffel_tangent(marg.z, xb, vb, dxb, dvb, marg.gamma, marg.alpha, p) for marg, p in parts]
+            four = slabs[0] if len(slabs) == 1 else [torch.cat([s[j] for s in slabs]) for j in range(4)]
+            blocks.append(ops.geodesic_accel_tangent(*four, w, vb))
         return tuple(bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
     return terms
 

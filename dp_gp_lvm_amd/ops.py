@@ -490,9 +490,11 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
 def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None):
     """The checks of the five point operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
     (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M], r [K,M,J] or c [K,G,M,M], `what` its wording);
-    dirs: the directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), checked in their place
-    after x; max_q: an operator's own limit on Q (ValueError, after the shapes)."""
-    args = (('z', z), ('x', x)) + (() if dirs is None else (('v', dirs[0]),)) + (('gamma', gamma), ('alpha', alpha), (name, a))
+    dirs: the directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), or (v, dx, dv) of
+    ard_rbf_point_christoffel_tangent, checked in their place after x; max_q: an operator's own limit on Q (ValueError, after the
+    shapes)."""
+    dirs = () if dirs is None else tuple(zip(('v', 'dx', 'dv'), dirs))
+    args = (('z', z), ('x', x)) + dirs + (('gamma', gamma), ('alpha', alpha), (name, a))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % nm)
@@ -501,8 +503,9 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None)
     k, m, q = z.shape
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != q:
         raise ValueError('x must be [N x Q] with Q = %d, got %s' % (q, tuple(x.shape)))
-    if dirs is not None and tuple(dirs[0].shape) != tuple(x.shape):
-        raise ValueError('v must be [N x Q] as x, got %s' % (tuple(dirs[0].shape),))
+    for nm, v in dirs:
+        if tuple(v.shape) != tuple(x.shape):
+            raise ValueError('%s must be [N x Q] as x, got %s' % (nm, tuple(v.shape)))
     if tuple(gamma.shape) != (k, q):
         raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
     if alpha.numel() != k:
@@ -591,6 +594,67 @@ def ard_rbf_point_christoffel(z, x, v, gamma, alpha, p):
     return g, gam
 
 
+def ard_rbf_point_christoffel_tangent(z, x, v, dx, dv, gamma, alpha, p):
+    """ard_rbf_point_christoffel's pair and its derivative along a direction (dx, dv) [N,Q] of the state (x, v)
+    (dpgp_ard_rbf_point_christoffel_tangent_f64): with u_q = gamma_kq (x_nq - z_kmq), k, b, d as there, a = sum_q u_q v_q and
+        e = sum_q u_q dx_q,   f = sum_q u_q dv_q,   c1 = sum_q gamma_kq dx_q v_q,   c2 = sum_q gamma_kq v_q dv_q
+        db_q = k (e u_q - gamma_kq dx_q),           dd = k (-e (a^2 - sum_q gamma_kq v_q^2) + 2 a (c1 + f) - 2 c2)
+    returns (g, gam, dg, dgam),
+        g [K,N,Q,Q], gam [K,N,Q]     the bits of ard_rbf_point_christoffel(z, x, v, gamma, alpha, p)
+        dg [K,N,Q,Q] = db^T p b + b^T p db,        dgam [K,N,Q] = db^T p d + b^T p dd
+    p [K,M,M] is used as given (not symmetrised); dg is symmetric for a symmetric p up to rounding.  One launch, all four results
+    from one product over the feature block [b | d | db | dd]; nothing of size N M in memory; fixed summation order, the same
+    bits on every run; exact zeros for a zero direction.  Q <= 31 (ValueError).  float64 tensors (TypeError) of these shapes
+    (ValueError) on one GPU (RuntimeError)."""
+    z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]', dirs=(v, dx, dv), max_q=31)
+    v, dx, dv = v.contiguous(), dx.contiguous(), dv.contiguous()
+    g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
+    gam = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
+    dg, dgam = torch.empty_like(g), torch.empty_like(gam)
+    _point_call('christoffel_tangent', (k, n, m, q), (z, x, v, dx, dv, gamma, alpha, p), (g, gam, dg, dgam))
+    return g, gam, dg, dgam
+
+
+def _accel_args(args):
+    """The checks of geodesic_accel / geodesic_accel_tangent on (('g', g), ('gam', gam)[, ('dg', dg), ('dgam', dgam)],
+    ('prior', prior), ('v', v)): contiguous tensors in that order and (K, N, Q)."""
+    for nm, t in args:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise TypeError('%s must be a float64 torch.Tensor' % nm)
+    g = args[0][1]
+    if g.dim() != 4 or min(g.shape) < 1 or g.shape[2] != g.shape[3] or g.shape[3] > 64:
+        raise ValueError('g must be [K x N x Q x Q] with Q <= 64, got %s' % (tuple(g.shape),))
+    k, n, q = g.shape[0], g.shape[1], g.shape[2]
+    want = dict(gam=((k, n, q), '[K x N x Q] as g'), dg=((k, n, q, q), '[K x N x Q x Q] as g'), dgam=((k, n, q), '[K x N x Q] as g'),
+                prior=((q,), '[Q]'), v=((n, q), '[N x Q]'))
+    for nm, t in args[1:]:
+        if tuple(t.shape) != want[nm][0]:
+            raise ValueError('%s must be %s, got %s' % (nm, want[nm][1], tuple(t.shape)))
+    for nm, t in args:
+        if not t.is_cuda or t.device != g.device:
+            raise RuntimeError('%s must live on the GPU of g: dp_gp_lvm_amd runs its operators in HIP only' % nm)
+    return [t.contiguous() for _, t in args], k, n, q
+
+
+def geodesic_accel_tangent(g, gam, dg, dgam, prior, v):
+    """geodesic_accel and its derivative from ard_rbf_point_christoffel_tangent's four results (dpgp_geodesic_accel_tangent_f64):
+    returns (a, da, speed, info); a, speed and info carry the bits of geodesic_accel(g, gam, prior, v), and with the same factor
+        da [N,Q] = -G_n^-1 (sum_k dgam[k,n] + (sum_k dg[k,n]) a_n)            (k ascending; the constant prior drops out)
+    the derivative of the acceleration along the direction that dg, dgam were taken in.  info[n] != 0: a[n, :] and da[n, :] are
+    NaN and the other points are unaffected.  dg [K,N,Q,Q], dgam [K,N,Q]; everything else as geodesic_accel."""
+    (g, gam, dg, dgam, prior, v), k, n, q = _accel_args((('g', g), ('gam', gam), ('dg', dg), ('dgam', dgam), ('prior', prior),
+                                                          ('v', v)))
+    a = torch.empty((n, q), dtype=torch.float64, device=g.device)
+    da = torch.empty_like(a)
+    speed = torch.empty((n,), dtype=torch.float64, device=g.device)
+    info = torch.empty((n,), dtype=torch.int32, device=g.device)
+    _lib.check(_lib.lib().dpgp_geodesic_accel_tangent_f64(k, n, q, g.data_ptr(), gam.data_ptr(), dg.data_ptr(), dgam.data_ptr(),
+                                                          prior.data_ptr(), v.data_ptr(), a.data_ptr(), da.data_ptr(),
+                                                          speed.data_ptr(), info.data_ptr(), _stream()),
+               'dpgp_geodesic_accel_tangent_f64')
+    return a, da, speed, info
+
+
 def geodesic_accel(g, gam, prior, v):
     """The acceleration of the geodesic equation from ard_rbf_point_christoffel's pair (dpgp_geodesic_accel_f64): per point, with
     G_n = sum_k g[k,n] + diag(prior) (k ascending), returns (a, speed, info),
@@ -599,23 +663,7 @@ def geodesic_accel(g, gam, prior, v):
     of the first pivot that is not positive: a[n, :] is then NaN and the other points are unaffected.  g [K,N,Q,Q], gam [K,N,Q],
     prior [Q], v [N,Q] with Q <= 64.  No atomics, nothing read on the host, the same bits on every run.  float64 tensors
     (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
-    args = (('g', g), ('gam', gam), ('prior', prior), ('v', v))
-    for nm, t in args:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise TypeError('%s must be a float64 torch.Tensor' % nm)
-    if g.dim() != 4 or min(g.shape) < 1 or g.shape[2] != g.shape[3] or g.shape[3] > 64:
-        raise ValueError('g must be [K x N x Q x Q] with Q <= 64, got %s' % (tuple(g.shape),))
-    k, n, q = g.shape[0], g.shape[1], g.shape[2]
-    if tuple(gam.shape) != (k, n, q):
-        raise ValueError('gam must be [K x N x Q] as g, got %s' % (tuple(gam.shape),))
-    if tuple(prior.shape) != (q,):
-        raise ValueError('prior must be [Q], got %s' % (tuple(prior.shape),))
-    if tuple(v.shape) != (n, q):
-        raise ValueError('v must be [N x Q], got %s' % (tuple(v.shape),))
-    for nm, t in args:
-        if not t.is_cuda or t.device != g.device:
-            raise RuntimeError('%s must live on the GPU of g: dp_gp_lvm_amd runs its operators in HIP only' % nm)
-    g, gam, prior, v = g.contiguous(), gam.contiguous(), prior.contiguous(), v.contiguous()
+    (g, gam, prior, v), k, n, q = _accel_args((('g', g), ('gam', gam), ('prior', prior), ('v', v)))
     a = torch.empty((n, q), dtype=torch.float64, device=g.device)
     speed = torch.empty((n,), dtype=torch.float64, device=g.device)
     info = torch.empty((n,), dtype=torch.int32, device=g.device)

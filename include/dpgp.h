@@ -354,6 +354,38 @@ int dpgp_ard_rbf_point_christoffel_f64(int K, int N, int M, int Q, const double 
 int dpgp_geodesic_accel_f64(int K, int N, int Q, const double *g, const double *gam, const double *prior, const double *v,
                             double *a, double *speed, int *info, void *stream);
 
+/* ---- The tangent of the geodesic equation (csrc/ard_rbf_point_metric.hip, csrc/geodesic_accel.hip): what one stage of the
+ *      tangent-linear (Jacobi field) integrator needs, the derivative of the pair (g, gam) above and of the acceleration along a
+ *      direction (dx, dv)[N][Q] of the state (x, v).  With u_q = gamma_kq (x_nq - z_kmq), k = k_km(x_n), b_q = -k u_q,
+ *      a = sum_q u_q v_q, s = sum_q gamma_kq v_nq^2, d = k (a^2 - s) as above and
+ *        e = sum_q u_q dx_q,   f = sum_q u_q dv_q,   c1 = sum_q gamma_kq dx_q v_q,   c2 = sum_q gamma_kq v_q dv_q
+ *        db_q = k (e u_q - gamma_kq dx_q),           dd = k (-e (a^2 - s) + 2 a (c1 + f) - 2 c2)
+ *      the first operator gives g and gam, WITH THE BITS of dpgp_ard_rbf_point_christoffel_f64, and
+ *        dg[K][N][Q][Q] = dB^T p B + B^T p dB,       dgam[K][N][Q] = dB^T p d + B^T p dd          (p used as given)
+ *      One launch: the same kernel with the feature block F = [B | d | dB | dd], W = 2 Q + 2 columns, ceil(W / 16) column tiles;
+ *      all four results are entries of the one product F^T p F (dg: rows 0 .. Q-1 x columns Q+1 .. 2Q plus rows Q+1 .. 2Q x
+ *      columns 0 .. Q-1; dgam: rows Q+1 .. 2Q of column Q plus rows 0 .. Q-1 of column 2Q+1).  The rules of the operator above
+ *      hold: nothing of size N M in memory, no atomics, sums ordered by (M, Q) alone, a point's bits independent of N, its place
+ *      and K, exact zeros far from every z and for a zero direction.  1 <= K, N, M;  1 <= Q <= 31.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, N -2, M -3, Q -4, z -5, x -6, v -7, dx -8, dv -9,
+ *      gamma -10, alpha -11, p -12, g -13, gam -14, dg -15, dgam -16, ws -17, ws_bytes too small -18.
+ *   ws: as above, a token 256 bytes for a shape in range, 0 for one out of range.
+ *      The finishing operator takes the four results, prior[Q] and v[N][Q] and gives a, speed and info WITH THE BITS of
+ *      dpgp_geodesic_accel_f64 on (g, gam), and with the same factor of G (the constant prior has no share in the tangent of G)
+ *        da[N][Q] = -G^-1 ( sum_k dgam[k][n] + (sum_k dg[k][n]) a )              (k ascending)
+ *      A pivot that is not positive ends that point alone: info = its 1-based index, a[n][:] = da[n][:] = NaN.
+ *      1 <= K, N;  1 <= Q <= DPGP_QX_PSI_MAX_Q.
+ *   Bad arguments, in this order:  K -1, N -2, Q -3, g -4, gam -5, dg -6, dgam -7, prior -8, v -9, a -10, da -11, speed -12,
+ *      info -13. */
+size_t dpgp_ard_rbf_point_christoffel_tangent_workspace_bytes(int K, int N, int M, int Q);
+int dpgp_ard_rbf_point_christoffel_tangent_f64(int K, int N, int M, int Q, const double *z, const double *x, const double *v,
+                                               const double *dx, const double *dv, const double *gamma, const double *alpha,
+                                               const double *p, double *g, double *gam, double *dg, double *dgam, void *ws,
+                                               size_t ws_bytes, void *stream);
+int dpgp_geodesic_accel_tangent_f64(int K, int N, int Q, const double *g, const double *gam, const double *dg,
+                                    const double *dgam, const double *prior, const double *v, double *a, double *da,
+                                    double *speed, int *info, void *stream);
+
 /* ---- Joint posterior covariance at deterministic latent points (csrc/ard_rbf_point_cov.hip): the off-diagonal that the per-point
  *      operators above leave out.  Kernels z[K][M][Q], gamma[K][Q], alpha[K] and points x[N][Q] as for the metric operator;
  *      c[K][G][M][M]: G matrices per kernel (one per training row pattern), any matrices.  With k_km as above,
