@@ -33,7 +33,8 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
-from . import collapsed, geodesic as _geodesic, marginals as _marginals, predictor as _predictor
+from . import collapsed, marginals as _marginals, predictor as _predictor
+from .latent_geometry import LatentGeometry
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
 from .frozen_bound import _TestBound
@@ -745,39 +746,20 @@ def dp_gp_lvm(y_train,
         assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
         return cols
 
-    def _curve_terms(columns, name):
-        """The terms of models/geodesic.py under latent_metric(., columns): _latent_geometry's kernels with their (P, prior) and
-        the prior of the columns never observed, formed once."""
+    def _require_unsharded(name):
         assert not split, '%s is not built for a model sharded over a process group' % name
-        cols = _geometry_columns(columns)
-        evaluate()
-        with torch.no_grad():
-            marg, _, prior_unseen = _latent_geometry(cols)
-            if marg is None:
-                weight = torch.diagonal(prior_unseen).contiguous()
-                return lambda x, v: _geodesic.prior_terms(v, weight)
-            p, prior = marg._metric_operands(None, None)
-            prior = torch.cat([prior, prior_unseen[None]])
-        return lambda x, v: marg.curve_terms(x, v, p, prior)
 
-    def _geodesic_terms(columns, name, tangent=False):
-        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms;
-        tangent: with its derivative along a direction (marginals.geodesic_tangent_terms)."""
-        assert not split, '%s is not built for a model sharded over a process group' % name
+    def _metric_under(columns, name):
+        """latent_geometry's hook: the marginals.Metric under latent_metric(., columns), _latent_geometry's kernels with their
+        (P, prior) and the prior of the columns never observed, formed once; that prior alone when no chosen column was
+        observed in training."""
+        _require_unsharded(name)
         cols = _geometry_columns(columns)
         evaluate()
         with torch.no_grad():
             marg, _, prior_unseen = _latent_geometry(cols)
-            if marg is None:
-                weight = torch.diagonal(prior_unseen).contiguous()
-                if tangent:
-                    return lambda x, v, dx, dv: _geodesic.prior_accel_tangent(v, weight)
-                return lambda x, v: _geodesic.prior_accel(v, weight)
-            p, prior = marg._metric_operands(None, None)
-            prior = torch.cat([prior, prior_unseen[None]])
-        if tangent:
-            return lambda x, v, dx, dv: marg.geodesic_tangent_terms(x, v, dx, dv, p, prior)
-        return lambda x, v: marg.geodesic_terms(x, v, p, prior)
+            parts = [] if marg is None else [(marg,) + marg._metric_operands(None, None)]
+            return _marginals.Metric(parts, prior_unseen[None])
 
     def _assembled_marginals(cols, xt, st_):
         """_marginals_at of the GLOBAL output dims `cols` (any order) on a sharded model: this rank computes the columns it owns
@@ -803,8 +785,14 @@ def dp_gp_lvm(y_train,
         assert form in ('slots', 'shared'), "form must be 'slots' or 'shared'"
         assert form == 'slots' or observed is not None, "form='shared' is the masked test bound: it needs observed="
 
-    class DP_GP_LVM(Trainable):
-        """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508)."""
+    class DP_GP_LVM(LatentGeometry, Trainable):
+        """Accessors as in the reference (dp_gp_lvm.py:161-231,502-508).  The latent-geometry methods are
+        models/latent_geometry.LatentGeometry's, every column under its own mixed kernel: an operator call runs over
+        K = len(columns) kernels and is summed over them in blocks of points; with the columns of one discovered group they show
+        that group's own energy, the paths it considers short and where its manifold takes a motion.  Not built for a model
+        sharded over a process group: AssertionError."""
+        _latent_dims, _device = num_latent_dims, device
+        _metric_of, _require_built = staticmethod(_metric_under), staticmethod(_require_unsharded)
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
                    beta_atoms=beta_atoms_raw, **{'dp_' + k: v for k, v in dp_model.raw.items()})
         shard = (d_lo, d_hi)
@@ -1046,8 +1034,7 @@ def dp_gp_lvm(y_train,
             of the trace term against predict_missing_data's array).  fp64, torch.no_grad.  On a model sharded over a process
             group (any precision, with or without observed=): `columns` are global, each rank computes those it owns and one sum
             all-reduce assembles the pair in the caller's column order, the same tensors on every rank."""
-            cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
-            assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+            cols = _geometry_columns(columns)
             val = lambda a: _t(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
             evaluate()
             with torch.no_grad():
@@ -1059,9 +1046,8 @@ def dp_gp_lvm(y_train,
             predictive_marginals, differentiably in q(X*); p.vjp is its vector-Jacobian product (ops.psi_latent_adjoint: the
             columns' kernels share Z and q(X*)).  The training side is built once, here, at the model's current parameters: stale
             after further training.  Not built for a model sharded over a process group: AssertionError."""
-            assert not split, 'frozen_predictor is not built for a model sharded over a process group'
-            cols = np.arange(num_dimensions) if columns is None else np.asarray(columns, dtype=np.int64).reshape(-1)
-            assert cols.size >= 1 and cols.min() >= 0 and cols.max() < num_dimensions, 'columns must be output dims in [0, D)'
+            _require_unsharded('frozen_predictor')
+            cols = _geometry_columns(columns)
             evaluate()
             with torch.no_grad():
                 return _frozen_predictor(cols)
@@ -1074,7 +1060,7 @@ def dp_gp_lvm(y_train,
             ops.ard_rbf_point_jacobian with every column its own kernel; the features [D, N*, M, Q] are never formed.  A column
             never observed in training has a zero row.  The training side is built once per call.  fp64, torch.no_grad.  Not
             built for a model sharded over a process group: AssertionError."""
-            assert not split, 'predictive_jacobian is not built for a model sharded over a process group'
+            _require_unsharded('predictive_jacobian')
             cols = _geometry_columns(columns)
             xp = _marginals.points_arg(x, num_latent_dims, device)
             evaluate()
@@ -1093,7 +1079,7 @@ def dp_gp_lvm(y_train,
             K = len(columns) kernels, summed over them in blocks of points.  With the columns of one discovered group it shows which region and which
             latent directions that group uses.  A column never observed in training contributes alpha_d diag(gamma_d).  fp64.
             Not built for a model sharded over a process group: AssertionError."""
-            assert not split, 'latent_metric is not built for a model sharded over a process group'
+            _require_unsharded('latent_metric')
             cols = _geometry_columns(columns)
             xp = _marginals.points_arg(x, num_latent_dims, device)
             evaluate()
@@ -1101,14 +1087,6 @@ def dp_gp_lvm(y_train,
                 marg, _, prior_unseen = _latent_geometry(cols)
                 g = prior_unseen[None].expand(xp.shape[0], -1, -1)
                 return g.clone() if marg is None else marg.metric_total(xp) + g
-
-        @staticmethod
-        def magnification(x, columns=None):
-            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), as exp(1/2 logdet) from a Cholesky
-            factorisation of G.  Not built for a model sharded over a process group: AssertionError."""
-            assert not split, 'magnification is not built for a model sharded over a process group'
-            with torch.no_grad():
-                return _marginals.magnification(DP_GP_LVM.latent_metric(x, columns))
 
         @staticmethod
         def predictive_covariance(x, columns=None, noise=False):
@@ -1122,7 +1100,7 @@ def dp_gp_lvm(y_train,
             J N*^2 doubles (here every column has its own matrix; in the other models columns of one (kernel, pattern) repeat the
             same one).  Works on a model trained on complete data and on one trained with observed=.  fp64, torch.no_grad.  Not
             built for a model sharded over a process group: AssertionError."""
-            assert not split, 'predictive_covariance is not built for a model sharded over a process group'
+            _require_unsharded('predictive_covariance')
             cols = _geometry_columns(columns)
             xp = _marginals.points_arg(x, num_latent_dims, device)
             evaluate()
@@ -1143,7 +1121,7 @@ def dp_gp_lvm(y_train,
             below rounding and the factorisation needs a shift well above eps N* lambda_max ~ 1e-12 alpha; 1e-6 alpha is far
             above that and far below any 1/beta the models train to.  fp64, torch.no_grad.  Not built for a model sharded over a
             process group: AssertionError."""
-            assert not split, 'sample_functions is not built for a model sharded over a process group'
+            _require_unsharded('sample_functions')
             cols = _geometry_columns(columns)
             xp = _marginals.points_arg(x, num_latent_dims, device)
             evaluate()
@@ -1153,88 +1131,6 @@ def dp_gp_lvm(y_train,
                 f, info = _column_marginals(cols).sample(xp, xi.permute(2, 0, 1)[:, :, :, None], None, noise, jitter)
                 _marginals.raise_if_not_factorised(info)
                 return f[:, :, :, 0].permute(1, 2, 0).contiguous()
-
-        @staticmethod
-        def curve_energy(curve, columns=None, return_gradient=False):
-            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
-            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
-            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy over K = len(columns)
-            kernels on the C S segments, summed over them in blocks of segments; with the columns of one discovered group, that
-            group's own energy.  The training side is built once per call.  fp64, torch.no_grad.  Not built for a model sharded
-            over a process group: AssertionError."""
-            return _geodesic.curve_energy(_curve_terms(columns, 'curve_energy'), curve, num_latent_dims, device, return_gradient)
-
-        @staticmethod
-        def curve_length(curve, columns=None):
-            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E).  Not built for a model
-            sharded over a process group: AssertionError."""
-            return _geodesic.curve_length(_curve_terms(columns, 'curve_length'), curve, num_latent_dims, device)
-
-        @staticmethod
-        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
-            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
-            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
-            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
-            iterate is returned, so its energy never exceeds the start's.  With the columns of one discovered group: the paths
-            that group considers short.  The training side is built once per call; an iteration is one call of
-            ops.ard_rbf_point_energy plus element-wise work.  fp64.  Not built for a model sharded over a process group:
-            AssertionError."""
-            return _geodesic.latent_geodesic(_curve_terms(columns, 'latent_geodesic'), x_from, x_to, num_latent_dims, device,
-                                             num_segments, num_iterations, learning_rate, init)
-
-        @staticmethod
-        def geodesic_acceleration(x, v, columns=None):
-            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
-            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), Gamma the Christoffel symbols of
-            the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
-            ops.ard_rbf_point_christoffel over K = len(columns) kernels and one of ops.geodesic_accel, which sums them, per
-            block of points; the training side is built once per call.  fp64, torch.no_grad.  Not built for a model sharded
-            over a process group: AssertionError."""
-            return _geodesic.geodesic_acceleration(_geodesic_terms(columns, 'geodesic_acceleration'), x, v, num_latent_dims,
-                                                   device)
-
-        @staticmethod
-        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
-            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
-            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
-            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
-            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
-            velocities, in the same shape.  With the columns of one discovered group: where that group's manifold takes a
-            motion.  A stage is one call of ops.ard_rbf_point_christoffel and one of ops.geodesic_accel plus element-wise work;
-            the training side is built once per call; one host read at the end: FloatingPointError if the metric failed to factor
-            at any stage.  fp64, torch.no_grad.  Not built for a model sharded over a process group: AssertionError."""
-            return _geodesic.exp_map(_geodesic_terms(columns, 'latent_exp_map'), x, v, num_latent_dims, device, num_steps,
-                                     return_velocity)
-
-        @staticmethod
-        def geodesic_deviation(x, v, dx, dv, columns=None):
-            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
-            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
-            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
-            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad.
-            Not built for a model sharded over a process group: AssertionError."""
-            return _geodesic.geodesic_deviation(_geodesic_terms(columns, 'geodesic_deviation', True), x, v, dx, dv, num_latent_dims, device)
-
-        @staticmethod
-        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
-            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
-            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
-            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
-            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
-            any stage.  Q <= 31.  fp64, torch.no_grad.
-            Not built for a model sharded over a process group: AssertionError."""
-            return _geodesic.exp_map_tangent(_geodesic_terms(columns, 'latent_exp_map_tangent', True), x, v, dx, dv, num_latent_dims, device, num_steps, return_velocity)
-
-        @staticmethod
-        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
-            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
-            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
-            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
-            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
-            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
-            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad.
-            Not built for a model sharded over a process group: AssertionError."""
-            return _geodesic.log_map(_geodesic_terms(columns, 'latent_log_map', True), x_from, x_to, num_latent_dims, device, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,
@@ -1867,27 +1763,19 @@ def dp_gp_lvm_t(y_train,
     def _columns_arg(columns):
         return _marginals.columns_arg(columns, num_dimensions, device)
 
-    def _curve_terms(columns):
-        """The terms of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+    def _metric_under(columns, name):
+        """latent_geometry's hook: the marginals.Metric under latent_metric(., columns), the training side and the atoms'
+        (P, prior), phi as weights, formed once."""
         cols = _columns_arg(columns)
         with torch.no_grad():
-            mom = _moments()
-            p, prior = mom.curve_operands(cols)
-        return lambda x, v: mom.curve_terms(x, v, p, prior)
+            return _marginals.Metric([_moments().metric_part(cols)])
 
-    def _geodesic_terms(columns, tangent=False):
-        """The acceleration of models/geodesic.py under latent_metric(., columns), from the same operands as _curve_terms;
-        tangent: with its derivative along a direction (marginals.geodesic_tangent_terms)."""
-        cols = _columns_arg(columns)
-        with torch.no_grad():
-            mom = _moments()
-            p, prior = mom.curve_operands(cols)
-        if tangent:
-            return lambda x, v, dx, dv: mom.geodesic_tangent_terms(x, v, dx, dv, p, prior)
-        return lambda x, v: mom.geodesic_terms(x, v, p, prior)
-
-    class DP_GP_LVM_T(Trainable):
-        """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here."""
+    class DP_GP_LVM_T(LatentGeometry, Trainable):
+        """Accessors as in the reference (dp_gp_lvm.py:679-740); the kernel has batch size T here.  The latent-geometry methods
+        are models/latent_geometry.LatentGeometry's: an operator call runs on the T atoms, the weights phi included; with the
+        columns of one discovered group they show that group's own energy, the paths it considers short and where its manifold
+        takes a motion."""
+        _latent_dims, _device, _metric_of = num_latent_dims, device, staticmethod(_metric_under)
         raw = dict(x_mean=x_mean, x_var=x_var_raw, x_u=x_u, gamma_atoms=gamma_atoms_raw, alpha_atoms=sig_var_atoms_raw,
                    beta_atoms=beta_atoms_raw, **{'dp_' + k: v for k, v in dp_model.raw.items()})
 
@@ -2041,13 +1929,6 @@ def dp_gp_lvm_t(y_train,
                 return _moments().metric(_marginals.points_arg(x, num_latent_dims, device), cols)
 
         @staticmethod
-        def magnification(x, columns=None):
-            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), as exp(1/2 logdet) from a Cholesky
-            factorisation of G."""
-            with torch.no_grad():
-                return _marginals.magnification(DP_GP_LVM_T.latent_metric(x, columns))
-
-        @staticmethod
         def predictive_covariance(x, columns=None, noise=False):
             """[len(columns) x N* x N*]: the covariance of the output dims `columns` (default: all D) at the DETERMINISTIC latent
             points x [N* x Q] (numpy or torch) under the mixture over the atoms,
@@ -2096,79 +1977,6 @@ def dp_gp_lvm_t(y_train,
                 f, info = mom.sample(xp, xi, cols, atoms, noise, jitter)
                 _marginals.raise_if_not_factorised(info)
                 return f
-
-        @staticmethod
-        def curve_energy(curve, columns=None, return_gradient=False):
-            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
-            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
-            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy on the T atoms and
-            the C S segments; with the columns of one discovered group, that group's own energy.  The training side is built once
-            per call.  fp64, torch.no_grad."""
-            return _geodesic.curve_energy(_curve_terms(columns), curve, num_latent_dims, device, return_gradient)
-
-        @staticmethod
-        def curve_length(curve, columns=None):
-            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E)."""
-            return _geodesic.curve_length(_curve_terms(columns), curve, num_latent_dims, device)
-
-        @staticmethod
-        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
-            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
-            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
-            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
-            iterate is returned, so its energy never exceeds the start's.  With the columns of one discovered group: the paths
-            that group considers short.  The training side is built once per call; an iteration is one call of
-            ops.ard_rbf_point_energy plus element-wise work.  fp64."""
-            return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, device, num_segments,
-                                             num_iterations, learning_rate, init)
-
-        @staticmethod
-        def geodesic_acceleration(x, v, columns=None):
-            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
-            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), the weights phi included; Gamma
-            the Christoffel symbols of the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
-            ops.ard_rbf_point_christoffel on the T atoms and one of ops.geodesic_accel, which sums them; the training side is
-            built once per call.  fp64, torch.no_grad."""
-            return _geodesic.geodesic_acceleration(_geodesic_terms(columns), x, v, num_latent_dims, device)
-
-        @staticmethod
-        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
-            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
-            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
-            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
-            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
-            velocities, in the same shape.  With the columns of one discovered group: where that group's manifold takes a
-            motion.  A stage is one call of ops.ard_rbf_point_christoffel on the T atoms and one of ops.geodesic_accel plus
-            element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
-            metric failed to factor at any stage.  fp64, torch.no_grad."""
-            return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, device, num_steps, return_velocity)
-
-        @staticmethod
-        def geodesic_deviation(x, v, dx, dv, columns=None):
-            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
-            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
-            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
-            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.geodesic_deviation(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, device)
-
-        @staticmethod
-        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
-            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
-            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
-            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
-            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
-            any stage.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.exp_map_tangent(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, device, num_steps, return_velocity)
-
-        @staticmethod
-        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
-            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
-            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
-            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
-            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
-            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
-            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.log_map(_geodesic_terms(columns, True), x_from, x_to, num_latent_dims, device, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predict_missing_data(y_test, use_pca=False, x_test_mean=None, x_test_var=None, observed=None):

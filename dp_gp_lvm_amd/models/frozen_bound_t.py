@@ -150,21 +150,8 @@ class _MomentsT:
         P_t = sum_d phi_td (r_td r_td^T - C_t,p(d))  (marginals._Marginals.metric_total with phi as the columns' weights)."""
         return self._atoms().metric_total(x, cols, weights=self.phit)
 
-    def curve_operands(self, cols):
-        """(P [T, M, M], prior [T, Q, Q]) of metric's text over the columns `cols`: marginals._Marginals._metric_operands with
-        phi as the columns' weights; formed once per curve call."""
-        self._curve_atoms = self._atoms()
-        return self._curve_atoms._metric_operands(cols, self.phit)
-
-    def curve_terms(self, x, v, p, prior):
-        """marginals._Marginals.curve_terms on the T atoms, (p, prior) from curve_operands."""
-        return self._curve_atoms.curve_terms(x, v, p, prior)
-
-    def geodesic_terms(self, x, v, p, prior):
-        """marginals._Marginals.geodesic_terms on the T atoms, (p, prior) from curve_operands: the acceleration under metric's
-        G, phi included."""
-        return self._curve_atoms.geodesic_terms(x, v, p, prior)
-
-    def geodesic_tangent_terms(self, x, v, dx, dv, p, prior):
-        """marginals._Marginals.geodesic_tangent_terms on the T atoms, (p, prior) from curve_operands."""
-        return self._curve_atoms.geodesic_tangent_terms(x, v, dx, dv, p, prior)
+    def metric_part(self, cols):
+        """(atoms, P [T, M, M], prior [T, Q, Q]): the part of a marginals.Metric under metric's G over the columns `cols`, the T
+        atoms with marginals._Marginals._metric_operands' pair, phi as the columns' weights; formed once per call."""
+        atoms = self._atoms()
+        return (atoms,) + atoms._metric_operands(cols, self.phit)

@@ -32,7 +32,8 @@ from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .frozen_bound import _TestBound, _as_device, kernel_slots
 from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
-from . import collapsed, geodesic as _geodesic, marginals as _marginals, predictor as _predictor
+from . import collapsed, marginals as _marginals, predictor as _predictor
+from .latent_geometry import LatentGeometry, ViewsLatentGeometry
 
 
 def _gp_forward(x, y, gamma, alpha, beta):
@@ -507,31 +508,22 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             mean, var = _train_marginals().at(xt, st_, _marginals.columns_arg(columns, num_dimensions, dev_))
         return mean[0], var[0]
 
-    def _curve_terms(columns):
-        """The terms of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once."""
+    def _metric_under(columns, name):
+        """latent_geometry's hook: the marginals.Metric under latent_metric(., columns), the training side and (P, prior)
+        formed once."""
         cols = _marginals.columns_arg(columns, num_dimensions, dev_)
         with torch.no_grad():
             marg = _train_marginals()
-            p, prior = marg._metric_operands(cols, None)
-        return lambda x, v: marg.curve_terms(x, v, p, prior)
+            return _marginals.Metric([(marg,) + marg._metric_operands(cols, None)])
 
-    def _geodesic_terms(columns, tangent=False):
-        """The acceleration of models/geodesic.py under latent_metric(., columns): the training side and (P, prior), formed once;
-        tangent: the acceleration with its derivative along a direction (marginals.geodesic_tangent_terms)."""
-        cols = _marginals.columns_arg(columns, num_dimensions, dev_)
-        with torch.no_grad():
-            marg = _train_marginals()
-            p, prior = marg._metric_operands(cols, None)
-        if tangent:
-            return lambda x, v, dx, dv: marg.geodesic_tangent_terms(x, v, dx, dv, p, prior)
-        return lambda x, v: marg.geodesic_terms(x, v, p, prior)
-
-    class BayesianGPLVM(Trainable):
+    class BayesianGPLVM(LatentGeometry, Trainable):
         """Accessors as in the reference (gaussian_process.py:276-340), and its two prediction methods (:329-538) with the same
         keywords and return tuples as dp_gp_lvm's, plus test_latent_gradients / optimise_test_latents / prediction_terms.
         Prediction runs in fp64 (the reference's dtype) whatever `precision` the model trains in; the training-side f_hat and
-        KL(q(X)) of the bounds are those of the model's own evaluation (mixed Psi statistics when precision='mixed')."""
+        KL(q(X)) of the bounds are those of the model's own evaluation (mixed Psi statistics when precision='mixed').
+        The latent-geometry methods are models/latent_geometry.LatentGeometry's, over the model's one kernel."""
         raw_variables = raw
+        _latent_dims, _device, _metric_of = num_latent_dims, dev_, staticmethod(_metric_under)
 
         @staticmethod
         def predict_new_latent_variables(y_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
@@ -585,83 +577,6 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             cols = _marginals.columns_arg(columns, num_dimensions, dev_)
             with torch.no_grad():
                 return _train_marginals().metric(_marginals.points_arg(x, num_latent_dims, dev_), cols)[0]
-
-        @staticmethod
-        def magnification(x, columns=None):
-            """[N*]: the magnification factor sqrt(det G(x)) of latent_metric(x, columns), the volume element of the learnt map
-            (what GPy draws as plot_magnification), as exp(1/2 logdet) from a Cholesky factorisation of G."""
-            with torch.no_grad():
-                return _marginals.magnification(BayesianGPLVM.latent_metric(x, columns))
-
-        @staticmethod
-        def curve_energy(curve, columns=None, return_gradient=False):
-            """E [C] of the curves `curve` [C x S+1 x Q] (or one curve [S+1 x Q]; numpy or torch) under latent_metric(., columns):
-            E = S sum_i v_i^T G(x_i) v_i over the segments' midpoints x_i and directions v_i (models/geodesic.py).  With
-            return_gradient also dE / dcurve in the shape of `curve`.  One call of ops.ard_rbf_point_energy on the C S segments;
-            the training side is built once per call.  fp64, torch.no_grad."""
-            return _geodesic.curve_energy(_curve_terms(columns), curve, num_latent_dims, dev_, return_gradient)
-
-        @staticmethod
-        def curve_length(curve, columns=None):
-            """L [C] = sum_i sqrt(v_i^T G(x_i) v_i) of the curves `curve`, as curve_energy (L^2 <= E)."""
-            return _geodesic.curve_length(_curve_terms(columns), curve, num_latent_dims, dev_)
-
-        @staticmethod
-        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, columns=None, init=None):
-            """(curve [C x S+1 x Q], length [C], energy [C]): discrete geodesics under latent_metric(., columns) between the
-            latent points x_from and x_to ([C x Q] or [Q]), S = num_segments: the curve energy minimised over the interior points
-            by Adam from the straight line (or from `init` [C x S+1 x Q]), the end points fixed; each curve's lowest-energy
-            iterate is returned, so its energy never exceeds the start's.  The training side is built once per call; an iteration
-            is one call of ops.ard_rbf_point_energy plus element-wise work.  fp64."""
-            return _geodesic.latent_geodesic(_curve_terms(columns), x_from, x_to, num_latent_dims, dev_, num_segments,
-                                             num_iterations, learning_rate, init)
-
-        @staticmethod
-        def geodesic_acceleration(x, v, columns=None):
-            """a [N* x Q] (or [Q]): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the latent points x with
-            the velocities v ([N* x Q] or [Q]; numpy or torch) under latent_metric(., columns), Gamma the Christoffel symbols of
-            the first kind contracted twice with v (models/marginals.geodesic_terms).  One call of
-            ops.ard_rbf_point_christoffel and one of ops.geodesic_accel; the training side is built once per call.  fp64,
-            torch.no_grad."""
-            return _geodesic.geodesic_acceleration(_geodesic_terms(columns), x, v, num_latent_dims, dev_)
-
-        @staticmethod
-        def latent_exp_map(x, v, num_steps=64, columns=None, return_velocity=False):
-            """curve [C x num_steps+1 x Q] (or [num_steps+1 x Q] for x, v [Q]): the exponential map of the velocities v at the
-            latent points x under latent_metric(., columns): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
-            t in [0, 1], all C curves in one batch (models/geodesic.exp_map); row 0 holds the bits of x, and the curve is what
-            curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
-            velocities, in the same shape.  A stage is one call of ops.ard_rbf_point_christoffel and one of ops.geodesic_accel
-            plus element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
-            metric failed to factor at any stage.  fp64, torch.no_grad."""
-            return _geodesic.exp_map(_geodesic_terms(columns), x, v, num_latent_dims, dev_, num_steps, return_velocity)
-
-        @staticmethod
-        def geodesic_deviation(x, v, dx, dv, columns=None):
-            """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
-            direction (dx, dv) of the state (x, v): the right-hand side of the Jacobi equation of latent_metric(., columns), in
-            closed form (no differencing).  One call of ops.ard_rbf_point_christoffel_tangent and one of
-            ops.geodesic_accel_tangent; the training side is built once per call.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.geodesic_deviation(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, dev_)
-
-        @staticmethod
-        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, columns=None, return_velocity=False):
-            """(curve, dcurve) [C x num_steps+1 x Q] (or [num_steps+1 x Q]): latent_exp_map(x, v, num_steps, columns), with its
-            bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
-            latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
-            (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
-            any stage.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.exp_map_tangent(_geodesic_terms(columns, True), x, v, dx, dv, num_latent_dims, dev_, num_steps, return_velocity)
-
-        @staticmethod
-        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
-            """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
-            logarithm map of x_to at x_from under latent_metric(., columns), the inverse of latent_exp_map at the same num_steps:
-            Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
-            does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
-            |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
-            not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad."""
-            return _geodesic.log_map(_geodesic_terms(columns, True), x_from, x_to, num_latent_dims, dev_, num_steps, max_iterations, tol, init)
 
         @staticmethod
         def predictive_covariance(x, columns=None, noise=False):
@@ -1129,34 +1044,23 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
         return vs
 
-    def _curve_terms(views, total):
-        """The terms of models/geodesic.py of every view of `views` (one entry: their sum, with total), formed once."""
+    def _metrics_under(views, total):
+        """latent_geometry's hook: the marginals.Metric of every view of `views`, or with total the one of their sum (one part
+        per view), the training side and every view's (P, prior) formed once."""
         vs = _views_arg(views)
         with torch.no_grad():
             train = _train_marginals()
-            pairs = [train[v]._metric_operands(None, None) for v in vs]
-        each = [lambda x, v, marg=train[vv], pair=pair: marg.curve_terms(x, v, *pair) for vv, pair in zip(vs, pairs)]
-        return [_geodesic.sum_terms(each)] if total else each
+            parts = [(train[v],) + train[v]._metric_operands(None, None) for v in vs]
+            return [_marginals.Metric(parts)] if total else [_marginals.Metric([part]) for part in parts]
 
-    def _geodesic_terms(views, total, tangent=False):
-        """The accelerations of models/geodesic.py of every view of `views` (one entry: under their summed metric, with total: the
-        views' slabs go to one factorisation), formed once; tangent: with their derivatives along a direction
-        (marginals.geodesic_tangent_terms)."""
-        vs = _views_arg(views)
-        with torch.no_grad():
-            train = _train_marginals()
-            pairs = [train[v]._metric_operands(None, None) for v in vs]
-        make = _marginals.geodesic_tangent_terms if tangent else _marginals.geodesic_terms
-        if total:
-            return [make([(train[vv], pair[0]) for vv, pair in zip(vs, pairs)], torch.cat([pair[1] for pair in pairs]))]
-        return [make([(train[vv], pair[0])], pair[1]) for vv, pair in zip(vs, pairs)]
-
-    class ManifoldRelevanceDetermination(Trainable):
+    class ManifoldRelevanceDetermination(ViewsLatentGeometry, Trainable):
         """Accessors as in the reference (gaussian_process.py:667-727), its two prediction methods (:729-990) and
         test_latent_gradients / optimise_test_latents / prediction_terms as bayesian_gp_lvm's, with lists of views in place of
         y_test: the first Vo views are observed.  Prediction runs in fp64 (the reference's dtype) whatever `precision` the
-        model trains in; the training-side f_hat and KL(q(X)) are those of the model's own evaluation."""
+        model trains in; the training-side f_hat and KL(q(X)) are those of the model's own evaluation.
+        The latent-geometry methods are models/latent_geometry.ViewsLatentGeometry's, every view under its own kernel."""
         raw_variables = raw
+        _latent_dims, _device, _metrics_of = num_latent_dims, dev_, staticmethod(_metrics_under)
 
         @staticmethod
         def predict_new_latent_variables(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False):
@@ -1177,8 +1081,7 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             observed; a column never observed in training has mean 0 and variance alpha_v + 1/beta_v):
             optimise_test_latents(..., observed=) followed by this is how a mask-trained model predicts at test points.
             fp64, torch.no_grad."""
-            vs = list(range(num_views)) if views is None else [int(v) for v in views]
-            assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
+            vs = _views_arg(views)
             return _marginals_at(_as_device(x_test_mean, dev_), _as_device(x_test_var, dev_), vs)
 
         @staticmethod
@@ -1187,8 +1090,7 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
             view: p(x_mean, x_var) gives the bits of that view's predictive_marginals, differentiably in q(X*); p.vjp is its
             vector-Jacobian product.  The training side of all views is built once, here, at the model's current parameters: stale
             after further training."""
-            vs = list(range(num_views)) if views is None else [int(v) for v in views]
-            assert vs and all(0 <= v < num_views for v in vs), 'views must be view indices in [0, V)'
+            vs = _views_arg(views)
             with torch.no_grad():
                 train = _train_marginals()
                 return [_predictor.of_marginals(train[v], _marginals.columns_arg(None, num_dimensions[v], dev_), dev_) for v in vs]
@@ -1245,80 +1147,6 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                     num_samples, noise, jitter, seed, None if draws is None else draws[i], infos) for i, v in enumerate(vs)]
                 _marginals.raise_if_not_factorised(torch.cat(infos))
             return out
-
-        @staticmethod
-        def magnification(x, views=None):
-            """One magnification factor sqrt(det G_v(x)) [N*] per view of `views` (default: all V, in order)."""
-            with torch.no_grad():
-                return [_marginals.magnification(g) for g in ManifoldRelevanceDetermination.latent_metric(x, views)]
-
-        @staticmethod
-        def curve_energy(curve, views=None, total=False, return_gradient=False):
-            """One curve energy E [C] per view of `views` (default: all V, in order) of the curves `curve` [C x S+1 x Q] (or one
-            curve [S+1 x Q]), as bayesian_gp_lvm.curve_energy under the view's latent_metric; with return_gradient one pair
-            (E, dE / dcurve) per view.  total=True: one result, under the summed metric latent_metric(., views, total=True)."""
-            out = [_geodesic.curve_energy(t, curve, num_latent_dims, dev_, return_gradient) for t in _curve_terms(views, total)]
-            return out[0] if total else out
-
-        @staticmethod
-        def curve_length(curve, views=None, total=False):
-            """One curve length L [C] per view of `views`, as bayesian_gp_lvm.curve_length; total=True: under the summed metric."""
-            out = [_geodesic.curve_length(t, curve, num_latent_dims, dev_) for t in _curve_terms(views, total)]
-            return out[0] if total else out
-
-        @staticmethod
-        def latent_geodesic(x_from, x_to, num_segments=32, num_iterations=200, learning_rate=0.01, views=None, total=False,
-                            init=None):
-            """One triple (curve [C x S+1 x Q], length [C], energy [C]) per view of `views`: the view's own geodesics, as
-            bayesian_gp_lvm.latent_geodesic under the view's latent_metric; total=True: one triple, the geodesics under the
-            summed metric.  The training side of all views is built once per call."""
-            out = [_geodesic.latent_geodesic(t, x_from, x_to, num_latent_dims, dev_, num_segments, num_iterations, learning_rate,
-                                             init) for t in _curve_terms(views, total)]
-            return out[0] if total else out
-
-        @staticmethod
-        def geodesic_acceleration(x, v, views=None, total=False):
-            """One acceleration a [N* x Q] (or [Q]) per view of `views` (default: all V, in order), as
-            bayesian_gp_lvm.geodesic_acceleration under the view's latent_metric; total=True: one result, under the summed
-            metric latent_metric(., views, total=True).  The training side of all views is built once per call."""
-            out = [_geodesic.geodesic_acceleration(t, x, v, num_latent_dims, dev_) for t in _geodesic_terms(views, total)]
-            return out[0] if total else out
-
-        @staticmethod
-        def latent_exp_map(x, v, num_steps=64, views=None, total=False, return_velocity=False):
-            """One curve [C x num_steps+1 x Q] (or [num_steps+1 x Q]; with return_velocity one pair (curve, velocities)) per view
-            of `views`: the view's own exponential map, as bayesian_gp_lvm.latent_exp_map under the view's latent_metric;
-            total=True: one result, under the summed metric (a stage is then one ops.ard_rbf_point_christoffel call per view and
-            one ops.geodesic_accel).  The training side of all views is built once per call."""
-            out = [_geodesic.exp_map(t, x, v, num_latent_dims, dev_, num_steps, return_velocity)
-                   for t in _geodesic_terms(views, total)]
-            return out[0] if total else out
-
-        @staticmethod
-        def geodesic_deviation(x, v, dx, dv, views=None, total=False):
-            """One pair (a, da) per view of `views` (default: all V, in order), as bayesian_gp_lvm.geodesic_deviation under the
-            view's latent_metric; total=True: one pair, under the summed metric.  The training side of all views is built once
-            per call."""
-            out = [_geodesic.geodesic_deviation(t, x, v, dx, dv, num_latent_dims, dev_) for t in _geodesic_terms(views, total, True)]
-            return out[0] if total else out
-
-        @staticmethod
-        def latent_exp_map_tangent(x, v, dx, dv, num_steps=64, views=None, total=False, return_velocity=False):
-            """One result (curve, dcurve[, velocity, dvelocity]) per view of `views`, as bayesian_gp_lvm.latent_exp_map_tangent
-            under the view's latent_metric; total=True: one result, under the summed metric (a stage is then one
-            ops.ard_rbf_point_christoffel_tangent call per view and one ops.geodesic_accel_tangent)."""
-            out = [_geodesic.exp_map_tangent(t, x, v, dx, dv, num_latent_dims, dev_, num_steps, return_velocity)
-                   for t in _geodesic_terms(views, total, True)]
-            return out[0] if total else out
-
-        @staticmethod
-        def latent_log_map(x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, views=None, total=False, init=None):
-            """One result (v, distance, curve, residual) per view of `views`: the view's own logarithm map, as
-            bayesian_gp_lvm.latent_log_map under the view's latent_metric; total=True: one result, under the summed metric.
-            The training side of all views is built once per call."""
-            out = [_geodesic.log_map(t, x_from, x_to, num_latent_dims, dev_, num_steps, max_iterations, tol, init)
-                   for t in _geodesic_terms(views, total, True)]
-            return out[0] if total else out
 
         @staticmethod
         def predict_missing_data(views_test, use_pca=False, x_test_mean=None, x_test_var=None, reference_compat=False,

@@ -9,18 +9,21 @@ v_i = c_{i+1} - c_i, and with e_i = v_i^T G(x_i) v_i
 
 (a segment moves its midpoint by half of either end and its direction by -/+ the end).  A minimiser of E between fixed ends is a
 discrete geodesic.  Everything here works on `terms`, a callable (x [N,Q], v [N,Q]) -> (e [N], dx [N,Q], dv [N,Q]) that a model
-builds ONCE per call from its training side (marginals._Marginals.curve_terms on ops.ard_rbf_point_energy): C curves are one
+builds ONCE per call from its training side (marginals.Metric.curve_terms on ops.ard_rbf_point_energy): C curves are one
 call with N = C S, and an iteration of latent_geodesic is one call plus element-wise work.  fp64, no autograd.
 
 The initial-value side: a geodesic obeys G x'' = -Gamma(x, x'), Gamma the Christoffel symbols of the first kind contracted twice
 with the velocity.  exp_map integrates (x', v') = (v, -G^-1 Gamma) over t in [0, 1] by the classical Runge-Kutta scheme on `accel`,
 a callable (x [N,Q], v [N,Q]) -> (a [N,Q], speed [N], info [N]) that a model builds ONCE per call
-(marginals.geodesic_terms on ops.ard_rbf_point_christoffel and ops.geodesic_accel): C curves are one batch, a stage is one call.
+(marginals.Metric.accel on ops.ard_rbf_point_christoffel and ops.geodesic_accel): C curves are one batch, a stage is one call.
 
 Its tangent and its inverse: exp_map_tangent integrates the tangent-linear equation beside the curve (a discrete Jacobi field, the
 exact derivative of exp_map's discrete map) on `accel_tangent`, a callable (x, v, dx, dv [N,Q]) -> (a, da [N,Q], speed [N], info [N])
-(marginals.geodesic_tangent_terms on ops.ard_rbf_point_christoffel_tangent and ops.geodesic_accel_tangent), and log_map is Newton
+(marginals.Metric.accel_tangent on ops.ard_rbf_point_christoffel_tangent and ops.geodesic_accel_tangent), and log_map is Newton
 shooting on it: one batched tangent shot over C Q rows per iteration.
+
+The three callables are the methods of ONE marginals.Metric, the metric that a public call runs under; the models' public methods
+on them are written once, in models/latent_geometry.py.
 """
 import numpy as np
 import torch
@@ -44,6 +47,17 @@ def ends_arg(x, q, device, name):
     x = x.to(device=device, dtype=TORCH_DTYPE)
     assert x.dim() in (1, 2) and x.shape[-1] == q and x.shape[0] >= 1, '%s must be [Q] or [C x Q]' % name
     return (x[None] if x.dim() == 1 else x).contiguous()
+
+
+def states_arg(q, device, **named):
+    """(the arguments `named`, each [Q] or [C x Q], as ends_arg's [C x Q] tensors in the order given, whether the first came as
+    one point [Q]); AssertionError unless all have the same shape."""
+    first = next(iter(named.values()))
+    single = (first.dim() if torch.is_tensor(first) else np.asarray(first).ndim) == 1
+    out = [ends_arg(x, q, device, name) for name, x in named.items()]
+    names = list(named)
+    assert all(o.shape == out[0].shape for o in out), '%s and %s must have the same shape' % (', '.join(names[:-1]), names[-1])
+    return out, single
 
 
 def segments(c):
@@ -79,14 +93,6 @@ def prior_terms(v, weight):
     return torch.sum(v * v * weight, dim=1), torch.zeros_like(v), 2.0 * v * weight
 
 
-def sum_terms(all_terms):
-    """The terms of a sum of metrics."""
-    def terms(x, v):
-        out = [t(x, v) for t in all_terms]
-        return tuple(torch.sum(torch.stack(parts), dim=0) if len(parts) > 1 else parts[0] for parts in zip(*out))
-    return terms
-
-
 def curve_energy(terms, curve, q, device, return_gradient=False):
     c, single = curves_arg(curve, q, device)
     with torch.no_grad():
@@ -116,8 +122,7 @@ def latent_geodesic(terms, x_from, x_to, q, device, num_segments=32, num_iterati
     """(curve [C x S+1 x Q], length [C], energy [C]): E minimised over the interior points by Adam (torch.optim.Adam only applies
     the update) from the straight line, or from `init` [C x S+1 x Q] with its end rows replaced; each curve's lowest-energy
     iterate is kept, the start included, so the returned energy never exceeds the start's."""
-    a, b = ends_arg(x_from, q, device, 'x_from'), ends_arg(x_to, q, device, 'x_to')
-    assert a.shape == b.shape, 'x_from and x_to must have the same shape'
+    (a, b), _ = states_arg(q, device, x_from=x_from, x_to=x_to)
     num_segments, num_iterations = int(num_segments), int(num_iterations)
     assert num_segments >= 1 and num_iterations >= 0, 'num_segments >= 1 and num_iterations >= 0'
     n = a.shape[0]
@@ -154,22 +159,9 @@ def latent_geodesic(terms, x_from, x_to, q, device, num_segments=32, num_iterati
         return best, length(best_e, n), best_energy
 
 
-def prior_accel(v, weight):
-    """accel's triple under a constant diagonal metric diag(weight [Q]): straight lines, (0, sum_q weight_q v_q^2, 0)."""
-    return torch.zeros_like(v), torch.sum(v * v * weight, dim=1), torch.zeros(v.shape[0], dtype=torch.int32, device=v.device)
-
-
-def prior_accel_tangent(v, weight):
-    """accel_tangent's four under a constant diagonal metric: prior_accel's triple with da = 0 in second place."""
-    a, speed, info = prior_accel(v, weight)
-    return a, torch.zeros_like(v), speed, info
-
-
 def geodesic_acceleration(accel, x, v, q, device):
     """a [N* x Q] (or [Q] for one point): x'' of the geodesics through x with the velocities v ([N* x Q] or [Q])."""
-    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
-    xs, vs = ends_arg(x, q, device, 'x'), ends_arg(v, q, device, 'v')
-    assert xs.shape == vs.shape, 'x and v must have the same shape'
+    (xs, vs), single = states_arg(q, device, x=x, v=v)
     with torch.no_grad():
         a = accel(xs, vs)[0]
     return a[0] if single else a
@@ -181,9 +173,7 @@ def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False):
     With return_velocity also the velocities in the same shape.  Four calls of accel per step plus element-wise work; nothing is
     read on the host until ONE read of the accumulated info at the end: FloatingPointError if the metric failed to factor at
     any stage of any curve."""
-    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
-    xs, vs = ends_arg(x, q, device, 'x'), ends_arg(v, q, device, 'v')
-    assert xs.shape == vs.shape, 'x and v must have the same shape'
+    (xs, vs), single = states_arg(q, device, x=x, v=v)
     num_steps = int(num_steps)
     assert num_steps >= 1, 'num_steps >= 1'
     c, h = xs.shape[0], 1.0 / num_steps
@@ -223,11 +213,8 @@ def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False):
 def geodesic_deviation(accel_tangent, x, v, dx, dv, q, device):
     """(a, da) [N* x Q] (or [Q] for one point): geodesic_acceleration's a with its bits, and its derivative along the direction
     (dx, dv) of the state (x, v), the right-hand side of the Jacobi equation.  accel_tangent: a callable
-    (x, v, dx, dv [N,Q]) -> (a, da [N,Q], speed [N], info [N]) that a model builds ONCE per call (marginals.geodesic_tangent_terms)."""
-    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
-    xs = ends_arg(x, q, device, 'x')
-    vs, dxs, dvs = (ends_arg(t, q, device, nm) for t, nm in ((v, 'v'), (dx, 'dx'), (dv, 'dv')))
-    assert xs.shape == vs.shape == dxs.shape == dvs.shape, 'x, v, dx and dv must have the same shape'
+    (x, v, dx, dv [N,Q]) -> (a, da [N,Q], speed [N], info [N]) that a model builds ONCE per call (marginals.Metric.accel_tangent)."""
+    (xs, vs, dxs, dvs), single = states_arg(q, device, x=x, v=v, dx=dx, dv=dv)
     with torch.no_grad():
         a, da = accel_tangent(xs, vs, dxs, dvs)[:2]
     return (a[0], da[0]) if single else (a, da)
@@ -275,10 +262,7 @@ def exp_map_tangent(accel_tangent, x, v, dx, dv, q, device, num_steps=64, return
     of (x, v), a discrete Jacobi field.  With return_velocity (curve, dcurve, velocity, dvelocity).  Four calls of accel_tangent
     per step plus element-wise work; the stages' info is accumulated on the device and read ONCE at the end:
     FloatingPointError if the metric failed to factor at any stage of any curve."""
-    single = (x.dim() if torch.is_tensor(x) else np.asarray(x).ndim) == 1
-    xs = ends_arg(x, q, device, 'x')
-    vs, dxs, dvs = (ends_arg(t, q, device, nm) for t, nm in ((v, 'v'), (dx, 'dx'), (dv, 'dv')))
-    assert xs.shape == vs.shape == dxs.shape == dvs.shape, 'x, v, dx and dv must have the same shape'
+    (xs, vs, dxs, dvs), single = states_arg(q, device, x=x, v=v, dx=dx, dv=dv)
     num_steps = int(num_steps)
     assert num_steps >= 1, 'num_steps >= 1'
     with torch.no_grad():
@@ -324,9 +308,7 @@ def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations
     <= tol max(1, |x_to|).  ONE host read per iteration, of that test.  A curve whose residual stays above it is reported through
     `residual`, not raised; FloatingPointError only if the very first shot fails to factor.  The base features are recomputed for
     each of the Q directions."""
-    single = (x_from.dim() if torch.is_tensor(x_from) else np.asarray(x_from).ndim) == 1
-    a, b = ends_arg(x_from, q, device, 'x_from'), ends_arg(x_to, q, device, 'x_to')
-    assert a.shape == b.shape, 'x_from and x_to must have the same shape'
+    (a, b), single = states_arg(q, device, x_from=x_from, x_to=x_to)
     num_steps, max_iterations = int(num_steps), int(max_iterations)
     assert num_steps >= 1 and max_iterations >= 0, 'num_steps >= 1 and max_iterations >= 0'
     c = a.shape[0]

@@ -21,6 +21,10 @@ And the JOINT posterior of column d's noise-free function at several determinist
     cov_d(x, x') = alpha exp(-1/2 sum_q gamma_q (x_q - x'_q)^2) - k(x)^T (K_uu^-1 - P_p(d)) k(x')
 whose diagonal is var(n,d) at s = 0 less 1/beta: _Marginals.pattern_covariance / .covariance (ops.ard_rbf_point_cov, or the composed
 form where it is faster) and .sample (one batched Cholesky over the (kernel, pattern) pairs, one batched product).
+
+Every model's metric is the same object, a sum over parts b_k(x)^T P_k b_k(x) plus constant diagonal terms: Metric, built once per
+public call from the models' (_Marginals, P, prior) parts, gives the curve terms, the geodesic acceleration and its tangent that
+models/geodesic.py works on (the shared methods are in models/latent_geometry.py).
 """
 import numpy as np
 import torch
@@ -28,6 +32,7 @@ import torch
 from .. import ops
 from ..utils.types import TORCH_DTYPE
 from . import collapsed
+from .geodesic import prior_terms
 
 
 class _Marginals:
@@ -79,37 +84,6 @@ class _Marginals:
         out = [torch.sum(ops.ard_rbf_point_metric(self.z, x[i:i + step], self.gamma, self.alpha, p), dim=0)
                for i in range(0, x.shape[0], step)]
         return torch.cat(out) + torch.sum(prior, dim=0)
-
-    def curve_terms(self, x, v, p, prior):
-        """(e [N*], dx [N*, Q], dv [N*, Q]): e_n = v_n^T G(x_n) v_n of metric_total's G along the directions v [N*, Q] at the
-        points x [N*, Q], and its gradients with respect to x_n and v_n: what a curve's energy and its gradient are made of
-        (models/geodesic.py).  (p, prior) are _metric_operands' pair, formed once by the caller; prior may hold further
-        constant diagonal metrics [*, Q, Q] (only the diagonals are read).  ONE call of ops.ard_rbf_point_energy per block of
-        points, summed over the K kernels, plus the prior's share sum_q w_q v_q^2 in e and 2 w_q v_q in dv,
-        w_q = sum_k n_k alpha_k gamma_kq.  Blocks of at most 2^25 result entries, as metric_total."""
-        x, v = x.contiguous(), v.contiguous()
-        k, q = self.z.shape[0], self.z.shape[2]
-        step = max(1, (1 << 25) // (k * (2 * q + 1)))
-        parts = []
-        for i in range(0, x.shape[0], step):
-            out = ops.ard_rbf_point_energy(self.z, x[i:i + step], v[i:i + step], self.gamma, self.alpha, p)
-            parts.append([o[0] if k == 1 else torch.sum(o, dim=0) for o in out])
-        e, dx, dv = (ps[0] if len(ps) == 1 else torch.cat(ps) for ps in zip(*parts))
-        w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0)
-        return e + torch.sum(v * v * w, dim=1), dx, dv + 2.0 * v * w
-
-    def geodesic_terms(self, x, v, p, prior):
-        """(a [N*, Q], speed [N*], info [N*] int32): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the
-        points x [N*, Q] with the velocities v [N*, Q] under metric_total's G, speed = v^T G v, and the factorisation's info (0, or
-        the failing pivot: a is then NaN at that point).  (p, prior) as for curve_terms.  ONE call of
-        ops.ard_rbf_point_christoffel and ONE of ops.geodesic_accel per block of points (geodesic_terms below)."""
-        return geodesic_terms([(self, p)], prior)(x, v)
-
-    def geodesic_tangent_terms(self, x, v, dx, dv, p, prior):
-        """(a, da [N*, Q], speed [N*], info [N*] int32): geodesic_terms' triple, with its bits, and the derivative da of the
-        acceleration along the direction (dx, dv) [N*, Q] of the state (x, v).  ONE call of ops.ard_rbf_point_christoffel_tangent
-        and ONE of ops.geodesic_accel_tangent per block of points (geodesic_tangent_terms below)."""
-        return geodesic_tangent_terms([(self, p)], prior)(x, v, dx, dv)
 
     def _patterns(self, cols):
         """(c [K, G', M, M], slot [K, J] long): the patterns to evaluate and, per kernel and column, its place among them.  With
@@ -195,52 +169,87 @@ class _Marginals:
         return p, (torch.sum(w, dim=1) * self.alpha)[:, None, None] * torch.diag_embed(self.gamma)
 
 
-# ---- the geodesic equation: what the models' geodesic_acceleration / latent_exp_map share ----------------------------------------
-def geodesic_terms(parts, prior):
-    """The callable (x [N, Q], v [N, Q]) -> (a [N, Q], speed [N], info [N]) of models/geodesic.py under the SUM of the metrics of
-    `parts`, a list of (_Marginals, P [K, M, M]) pairs (_metric_operands' P; MRD's summed metric has one pair per view), plus
-    the constant diagonal metrics `prior` [*, Q, Q] (only the diagonals are read).  With G = G0 + sum_k b_k^T P_k b_k the geodesic
-    obeys G x'' = -sum_k Gamma_k: one call of ops.ard_rbf_point_christoffel per pair gives the slabs (g_k, Gamma_k), one call of
-    ops.geodesic_accel sums them, adds G0, factorises and solves.  Blocks of at most 2^25 result entries, as curve_terms; a
-    point's bits do not depend on its block."""
-    q = parts[0][0].z.shape[2]
-    k = sum(marg.z.shape[0] for marg, _ in parts)
-    w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0).contiguous()
-    step = max(1, (1 << 25) // (k * (q * q + q)))
+# ---- the metric a latent-geometry call runs under: what models/latent_geometry.py hands to models/geodesic.py -------------------
+def _diagonal_sum(prior, q):
+    """w [Q]: the summed diagonals of the constant metrics prior [*, Q, Q]."""
+    return torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0).contiguous()
 
-    def terms(x, v):
-        x, v = x.contiguous(), v.contiguous()
+
+class Metric:
+    """The metric that ONE public call runs under, G(x) = sum over parts and their kernels of b_k(x)^T P_k b_k(x), plus constant
+    diagonal metrics.  parts: a list of (marg: _Marginals, P [K, M, M], prior [K, Q, Q]), _metric_operands' pair behind its
+    _Marginals (one part per model; MRD's summed metric has one per view); extra: further constant diagonal metrics [*, Q, Q] or
+    None (only the diagonals of prior and extra are read).  No part and an extra is the prior-only metric (dp_gp_lvm with no
+    chosen column observed in training).  Several parts with an extra occur nowhere and are refused.  Its three methods are the
+    callables of models/geodesic.py; every one runs in blocks of points of at most 2^25 result entries, and a point's bits do not
+    depend on its block.
+
+    A part carries its own prior because the sums differ: the energy of several parts is formed part by part, each with its own
+    prior share, and summed over the stacked parts; the acceleration hands ONE w, over all priors, to one factorisation."""
+
+    def __init__(self, parts, extra=None):
+        assert len(parts) <= 1 or extra is None, 'several parts with an extra prior are not defined'
+        assert parts or extra is not None, 'a metric needs a part or a prior'
+        self.parts = [(marg, p) for marg, p, _ in parts]
+        self.q = q = parts[0][0].z.shape[2] if parts else extra.shape[-1]
+        self.block = (1 << 25) // max(1, sum(marg.z.shape[0] for marg, _ in self.parts) * (q * q + q))   # accel's points per block
+        priors = [prior for _, _, prior in parts] + ([] if extra is None else [extra])
+        self.w = _diagonal_sum(priors[0] if len(priors) == 1 else torch.cat(priors), q)        # over all priors: accel's
+        self.ws = [self.w] if len(parts) <= 1 else [_diagonal_sum(prior, q) for prior in priors]  # per part: curve_terms'
+
+    def curve_terms(self, x, v):
+        """(e [N], dx [N, Q], dv [N, Q]): e_n = v_n^T G(x_n) v_n along the directions v [N, Q] at the points x [N, Q], and its
+        gradients with respect to x_n and v_n: what a curve's energy and its gradient are made of.  Per part ONE call of
+        ops.ard_rbf_point_energy per block of points, summed over the part's K kernels, plus its prior's share sum_q w_q v_q^2
+        in e and 2 w_q v_q in dv; several parts' terms are stacked and summed."""
+        if not self.parts:
+            return prior_terms(v, self.w)
+        x, v, q = x.contiguous(), v.contiguous(), self.q
+        each = []
+        for (marg, p), w in zip(self.parts, self.ws):
+            k = marg.z.shape[0]
+            step = max(1, (1 << 25) // (k * (2 * q + 1)))
+            blocks = []
+            for i in range(0, x.shape[0], step):
+                out = ops.ard_rbf_point_energy(marg.z, x[i:i + step], v[i:i + step], marg.gamma, marg.alpha, p)
+                blocks.append([o[0] if k == 1 else torch.sum(o, dim=0) for o in out])
+            e, dx, dv = (bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
+            each.append((e + torch.sum(v * v * w, dim=1), dx, dv + 2.0 * v * w))
+        return each[0] if len(each) == 1 else tuple(torch.sum(torch.stack(ts), dim=0) for ts in zip(*each))
+
+    def accel(self, x, v):
+        """(a [N, Q], speed [N], info [N] int32): the acceleration x'' = -G(x)^-1 Gamma(x, v) of the geodesic through the points
+        x with the velocities v, speed = v^T G v, and the factorisation's info (0, or the failing pivot: a is then NaN at that
+        point).  With G = G0 + sum_k b_k^T P_k b_k the geodesic obeys G x'' = -sum_k Gamma_k: one call of
+        ops.ard_rbf_point_christoffel per part gives the slabs (g_k, Gamma_k), one call of ops.geodesic_accel sums the
+        concatenated slabs, adds G0 = diag(w), factorises and solves.  The prior-only metric has straight lines: (0, w . v^2, 0)."""
+        if not self.parts:
+            return torch.zeros_like(v), torch.sum(v * v * self.w, dim=1), torch.zeros(v.shape[0], dtype=torch.int32, device=v.device)
+        return self._solve(ops.ard_rbf_point_christoffel, ops.geodesic_accel, 1, (x.contiguous(), v.contiguous()))
+
+    def accel_tangent(self, x, v, dx, dv):
+        """(a, da [N, Q], speed [N], info [N] int32): accel's triple with its bits, and da, the derivative of the acceleration
+        along the direction (dx, dv) of the state (x, v).  One call of ops.ard_rbf_point_christoffel_tangent per part gives the
+        slabs (g_k, Gamma_k, dg_k, dGamma_k), one call of ops.geodesic_accel_tangent sums them and solves twice with one
+        factor.  Twice accel's entries per point, so half its points per block.  The prior-only metric: da = 0."""
+        if not self.parts:
+            a, speed, info = self.accel(x, v)
+            return a, torch.zeros_like(v), speed, info
+        return self._solve(ops.ard_rbf_point_christoffel_tangent, ops.geodesic_accel_tangent, 2,
+                           (x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()))
+
+    def _solve(self, slabs_of, solve, width, state):
+        """solve(the parts' concatenated slabs_of(state), w, v) per block of the points of state = (x, v[, dx, dv]), `width` times
+        accel's entries per point.  A stage of an integrator comes here: one block (the usual case) is neither sliced nor
+        concatenated."""
+        parts, w, n = self.parts, self.w, state[0].shape[0]
+        step = max(1, self.block // width)
         blocks = []
-        for i in range(0, x.shape[0], step):
-            xb, vb = x[i:i + step], v[i:i + step]
-            slabs = [ops.ard_rbf_point_christoffel(marg.z, xb, vb, marg.gamma, marg.alpha, p) for marg, p in parts]
-            g, gam = slabs[0] if len(slabs) == 1 else (torch.cat([s[0] for s in slabs]), torch.cat([s[1] for s in slabs]))
-            blocks.append(ops.geodesic_accel(g, gam, w, vb))
-        return tuple(bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
-    return terms
-
-
-def geodesic_tangent_terms(parts, prior):
-    """The callable (x, v, dx, dv [N, Q]) -> (a [N, Q], da [N, Q], speed [N], info [N]) of models/geodesic.py: geodesic_terms'
-    triple with its bits, and da, the derivative of the acceleration along the direction (dx, dv) of the state (x, v).  One call
-    of ops.ard_rbf_point_christoffel_tangent per pair gives the slabs (g_k, Gamma_k, dg_k, dGamma_k), one call of
-    ops.geodesic_accel_tangent sums them and solves twice with one factor.  Blocks and the concatenation of the pairs' slabs as
-    geodesic_terms (twice the entries per point, so half its points per block); a point's bits do not depend on its block."""
-    q = parts[0][0].z.shape[2]
-    k = sum(marg.z.shape[0] for marg, _ in parts)
-    w = torch.sum(torch.diagonal(prior, dim1=-2, dim2=-1).reshape(-1, q), dim=0).contiguous()
-    step = max(1, (1 << 25) // (2 * k * (q * q + q)))
-
-    def terms(x, v, dx, dv):
-        x, v, dx, dv = x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()
-        blocks = []
-        for i in range(0, x.shape[0], step):
-            xb, vb, dxb, dvb = x[i:i + step], v[i:i + step], dx[i:i + step], dv[i:i + step]
-            slabs = [ops.ard_rbf_point_christoffel_tangent(marg.z, xb, vb, dxb, dvb, marg.gamma, marg.alpha, p) for marg, p in parts]
-            four = slabs[0] if len(slabs) == 1 else [torch.cat([s[j] for s in slabs]) for j in range(4)]
-            blocks.append(ops.geodesic_accel_tangent(*four, w, vb))
-        return tuple(bs[0] if len(bs) == 1 else torch.cat(bs) for bs in zip(*blocks))
-    return terms
+        for i in range(0, n, step):
+            sb = state if step >= n else [t[i:i + step] for t in state]
+            slabs = [slabs_of(marg.z, *sb, marg.gamma, marg.alpha, p) for marg, p in parts]
+            blocks.append(solve(*(slabs[0] if len(slabs) == 1 else [torch.cat(ss) for ss in zip(*slabs)]), w, sb[1]))
+        return blocks[0] if len(blocks) == 1 else tuple(torch.cat(bs) for bs in zip(*blocks))
 
 
 # ---- the joint posterior at latent points: what the models' predictive_covariance / sample_functions share ---------------------
