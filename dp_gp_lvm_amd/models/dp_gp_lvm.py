@@ -16,6 +16,7 @@ per-entry moments and for the shared-inducing test bound, whose sums over column
 (DESIGN.md section 7.15).
 """
 import contextlib
+import functools
 import gc
 import os
 import numpy as np
@@ -33,7 +34,7 @@ from ..utils import missing as _missing
 from ..utils.types import TORCH_DTYPE, create_positive_variable, default_device, register_variable
 from .dirichlet_process import dirichlet_process
 from .interfaces.trainable import Trainable
-from . import collapsed, marginals as _marginals, predictor as _predictor
+from . import collapsed, marginals as _marginals, predictor as _predictor, test_latents as _latents
 from .latent_geometry import LatentGeometry
 from .masked_bound_d import _MaskedBoundD
 from .masked_bound_t import _MaskedBoundT
@@ -507,28 +508,19 @@ def dp_gp_lvm(y_train,
 
     pred_state = {}
 
-    def _init_test_latents(y_test, y_ref, use_pca, x_test_mean, x_test_var):
-        """q(X*) as dp_gp_lvm.py:246-262: mean from PCA of y_test or from the nearest training neighbour (L2 over the given
-        columns) plus N(0, 0.01^2) noise, variances 1 — unless values are handed in."""
-        n_t = y_test.shape[0]
-        if x_test_mean is not None:
-            init = np.asarray(x_test_mean.detach().cpu() if torch.is_tensor(x_test_mean) else x_test_mean, dtype=np.float64)
-        elif use_pca:
-            init = pca(y_test, num_latent_dimensions=num_latent_dims)
-        else:
-            d2 = ((y_ref[:, None, :] - y_test[None, :, :]) ** 2).sum(-1)            # [N x N*]  (utils/expressions.py:28-44)
-            init = x_mean.detach().cpu().numpy()[np.argmin(d2, axis=0)] + \
-                np.random.normal(scale=0.01, size=(n_t, num_latent_dims))
-        if x_test_var is not None:
-            var = np.asarray(x_test_var.detach().cpu() if torch.is_tensor(x_test_var) else x_test_var, dtype=np.float64)
-        else:
-            var = np.ones((n_t, num_latent_dims))
-        xt_, st__ = _t(init), _t(var.reshape(n_t, num_latent_dims))
+    def _start(y_test, use_pca, x_test_mean, x_test_var, neighbour):
+        """q(X*) as dp_gp_lvm.py:246-262 (models/test_latents.start), registered as prediction variables."""
+        xt_, st__ = _latents.start(y_test.shape[0], num_latent_dims, device, x_test_mean, x_test_var, use_pca, y_test, neighbour)
         # q(X*): the reference creates these two as NON-trainable tf.Variables (dp_gp_lvm.py:258-262), which is what
         # get_prediction_variables() hands to the test-time optimiser (test/frey_faces_prediction.py:165-171)
         pred_state['x_test_mean'] = register_variable(xt_, trainable=False)
         pred_state['x_test_var_raw'] = register_variable(torch.log(torch.expm1(st__)), trainable=False)
         return xt_, st__
+
+    def _first_columns_start(y_test, do, use_pca, x_test_mean, x_test_var):
+        """The start for test points observed in their first `do` output dims: nearest neighbour over those columns."""
+        return _start(y_test, use_pca, x_test_mean, x_test_var,
+                      lambda: _latents.l2_neighbour(np.asarray(y_train)[:, :do], y_test, x_mean.detach().cpu().numpy()))
 
     def _fhat_on(y_t, xt, st_, dims=None):
         """f_hat (fused ELBO, dpgp_elbo_fhat) of the first `dims` output dims on (y_t, q(X*)) with the trained kernel and
@@ -583,12 +575,8 @@ def dp_gp_lvm(y_train,
         return xt, st_
 
     def _masked_init_local(y0, obs, use_pca, x_test_mean, x_test_var):
-        if x_test_mean is None and not use_pca and train_obs is not None:
-            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(np.asarray(y_train), train_obs, y0, obs,
-                                                                           x_mean.detach().cpu().numpy())
-        elif x_test_mean is None and not use_pca:
-            x_test_mean = _missing.masked_nearest_neighbour_init(np.asarray(y_train), y0, obs, x_mean.detach().cpu().numpy())
-        return _init_test_latents(y0, None, use_pca, x_test_mean, x_test_var)
+        return _start(y0, use_pca, x_test_mean, x_test_var,
+                      lambda: _latents.masked_neighbour(np.asarray(y_train), train_obs, y0, obs, x_mean.detach().cpu().numpy()))
 
     def _predictive_moments(cols, xt, st_):
         """Predictive mean [N* x Du] and covariance [Du x N* x N*] of the output dims `cols` at q(X*) (dp_gp_lvm.py:426-498)."""
@@ -935,10 +923,10 @@ def dp_gp_lvm(y_train,
                 y0, obs = _masked(y_test, observed, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound, out = _masked_bound(y0, obs, 'shared')
+                f_hat_test, kl_test = _latents.bound_at(bound, xt, st_)
+                pred_state['terms'] = bound.terms
                 with torch.no_grad():
-                    f_hat_test, _, _ = bound.evaluate(xt, st_)
-                    pred_state['terms'] = bound.terms
-                    test_ll = f_hat_test - ops.kl_qx(xt, st_)
+                    test_ll = f_hat_test - kl_test
                     return out[1] - out[2] + test_ll, xt, torch.diag_embed(st_), test_ll
             assert observed is None, 'observed= is taken by a model trained with observed='
             assert not split, ONE_GPU
@@ -946,7 +934,7 @@ def dp_gp_lvm(y_train,
             num_test_points, test_dims = np.shape(y_test)
             assert test_dims == num_dimensions, \
                 'Observed dimensionality for prediction must be equal to the dimensionality of the training data.'
-            xt, st_ = _init_test_latents(y_test, np.asarray(y_train), use_pca, x_test_mean, x_test_var)
+            xt, st_ = _first_columns_start(y_test, num_dimensions, use_pca, x_test_mean, x_test_var)
             out = evaluate().clone()                                                 # (objective, f_hat, KL, DP, hyper)
             f_hat_test, kl_test = _fhat_on(_t(y_test), xt, st_)
             lower_bound = out[1] + f_hat_test - out[2] - kl_test
@@ -970,25 +958,26 @@ def dp_gp_lvm(y_train,
             gradient is added once on every rank; prediction_terms then holds this rank's columns only."""
             _form_arg(form, observed)
             if observed is not None:
-                bound, _ = _masked_bound(*_masked(y_test, observed, form=form), form)
-                xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
-                    _t(x_test_var.detach().cpu().numpy() if torch.is_tensor(x_test_var) else x_test_var)
+                y0, obs = _masked(y_test, observed, form=form)
+                bound, _ = _masked_bound(y0, obs, form)
                 with torch.no_grad():
-                    _, dmu, ds = bound.evaluate(xt, st_, grad=True)
+                    grads = _latents.ascent_gradient(bound, _latents.latent_values(x_test_mean, device, num_latent_dims, y0.shape[0]),
+                                                     _latents.latent_values(x_test_var, device, num_latent_dims, y0.shape[0]))
                     pred_state['terms'] = bound.terms
-                return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)
+                return grads
             assert not split, ONE_GPU
             y_t = _t(np.asarray(y_test, dtype=np.float64))
             dd = y_t.shape[1]
-            xt, st_ = _t(x_test_mean.detach().cpu().numpy() if torch.is_tensor(x_test_mean) else x_test_mean), \
-                _t(x_test_var.detach().cpu().numpy() if torch.is_tensor(x_test_var) else x_test_var)
+            xt, st_ = _latents.latent_values(x_test_mean, device, num_latent_dims, y_t.shape[0]), \
+                _latents.latent_values(x_test_var, device, num_latent_dims, y_t.shape[0])
             evaluate()
             gam, al, be = buf['gamma'][:dd].contiguous(), buf['alpha'][:dd].contiguous(), buf['beta'][:dd].contiguous()
             ws_t = ops.ElboWorkspace(dd, y_t.shape[0], num_inducing_points, num_latent_dims, precision, device)
             ops.elbo_fhat(y_t, x_u, xt, st_, gam, al, be, jitter=GP_DEFAULT_JITTER, prec=precision, workspace=ws_t)
             gp, wk, gv, _, _ = ops.elbo_grad_chain(al, be, ws_t, jitter=GP_DEFAULT_JITTER, z=x_u, gamma=gam)
             dmu, ds, _, _ = ops.elbo_grad_psi(y_t, x_u, xt, st_, gam, al, gp, wk, gv, prec=precision)
-            return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)                        # minus the KL gradient (gp_expressions.py:10-24)
+            k_mu, k_s = _latents.kl_gradient(xt, st_)
+            return dmu - k_mu, ds - k_s
 
         @staticmethod
         def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
@@ -1004,27 +993,15 @@ def dp_gp_lvm(y_train,
                 y0, obs = _masked(y_test, observed, form=form)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound, _ = _masked_bound(y0, obs, form)
-                raw = torch.log(torch.expm1(st_))
-                opt = torch.optim.Adam([xt, raw], lr=learning_rate)
                 with torch.no_grad():
-                    for _ in range(num_iterations):
-                        sv = F.softplus(raw)
-                        _, g_mu, g_s = bound.evaluate(xt, sv, grad=True)
-                        xt.grad, raw.grad = -(g_mu - xt), -(g_s - 0.5 * (1.0 - 1.0 / sv)) * torch.sigmoid(raw)
-                        opt.step()
+                    fitted = _latents.fit(functools.partial(_latents.ascent_gradient, bound), xt, st_, num_iterations, learning_rate)
                     pred_state['terms'] = bound.terms
-                    return xt, F.softplus(raw)
+                    return fitted
             assert not split, ONE_GPU
             y_test = np.asarray(y_test, dtype=np.float64)
-            xt, st_ = _init_test_latents(y_test, np.asarray(y_train)[:, :y_test.shape[1]], use_pca, x_test_mean, x_test_var)
-            raw = torch.log(torch.expm1(st_))
-            opt = torch.optim.Adam([xt, raw], lr=learning_rate)
-            for _ in range(num_iterations):
-                sv = F.softplus(raw)
-                g_mu, g_s = DP_GP_LVM.test_latent_gradients(y_test, xt, sv)
-                xt.grad, raw.grad = -g_mu, -g_s * torch.sigmoid(raw)
-                opt.step()
-            return xt, F.softplus(raw)
+            xt, st_ = _first_columns_start(y_test, y_test.shape[1], use_pca, x_test_mean, x_test_var)
+            # (every iteration is one public test_latent_gradients call: an evaluate(), a workspace and a host round trip of q(X*))
+            return _latents.fit(functools.partial(DP_GP_LVM.test_latent_gradients, y_test), xt, st_, num_iterations, learning_rate)
 
         @staticmethod
         def predictive_marginals(x_test_mean, x_test_var, columns=None):
@@ -1176,10 +1153,10 @@ def dp_gp_lvm(y_train,
                                   reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound, out = _masked_bound(y0, obs, 'shared')
+                f_hat_test, kl_test = _latents.bound_at(bound, xt, st_)
+                pred_state['terms'] = bound.terms
                 with torch.no_grad():
-                    f_hat_test, _, _ = bound.evaluate(xt, st_)
-                    pred_state['terms'] = bound.terms
-                    lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                    lower_bound = out[1] + f_hat_test - out[2] - kl_test
                     predicted_mean, predicted_var = (_assembled_marginals if split else _marginals_at_masked)(
                         pred_state['missing_columns'], xt, st_)
                 return lower_bound, xt, torch.diag_embed(st_), predicted_mean, predicted_var
@@ -1187,10 +1164,10 @@ def dp_gp_lvm(y_train,
                 y0, obs = _masked(y_test, observed, predict=True, reference_compat=reference_compat)
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound, out = _masked_bound(y0, obs, form)
+                f_hat_test, kl_test = _latents.bound_at(bound, xt, st_)
+                pred_state['terms'] = bound.terms
                 with torch.no_grad():
-                    f_hat_test, _, _ = bound.evaluate(xt, st_)
-                    pred_state['terms'] = bound.terms
-                    lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                    lower_bound = out[1] + f_hat_test - out[2] - kl_test
                     predicted_mean, predicted_covar = _predictive_moments(pred_state['missing_columns'], xt, st_)
                     if marginal_variance:
                         predicted_covar = _marginals_at(pred_state['missing_columns'], xt, st_)[1]
@@ -1202,7 +1179,7 @@ def dp_gp_lvm(y_train,
                 'Observed dimensionality for missing data scenario must be less than total ' \
                 'dimensionality of training data.'
             do = num_observed_dims
-            xt, st_ = _init_test_latents(y_test, np.asarray(y_train)[:, :do], use_pca, x_test_mean, x_test_var)
+            xt, st_ = _first_columns_start(y_test, do, use_pca, x_test_mean, x_test_var)
             out = evaluate().clone()
             f_hat_test, kl_test = _fhat_on(_t(y_test), xt, st_, dims=do)
             lower_bound = out[1] + f_hat_test - out[2] - kl_test
@@ -1731,25 +1708,12 @@ def dp_gp_lvm_t(y_train,
         gat, aat, bat, phit, _ = _frozen()
         return _TestBoundT(x_u.detach(), gat, aat, bat, phit, y0, obs, device)
 
-    def _values(v):
-        return _t(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
-
-    def _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var):
+    def _start(y0, obs, use_pca, x_test_mean, x_test_var):
         """q(X*) at the start: the given values, or the PCA of the zero-filled test rows, or the training latent mean of the
         nearest training row over the jointly observed columns plus N(0, 0.01^2) noise; variances 1 unless given."""
-        n_t = y0.shape[0]
-        if x_test_mean is not None:
-            init = _values(x_test_mean).reshape(n_t, num_latent_dims)
-        elif use_pca:
-            init = _t(pca(y0, num_latent_dimensions=num_latent_dims))
-        elif train_obs is None:
-            init = _t(_missing.masked_nearest_neighbour_init(np.asarray(y_train), y0, obs, x_mean.detach().cpu().numpy()))
-        else:
-            init = _t(_missing.jointly_observed_nearest_neighbour_init(np.asarray(y_train), train_obs, y0, obs,
-                                                                       x_mean.detach().cpu().numpy()))
-        var = _values(x_test_var).reshape(n_t, num_latent_dims) if x_test_var is not None else \
-            torch.ones((n_t, num_latent_dims), dtype=TORCH_DTYPE, device=device)
-        return init, var
+        return _latents.start(
+            y0.shape[0], num_latent_dims, device, x_test_mean, x_test_var, use_pca, y0,
+            lambda: _latents.masked_neighbour(np.asarray(y_train), train_obs, y0, obs, x_mean.detach().cpu().numpy()))
 
     def _moments():
         """The training side of the predictive moments (frozen_bound_t._MomentsT), formed once per call."""
@@ -1847,13 +1811,12 @@ def dp_gp_lvm_t(y_train,
             y0, obs = _test_arguments(y_test, None)
             assert np.shape(y_test)[1] == num_dimensions, \
                 'Observed dimensionality for prediction must be equal to the dimensionality of the training data.'
-            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            xt, st_ = _start(y0, obs, use_pca, x_test_mean, x_test_var)
             out = evaluate()[0].clone()                                           # (objective, f_hat, KL, DP, hyper)
             bound = _test_bound(y0, obs)
-            with torch.no_grad():
-                f_hat_test, _, _ = bound.evaluate(xt, st_)
-                pred_state['terms'] = bound.terms
-                test_ll = f_hat_test - ops.kl_qx(xt, st_)
+            f_hat_test, kl_test = _latents.bound_at(bound, xt, st_)
+            pred_state['terms'] = bound.terms
+            test_ll = f_hat_test - kl_test
             return out[1] - out[2] + test_ll, xt, torch.diag_embed(st_), test_ll
 
         @staticmethod
@@ -1861,12 +1824,13 @@ def dp_gp_lvm_t(y_train,
             """d (f_hat* - KL(q(X*))) / d (x_test_mean, x_test_var) with the trained model fixed.  y_test [N* x Do] (the first
             Do <= D output dims), or [N* x D] with a boolean mask `observed` of any pattern (entries where it is False are ignored
             and may be NaN; True everywhere is allowed here)."""
-            bound = _test_bound(*_test_arguments(y_test, observed))
-            xt, st_ = _values(x_test_mean), _values(x_test_var)
+            y0, obs = _test_arguments(y_test, observed)
+            bound = _test_bound(y0, obs)
             with torch.no_grad():
-                _, dmu, ds = bound.evaluate(xt, st_, grad=True)
+                grads = _latents.ascent_gradient(bound, _latents.latent_values(x_test_mean, device, num_latent_dims, y0.shape[0]),
+                                                 _latents.latent_values(x_test_var, device, num_latent_dims, y0.shape[0]))
                 pred_state['terms'] = bound.terms
-            return dmu - xt, ds - 0.5 * (1.0 - 1.0 / st_)                        # minus the KL gradient
+            return grads
 
         @staticmethod
         def optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
@@ -1875,18 +1839,12 @@ def dp_gp_lvm_t(y_train,
             x_test_var) to hand to predict_*.  The frozen bound is formed once and nothing is read back on the host inside the
             loop.  observed: as test_latent_gradients; the start is then the masked nearest neighbour."""
             y0, obs = _test_arguments(y_test, observed)
-            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            xt, st_ = _start(y0, obs, use_pca, x_test_mean, x_test_var)
             bound = _test_bound(y0, obs)
-            raw = torch.log(torch.expm1(st_))
-            opt = torch.optim.Adam([xt, raw], lr=learning_rate)
             with torch.no_grad():
-                for _ in range(num_iterations):
-                    sv = F.softplus(raw)
-                    _, g_mu, g_s = bound.evaluate(xt, sv, grad=True)
-                    xt.grad, raw.grad = -(g_mu - xt), -(g_s - 0.5 * (1.0 - 1.0 / sv)) * torch.sigmoid(raw)
-                    opt.step()
+                fitted = _latents.fit(functools.partial(_latents.ascent_gradient, bound), xt, st_, num_iterations, learning_rate)
                 pred_state['terms'] = bound.terms
-                return xt, F.softplus(raw)
+                return fitted
 
         @staticmethod
         def predictive_marginals(x_test_mean, x_test_var, columns=None):
@@ -1896,7 +1854,8 @@ def dp_gp_lvm_t(y_train,
             0 and variance sum_t phi_td (alpha_t + 1 / beta_t)."""
             cols = _columns_arg(columns)
             with torch.no_grad():
-                return _moments().at(_values(x_test_mean), _values(x_test_var), cols)
+                return _moments().at(_latents.latent_values(x_test_mean, device, num_latent_dims),
+                                     _latents.latent_values(x_test_var, device, num_latent_dims), cols)
 
         @staticmethod
         def frozen_predictor(columns=None):
@@ -1993,14 +1952,14 @@ def dp_gp_lvm_t(y_train,
             cannot say how sure the model is about one filled-in value.  The per-entry variance needs each test point's own
             Psi2*, contracted on the fly by ops.qx_psi_pointwise; the reference has no working over-T prediction to mirror."""
             y0, obs = _test_arguments(y_test, observed, predict=True)
-            xt, st_ = _init_test_latents(y0, obs, use_pca, x_test_mean, x_test_var)
+            xt, st_ = _start(y0, obs, use_pca, x_test_mean, x_test_var)
             out = evaluate()[0].clone()
             bound = _test_bound(y0, obs)
             pred_state['missing_columns'] = _missing.missing_columns(obs)
+            f_hat_test, kl_test = _latents.bound_at(bound, xt, st_)
+            pred_state['terms'] = bound.terms
             with torch.no_grad():
-                f_hat_test, _, _ = bound.evaluate(xt, st_)
-                pred_state['terms'] = bound.terms
-                lower_bound = out[1] + f_hat_test - out[2] - ops.kl_qx(xt, st_)
+                lower_bound = out[1] + f_hat_test - out[2] - kl_test
                 mean, var = _moments().at(xt, st_, _columns_arg(pred_state['missing_columns']))
             return lower_bound, xt, torch.diag_embed(st_), mean, var
 

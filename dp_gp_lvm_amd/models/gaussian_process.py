@@ -12,6 +12,7 @@ builds a one-atom ``dp_gp_lvm_t`` (library operators for the forward, its autogr
 (constant) DP terms.  The reference's stochastic variant (``num_latent_samples > 0``: Monte-Carlo psi statistics through
 tensorflow_probability) is not built.
 """
+import functools
 import math
 
 import numpy as np
@@ -32,7 +33,7 @@ from ..utils.types import TORCH_DTYPE, default_device, inverse_softplus
 from .interfaces.trainable import Trainable
 from .frozen_bound import _TestBound, _as_device, kernel_slots
 from .masked_bound import MaskedBayesianGPLVM, MaskedMRD, _MaskedBound, _MaskedViewsBound
-from . import collapsed, marginals as _marginals, predictor as _predictor
+from . import collapsed, marginals as _marginals, predictor as _predictor, test_latents as _latents
 from .latent_geometry import LatentGeometry, ViewsLatentGeometry
 
 
@@ -185,43 +186,6 @@ def _gaussian_process(x_raw, y, raw, x_name, device):
                 return raw[x_name]
         return GPLVM()
     return GaussianProcess()
-
-
-def _kl_test(mu, s):
-    """KL(q(X*) || N(0, I)) (gp_expressions.py:10-24) and its gradient with respect to (mu, s)."""
-    return ops.kl_qx(mu, s), mu, 0.5 * (1.0 - 1.0 / s)
-
-
-def _init_test_latents(y_ref, y_test, x_train_mean, num_latent_dims, use_pca, x_test_mean, x_test_var, device):
-    """q(X*) as gaussian_process.py:346-360: mean from the PCA of y_test, or from the nearest training neighbour (L2 over the given
-    columns, utils/expressions.py:28-44) plus N(0, 0.01^2) noise; variances 1 — unless values are handed in."""
-    n_t = y_test.shape[0]
-    if x_test_mean is not None:
-        init = np.asarray(x_test_mean.detach().cpu() if torch.is_tensor(x_test_mean) else x_test_mean, dtype=np.float64)
-    elif use_pca:
-        init = pca(y_test, num_latent_dimensions=num_latent_dims)
-    else:
-        d2 = ((y_ref[:, None, :] - y_test[None, :, :]) ** 2).sum(-1)
-        init = x_train_mean.detach().cpu().numpy()[np.argmin(d2, axis=0)] + \
-            np.random.normal(scale=0.01, size=(n_t, num_latent_dims))
-    if x_test_var is not None:
-        var = np.asarray(x_test_var.detach().cpu() if torch.is_tensor(x_test_var) else x_test_var, dtype=np.float64)
-    else:
-        var = np.ones((n_t, num_latent_dims))
-    return _as_device(init, device, (n_t, num_latent_dims)), _as_device(var, device, (n_t, num_latent_dims))
-
-
-def _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate):
-    """Adam on q(X*) (mean, softplus-parametrised variances) ascending the bound whose gradient grad_fn(mu, s) returns; no host
-    reads inside the loop."""
-    xt = xt.clone()
-    raw = torch.log(torch.expm1(st_))
-    opt = torch.optim.Adam([xt, raw], lr=learning_rate)
-    for _ in range(num_iterations):
-        g_mu, g_s = grad_fn(xt, F.softplus(raw))
-        xt.grad, raw.grad = -g_mu, -g_s * torch.sigmoid(raw)
-        opt.step()
-    return xt.detach(), F.softplus(raw).detach()
 
 
 def _predictive_moments(bound_u, c_index, x_mean, s_train, y_train_u, xt, st_):
@@ -397,10 +361,12 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
     def _init_latents(do, y_test, use_pca, x_test_mean, x_test_var):
         """q(X*) for test points observed in their first `do` output dims; on a mask-trained model the nearest neighbour
         compares over the columns that the training row observed too."""
-        if train_obs is not None and x_test_mean is None and not use_pca:
-            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(
-                y_np[:, :do], train_obs[:, :do], y_test, np.ones(y_test.shape, dtype=bool), raw['x_mean'].detach().cpu().numpy())
-        return _init_test_latents(y_np[:, :do], y_test, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
+        def neighbour():
+            xm = raw['x_mean'].detach().cpu().numpy()
+            if train_obs is None:
+                return _latents.l2_neighbour(y_np[:, :do], y_test, xm)
+            return _latents.masked_neighbour(y_np[:, :do], train_obs[:, :do], y_test, np.ones(y_test.shape, dtype=bool), xm)
+        return _latents.start(y_test.shape[0], num_latent_dims, dev_, x_test_mean, x_test_var, use_pca, y_test, neighbour)
 
     def _frozen():
         """The trained kernel as a B = 1 test bound's parameters (fp64 values of the raw variables)."""
@@ -432,12 +398,9 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         return bound
 
     def _masked_init(y0, obs, use_pca, x_test_mean, x_test_var):
-        if x_test_mean is None and not use_pca and train_obs is not None:
-            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(y_np, train_obs, y0, obs,
-                                                                           raw['x_mean'].detach().cpu().numpy())
-        elif x_test_mean is None and not use_pca:
-            x_test_mean = _missing.masked_nearest_neighbour_init(y_np, y0, obs, raw['x_mean'].detach().cpu().numpy())
-        return _init_test_latents(None, y0, raw['x_mean'], num_latent_dims, use_pca, x_test_mean, x_test_var, dev_)
+        return _latents.start(
+            y0.shape[0], num_latent_dims, dev_, x_test_mean, x_test_var, use_pca, y0,
+            lambda: _latents.masked_neighbour(y_np, train_obs, y0, obs, raw['x_mean'].detach().cpu().numpy()))
 
     def _check_observed(y_test, full):
         y_test = np.asarray(y_test, dtype=np.float64)
@@ -456,11 +419,9 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
         return t_[1], t_[2]
 
     def _bound_at(y_test, xt, st_):
-        bound = _test_bound(y_test)
+        f_test, kl_t = _latents.bound_at(_test_bound(y_test), xt, st_)
         with torch.no_grad():
-            f_test, _, _ = bound.evaluate(xt, st_)
             f_hat, kl = _train_terms()
-            kl_t = ops.kl_qx(xt, st_)
         return f_hat, kl, f_test, kl_t
 
     def _test_latent_gradients(y_test, x_test_mean, x_test_var, observed=None):
@@ -470,11 +431,9 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             y_test = np.asarray(y_test, dtype=np.float64)
             assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
             bound = _test_bound(y_test)
-        xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
         with torch.no_grad():
-            _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
-            _, k_mu, k_s = _kl_test(xt, st_)
-        return d_mu - k_mu, d_s - k_s
+            return _latents.ascent_gradient(bound, _latents.latent_values(x_test_mean, dev_, num_latent_dims, bound.n_t),
+                                            _latents.latent_values(x_test_var, dev_, num_latent_dims, bound.n_t))
 
     def _optimise_test_latents(y_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None, x_test_var=None,
                                observed=None):
@@ -487,12 +446,8 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
             assert y_test.ndim == 2 and y_test.shape[1] <= num_dimensions, 'y_test must be [N* x Do], Do <= D'
             xt, st_ = _init_latents(y_test.shape[1], y_test, use_pca, x_test_mean, x_test_var)
             bound = _test_bound(y_test)
-
-        def grad_fn(mu, s):
-            _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
-            return d_mu - mu, d_s - 0.5 * (1.0 - 1.0 / s)
         with torch.no_grad():
-            return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
+            return _latents.fit(functools.partial(_latents.ascent_gradient, bound), xt.clone(), st_, num_iterations, learning_rate)
 
     def _train_marginals():
         """The training side of the per-entry moments (models/marginals.py), formed once per call: the model's own masked bound,
@@ -640,10 +595,9 @@ def bayesian_gp_lvm(y_train, kernel=None, num_latent_dims=GP_LVM_DEFAULT_LATENT_
                 xt, st_ = _masked_init(y0, obs, use_pca, x_test_mean, x_test_var)
                 bound = _masked_bound(y0, obs)
                 mc = pred_state['missing_columns']
+                f_test, kl_t = _latents.bound_at(bound, xt, st_)
                 with torch.no_grad():
-                    f_test, _, _ = bound.evaluate(xt, st_)
                     f_hat, kl = _train_terms()
-                    kl_t = ops.kl_qx(xt, st_)
                     z, g, a, b = _frozen()
                     plain = _TestBound.kernels(z, g, a, b, [torch.zeros((y0.shape[0], 1), dtype=TORCH_DTYPE, device=dev_)], dev_)
                     means, covars = _predictive_moments(plain, [0], raw['x_mean'].detach(), F.softplus(raw['x_var']).detach(),
@@ -925,22 +879,21 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
         return views_test
 
     def _bound_at(views_test, xt, st_):
-        bound = _test_bound(views_test)
+        f_test, kl_t = _latents.bound_at(_test_bound(views_test), xt, st_)
         with torch.no_grad():
-            f_test, _, _ = bound.evaluate(xt, st_)
             f_hat, kl = _train_terms()
-            kl_t = ops.kl_qx(xt, st_)
         return f_hat + f_test - kl - kl_t
 
     def _init(views_test, use_pca, x_test_mean, x_test_var):
-        vo = len(views_test)
-        if masked is not None and x_test_mean is None and not use_pca:
-            y_t = np.hstack(views_test)
-            x_test_mean = _missing.jointly_observed_nearest_neighbour_init(
-                np.hstack(views_np[:vo]), np.hstack(train_obs[:vo]), y_t, np.ones(y_t.shape, dtype=bool),
-                x_mean_t.detach().cpu().numpy())
-        return _init_test_latents(np.hstack(views_np[:vo]), np.hstack(views_test), x_mean_t, q, use_pca, x_test_mean,
-                                  x_test_var, dev_)
+        vo, y_t = len(views_test), np.hstack(views_test)
+
+        def neighbour():
+            xm = x_mean_t.detach().cpu().numpy()
+            if masked is None:
+                return _latents.l2_neighbour(np.hstack(views_np[:vo]), y_t, xm)
+            return _latents.masked_neighbour(np.hstack(views_np[:vo]), np.hstack(train_obs[:vo]), y_t,
+                                             np.ones(y_t.shape, dtype=bool), xm)
+        return _latents.start(y_t.shape[0], q, dev_, x_test_mean, x_test_var, use_pca, y_t, neighbour)
 
     def _masked(views_test, observed, predict=False, reference_compat=False):
         """The argument checks of the observed= paths; returns (the V test views zero-filled where unobserved, the V masks)."""
@@ -977,29 +930,22 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
 
     def _masked_init(y0s, obs, use_pca, x_test_mean, x_test_var):
         y_t, o_t = np.hstack(y0s), np.hstack(obs)
-        if x_test_mean is None and not use_pca:
-            xm = x_mean_t.detach().cpu().numpy()
-            x_test_mean = _missing.masked_nearest_neighbour_init(np.hstack(views_np), y_t, o_t, xm) if masked is None else \
-                _missing.jointly_observed_nearest_neighbour_init(np.hstack(views_np), np.hstack(train_obs), y_t, o_t, xm)
-        return _init_test_latents(None, y_t, x_mean_t, q, use_pca, x_test_mean, x_test_var, dev_)
+        return _latents.start(
+            y_t.shape[0], q, dev_, x_test_mean, x_test_var, use_pca, y_t,
+            lambda: _latents.masked_neighbour(np.hstack(views_np), None if masked is None else np.hstack(train_obs), y_t, o_t,
+                                              x_mean_t.detach().cpu().numpy()))
 
     def _test_latent_gradients(views_test, x_test_mean, x_test_var, observed=None):
         if observed is not None:
             bound = _masked_bound(*_masked(views_test, observed))
-            xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
-            with torch.no_grad():
-                _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
-                _, k_mu, k_s = _kl_test(xt, st_)
-            return d_mu - k_mu, d_s - k_s
-        views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
-        assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
-            'views_test must be the first Vo <= V views, each [N* x D_v]'
-        bound = _test_bound(views_test)
-        xt, st_ = _as_device(x_test_mean, dev_), _as_device(x_test_var, dev_)
+        else:
+            views_test = [np.asarray(v, dtype=np.float64) for v in views_test]
+            assert 0 < len(views_test) <= num_views and [v.shape[1] for v in views_test] == num_dimensions[:len(views_test)], \
+                'views_test must be the first Vo <= V views, each [N* x D_v]'
+            bound = _test_bound(views_test)
         with torch.no_grad():
-            _, d_mu, d_s = bound.evaluate(xt, st_, grad=True)
-            _, k_mu, k_s = _kl_test(xt, st_)
-        return d_mu - k_mu, d_s - k_s
+            return _latents.ascent_gradient(bound, _latents.latent_values(x_test_mean, dev_, q, bound.n_t),
+                                            _latents.latent_values(x_test_var, dev_, q, bound.n_t))
 
     def _optimise_test_latents(views_test, num_iterations=200, learning_rate=0.01, use_pca=False, x_test_mean=None,
                                x_test_var=None, observed=None):
@@ -1013,12 +959,8 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                 'views_test must be the first Vo <= V views, each [N* x D_v]'
             xt, st_ = _init(views_test, use_pca, x_test_mean, x_test_var)
             bound = _test_bound(views_test)
-
-        def grad_fn(mu, s):
-            _, d_mu, d_s = bound.evaluate(mu, s, grad=True)
-            return d_mu - mu, d_s - 0.5 * (1.0 - 1.0 / s)
         with torch.no_grad():
-            return _adam_test_latents(grad_fn, xt, st_, num_iterations, learning_rate)
+            return _latents.fit(functools.partial(_latents.ascent_gradient, bound), xt.clone(), st_, num_iterations, learning_rate)
 
     def _train_marginals():
         """The training side of the per-entry moments of every view (models/marginals.py), formed once per call: the model's own
@@ -1181,10 +1123,9 @@ def manifold_relevance_determination(views_train, num_latent_dims=GP_LVM_DEFAULT
                 xt, st_ = _masked_init(y0s, obs, use_pca, x_test_mean, x_test_var)
                 bound = _masked_bound(y0s, obs)
                 mv_, mc = pred_state['missing_views'], pred_state['missing_columns']
+                f_test, kl_t = _latents.bound_at(bound, xt, st_)
                 with torch.no_grad():
-                    f_test, _, _ = bound.evaluate(xt, st_)
                     f_hat, kl = _train_terms()
-                    kl_t = ops.kl_qx(xt, st_)
                     bound_u = _TestBound.kernels(*_frozen([inner[v] for v in mv_]),
                                                  [torch.zeros((1, 1), dtype=TORCH_DTYPE, device=dev_)] * len(mv_), dev_)
                     means, covars = _predictive_moments(bound_u, list(range(len(mv_))), x_mean_t.detach(),
