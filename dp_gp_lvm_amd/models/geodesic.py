@@ -22,6 +22,10 @@ exact derivative of exp_map's discrete map) on `accel_tangent`, a callable (x, v
 (marginals.Metric.accel_tangent on ops.ard_rbf_point_christoffel_tangent and ops.geodesic_accel_tangent), and log_map is Newton
 shooting on it: one batched tangent shot over C Q rows per iteration.
 
+The Runge-Kutta loops of exp_map, exp_map_tangent and log_map run here, in Python, a stage being a handful of launches; each takes
+`shoot`, a callable that returns the loop's results from elsewhere: marginals.Metric.shoot / shoot_tangent, ONE call of
+ops.geodesic_shoot[_tangent] per shot, with the loop's bits (a model's integrator = 'device').
+
 The three callables are the methods of ONE marginals.Metric, the metric that a public call runs under; the models' public methods
 on them are written once, in models/latent_geometry.py.
 """
@@ -167,39 +171,48 @@ def geodesic_acceleration(accel, x, v, q, device):
     return a[0] if single else a
 
 
-def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False):
+def _rk4(accel, xs, vs, num_steps):
+    """(curve, vel [C x S+1 x Q], bad [C] int32): the classical RK4 steps of exp_map on the states xs, vs [C x Q]; bad counts the
+    stages whose metric failed to factor.  Nothing is read on the host."""
+    c, q, h = xs.shape[0], xs.shape[1], 1.0 / num_steps
+    curve = torch.empty((c, num_steps + 1, q), dtype=xs.dtype, device=xs.device)
+    vel = torch.empty_like(curve)
+    bad = torch.zeros(c, dtype=torch.int32, device=xs.device)
+
+    def f(xx, vv):
+        nonlocal bad
+        a, _, info = accel(xx, vv)
+        bad = bad + (info != 0).to(torch.int32)
+        return a
+
+    curve[:, 0], vel[:, 0] = xs, vs
+    for s in range(num_steps):
+        k1x, k1v = vs, f(xs, vs)
+        k2x = vs + (0.5 * h) * k1v
+        k2v = f(xs + (0.5 * h) * k1x, k2x)
+        k3x = vs + (0.5 * h) * k2v
+        k3v = f(xs + (0.5 * h) * k2x, k3x)
+        k4x = vs + h * k3v
+        k4v = f(xs + h * k3x, k4x)
+        xs = xs + (h / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x)
+        vs = vs + (h / 6.0) * (k1v + 2.0 * k2v + 2.0 * k3v + k4v)
+        curve[:, s + 1], vel[:, s + 1] = xs, vs
+    return curve, vel, bad
+
+
+def exp_map(accel, x, v, q, device, num_steps=64, return_velocity=False, shoot=None):
     """curve [C x S+1 x Q] (one curve [S+1 x Q] for x, v [Q]), S = num_steps: the exponential map of v at x, the classical RK4
     solution of (x', v') = (v, accel(x, v)) on t in [0, 1] at step 1 / S, all C curves in one batch; row 0 holds the bits of x.
     With return_velocity also the velocities in the same shape.  Four calls of accel per step plus element-wise work; nothing is
     read on the host until ONE read of the accumulated info at the end: FloatingPointError if the metric failed to factor at
-    any stage of any curve."""
+    any stage of any curve.  shoot: None, or a callable (xs, vs [C x Q], num_steps) -> (curve, vel, bad) that takes the place of
+    the loop on accel (marginals.Metric.shoot, the integrator on the device: the same bits)."""
     (xs, vs), single = states_arg(q, device, x=x, v=v)
     num_steps = int(num_steps)
     assert num_steps >= 1, 'num_steps >= 1'
-    c, h = xs.shape[0], 1.0 / num_steps
+    c = xs.shape[0]
     with torch.no_grad():
-        curve = torch.empty((c, num_steps + 1, q), dtype=xs.dtype, device=xs.device)
-        vel = torch.empty_like(curve)
-        bad = torch.zeros(c, dtype=torch.int32, device=xs.device)
-
-        def f(xx, vv):
-            nonlocal bad
-            a, _, info = accel(xx, vv)
-            bad = bad + (info != 0).to(torch.int32)
-            return a
-
-        curve[:, 0], vel[:, 0] = xs, vs
-        for s in range(num_steps):
-            k1x, k1v = vs, f(xs, vs)
-            k2x = vs + (0.5 * h) * k1v
-            k2v = f(xs + (0.5 * h) * k1x, k2x)
-            k3x = vs + (0.5 * h) * k2v
-            k3v = f(xs + (0.5 * h) * k2x, k3x)
-            k4x = vs + h * k3v
-            k4v = f(xs + h * k3x, k4x)
-            xs = xs + (h / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x)
-            vs = vs + (h / 6.0) * (k1v + 2.0 * k2v + 2.0 * k3v + k4v)
-            curve[:, s + 1], vel[:, s + 1] = xs, vs
+        curve, vel, bad = _rk4(accel, xs, vs, num_steps) if shoot is None else shoot(xs, vs, num_steps)
         failed = int(torch.count_nonzero(bad))
         if failed:
             raise FloatingPointError('latent_exp_map: the metric failed to factor (not positive definite in fp64) along %d of %d '
@@ -256,17 +269,20 @@ def _rk4_tangent(accel_tangent, xs, vs, dxs, dvs, num_steps):
     return curve, vel, dcurve, dvel, bad, speed0
 
 
-def exp_map_tangent(accel_tangent, x, v, dx, dv, q, device, num_steps=64, return_velocity=False):
+def exp_map_tangent(accel_tangent, x, v, dx, dv, q, device, num_steps=64, return_velocity=False, shoot=None):
     """(curve, dcurve) [C x S+1 x Q] (single curves [S+1 x Q] for x, v, dx, dv [Q]): exp_map's curve, with its bits, and the
     tangent-linear classical RK4 solution started at (dx, dv): the EXACT derivative of exp_map's discrete map along that direction
     of (x, v), a discrete Jacobi field.  With return_velocity (curve, dcurve, velocity, dvelocity).  Four calls of accel_tangent
     per step plus element-wise work; the stages' info is accumulated on the device and read ONCE at the end:
-    FloatingPointError if the metric failed to factor at any stage of any curve."""
+    FloatingPointError if the metric failed to factor at any stage of any curve.  shoot: None, or a callable
+    (xs, vs, dxs, dvs [C x Q], num_steps) -> _rk4_tangent's six results that takes its place (marginals.Metric.shoot_tangent,
+    the integrator on the device: the same bits)."""
     (xs, vs, dxs, dvs), single = states_arg(q, device, x=x, v=v, dx=dx, dv=dv)
     num_steps = int(num_steps)
     assert num_steps >= 1, 'num_steps >= 1'
     with torch.no_grad():
-        curve, vel, dcurve, dvel, bad, _ = _rk4_tangent(accel_tangent, xs, vs, dxs, dvs, num_steps)
+        curve, vel, dcurve, dvel, bad, _ = _rk4_tangent(accel_tangent, xs, vs, dxs, dvs, num_steps) if shoot is None else \
+            shoot(xs, vs, dxs, dvs, num_steps)
         failed = int(torch.count_nonzero(bad))
         if failed:
             raise FloatingPointError('latent_exp_map_tangent: the metric failed to factor (not positive definite in fp64) along '
@@ -292,7 +308,7 @@ def _small_solve(a, b):
     return w[:, :, q].contiguous()
 
 
-def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations=20, tol=1e-10, init=None):
+def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations=20, tol=1e-10, init=None, shoot=None):
     """(v [C x Q], distance [C], curve [C x S+1 x Q], residual [C]) (unbatched shapes for one pair): the logarithm map of x_to at
     x_from, the initial velocity whose exp_map at num_steps steps ends in x_to, by Newton shooting on the discrete map; distance =
     sqrt(v^T G(x_from) v), curve = exp_map(x_from, v), residual = |curve end - x_to|.
@@ -307,7 +323,7 @@ def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations
     max_iterations proposals are made and judged (1 + max_iterations shots); the loop ends early once every accepted residual is
     <= tol max(1, |x_to|).  ONE host read per iteration, of that test.  A curve whose residual stays above it is reported through
     `residual`, not raised; FloatingPointError only if the very first shot fails to factor.  The base features are recomputed for
-    each of the Q directions."""
+    each of the Q directions.  shoot: as exp_map_tangent's; it fires every shot in the place of _rk4_tangent."""
     (a, b), single = states_arg(q, device, x_from=x_from, x_to=x_to)
     num_steps, max_iterations = int(num_steps), int(max_iterations)
     assert num_steps >= 1 and max_iterations >= 0, 'num_steps >= 1 and max_iterations >= 0'
@@ -321,8 +337,9 @@ def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations
         unit = torch.eye(q, dtype=a.dtype, device=a.device).repeat(c, 1)
         lam = torch.ones(c, dtype=a.dtype, device=a.device)
         best = None                                           # (v, residual, step, curve, speed) of the accepted iterate
+        fire = (lambda *state: _rk4_tangent(accel_tangent, *state)) if shoot is None else shoot
         for it in range(max_iterations + 1):
-            curve, _, dcurve, _, bad, speed = _rk4_tangent(accel_tangent, xs, rep(v), zero, unit, num_steps)
+            curve, _, dcurve, _, bad, speed = fire(xs, rep(v), zero, unit, num_steps)
             base = curve.reshape(c, q, num_steps + 1, q)[:, 0]
             res = base[:, -1] - b
             norm = torch.linalg.vector_norm(res, dim=1)

@@ -17,7 +17,34 @@ from . import geodesic as _geodesic
 from . import marginals as _marginals
 
 
-class LatentGeometry:
+def _shoot_of(metric, where, tangent=False):
+    """The `shoot` of models/geodesic.py's integrating functions for a model's integrator `where`: 'host' (None: their own loop,
+    a stage is a handful of launches from Python) or 'device' (the metric's shoot / shoot_tangent: ops.geodesic_shoot[_tangent],
+    every stage of every step from one C call, the same bits)."""
+    if where == 'host':
+        return None
+    return metric.shoot_tangent if tangent else metric.shoot
+
+
+class _Integrator:
+    """The attribute `integrator` of a model: where the Runge-Kutta loops of latent_exp_map, latent_exp_map_tangent and
+    latent_log_map run.  'host' (the default: the Python loops of models/geodesic.py) or 'device' (the same steps, to the same
+    bits, from one C call per shot); assigning anything else raises ValueError.  An attribute and not a keyword
+    of the three methods: their signatures are pinned."""
+    _integrator = 'host'
+
+    @property
+    def integrator(self):
+        return self._integrator
+
+    @integrator.setter
+    def integrator(self, value):
+        if value not in ('host', 'device'):
+            raise ValueError("integrator must be 'host' or 'device', got %r" % (value,))
+        self._integrator = value
+
+
+class LatentGeometry(_Integrator):
     """The methods of a model whose geometry calls choose output dims by columns= (default: all D).  _metric_of(columns, name):
     the checks of `columns`, the training side and the Metric under latent_metric(., columns), formed once per call; `name` is
     the public method's, for a refusal's text.  _require_built(name) raises where a model in its current state builds none of
@@ -71,9 +98,11 @@ class LatentGeometry:
         curve_energy, curve_length, predictive_marginals and sample_functions take.  With return_velocity also the
         velocities, in the same shape.  A stage is one call of ops.ard_rbf_point_christoffel and one of ops.geodesic_accel
         plus element-wise work; the training side is built once per call; one host read at the end: FloatingPointError if the
-        metric failed to factor at any stage.  fp64, torch.no_grad."""
+        metric failed to factor at any stage.  With self.integrator = 'device' the same steps run, to the same bits, inside ONE
+        call of ops.geodesic_shoot.  fp64, torch.no_grad."""
         metric = self._metric_of(columns, 'latent_exp_map')
-        return _geodesic.exp_map(metric.accel, x, v, self._latent_dims, self._device, num_steps, return_velocity)
+        return _geodesic.exp_map(metric.accel, x, v, self._latent_dims, self._device, num_steps, return_velocity,
+                                 shoot=_shoot_of(metric, self.integrator))
 
     def geodesic_deviation(self, x, v, dx, dv, columns=None):
         """(a, da) [N* x Q] (or [Q]): geodesic_acceleration(x, v, columns), with its bits, and its derivative along the
@@ -88,10 +117,10 @@ class LatentGeometry:
         bits, and the discrete Jacobi field started at (dx, dv): the tangent-linear RK4, the exact derivative of
         latent_exp_map's discrete map along that direction (models/geodesic.exp_map_tangent).  With return_velocity
         (curve, dcurve, velocity, dvelocity).  One host read at the end: FloatingPointError if the metric failed to factor at
-        any stage.  Q <= 31.  fp64, torch.no_grad."""
+        any stage.  self.integrator: as latent_exp_map ('device': ops.geodesic_shoot_tangent).  Q <= 31.  fp64, torch.no_grad."""
         metric = self._metric_of(columns, 'latent_exp_map_tangent')
         return _geodesic.exp_map_tangent(metric.accel_tangent, x, v, dx, dv, self._latent_dims, self._device, num_steps,
-                                         return_velocity)
+                                         return_velocity, shoot=_shoot_of(metric, self.integrator, True))
 
     def latent_log_map(self, x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, columns=None, init=None):
         """(v [C x Q], distance [C], curve [C x num_steps+1 x Q], residual [C]) (unbatched for x_from, x_to [Q]): the
@@ -99,13 +128,14 @@ class LatentGeometry:
         Newton shooting on the discrete map with latent_exp_map_tangent's exact Jacobian, step halving on a residual that
         does not fall, the best iterate kept (models/geodesic.log_map).  distance = sqrt(v^T G(x_from) v); residual =
         |curve end - x_to|, converged where it is <= tol max(1, |x_to|); a curve that is not is reported through residual,
-        not raised.  An iteration is ONE batched shot over C Q rows and one host read.  Q <= 31.  fp64, torch.no_grad."""
+        not raised.  An iteration is ONE batched shot over C Q rows and one host read; self.integrator = 'device' fires every shot
+        through ops.geodesic_shoot_tangent, as latent_exp_map_tangent's.  Q <= 31.  fp64, torch.no_grad."""
         metric = self._metric_of(columns, 'latent_log_map')
         return _geodesic.log_map(metric.accel_tangent, x_from, x_to, self._latent_dims, self._device, num_steps, max_iterations,
-                                 tol, init)
+                                 tol, init, shoot=_shoot_of(metric, self.integrator, True))
 
 
-class ViewsLatentGeometry:
+class ViewsLatentGeometry(_Integrator):
     """The methods of manifold_relevance_determination: one result per view of `views` (default: all V, in order), each under the
     view's own latent_metric, or, with total=True, ONE result under the summed metric latent_metric(., views, total=True).
     _metrics_of(views, total): the check of `views`, the training side of all views and the Metrics, one per view or the one of
@@ -152,9 +182,10 @@ class ViewsLatentGeometry:
         """One curve [C x num_steps+1 x Q] (or [num_steps+1 x Q]; with return_velocity one pair (curve, velocities)) per view
         of `views`: the view's own exponential map, as bayesian_gp_lvm.latent_exp_map under the view's latent_metric;
         total=True: one result, under the summed metric (a stage is then one ops.ard_rbf_point_christoffel call per view and
-        one ops.geodesic_accel).  The training side of all views is built once per call."""
+        one ops.geodesic_accel).  The training side of all views is built once per call.  self.integrator: 'host' or 'device', as
+        bayesian_gp_lvm's (the summed metric's views are the parts of one ops.geodesic_shoot call)."""
         return self._per_metric(views, total, lambda m: _geodesic.exp_map(
-            m.accel, x, v, self._latent_dims, self._device, num_steps, return_velocity))
+            m.accel, x, v, self._latent_dims, self._device, num_steps, return_velocity, shoot=_shoot_of(m, self.integrator)))
 
     def geodesic_deviation(self, x, v, dx, dv, views=None, total=False):
         """One pair (a, da) per view of `views` (default: all V, in order), as bayesian_gp_lvm.geodesic_deviation under the
@@ -166,13 +197,16 @@ class ViewsLatentGeometry:
     def latent_exp_map_tangent(self, x, v, dx, dv, num_steps=64, views=None, total=False, return_velocity=False):
         """One result (curve, dcurve[, velocity, dvelocity]) per view of `views`, as bayesian_gp_lvm.latent_exp_map_tangent
         under the view's latent_metric; total=True: one result, under the summed metric (a stage is then one
-        ops.ard_rbf_point_christoffel_tangent call per view and one ops.geodesic_accel_tangent)."""
+        ops.ard_rbf_point_christoffel_tangent call per view and one ops.geodesic_accel_tangent).  self.integrator: as
+        latent_exp_map."""
         return self._per_metric(views, total, lambda m: _geodesic.exp_map_tangent(
-            m.accel_tangent, x, v, dx, dv, self._latent_dims, self._device, num_steps, return_velocity))
+            m.accel_tangent, x, v, dx, dv, self._latent_dims, self._device, num_steps, return_velocity,
+            shoot=_shoot_of(m, self.integrator, True)))
 
     def latent_log_map(self, x_from, x_to, num_steps=64, max_iterations=20, tol=1e-10, views=None, total=False, init=None):
         """One result (v, distance, curve, residual) per view of `views`: the view's own logarithm map, as
         bayesian_gp_lvm.latent_log_map under the view's latent_metric; total=True: one result, under the summed metric.
-        The training side of all views is built once per call."""
+        The training side of all views is built once per call.  self.integrator: as latent_exp_map."""
         return self._per_metric(views, total, lambda m: _geodesic.log_map(
-            m.accel_tangent, x_from, x_to, self._latent_dims, self._device, num_steps, max_iterations, tol, init))
+            m.accel_tangent, x_from, x_to, self._latent_dims, self._device, num_steps, max_iterations, tol, init,
+            shoot=_shoot_of(m, self.integrator, True)))

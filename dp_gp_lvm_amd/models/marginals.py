@@ -32,7 +32,7 @@ import torch
 from .. import ops
 from ..utils.types import TORCH_DTYPE
 from . import collapsed
-from .geodesic import prior_terms
+from .geodesic import _rk4, _rk4_tangent, prior_terms
 
 
 class _Marginals:
@@ -182,7 +182,8 @@ class Metric:
     None (only the diagonals of prior and extra are read).  No part and an extra is the prior-only metric (dp_gp_lvm with no
     chosen column observed in training).  Several parts with an extra occur nowhere and are refused.  Its three methods are the
     callables of models/geodesic.py; every one runs in blocks of points of at most 2^25 result entries, and a point's bits do not
-    depend on its block.
+    depend on its block.  shoot and shoot_tangent are the integrators on the device over accel and accel_tangent: whole
+    Runge-Kutta solutions with the bits of geodesic.py's loops, blocked over the curves in the same way.
 
     A part carries its own prior because the sums differ: the energy of several parts is formed part by part, each with its own
     prior share, and summed over the stacked parts; the acceleration hands ONE w, over all priors, to one factorisation."""
@@ -237,6 +238,30 @@ class Metric:
             return a, torch.zeros_like(v), speed, info
         return self._solve(ops.ard_rbf_point_christoffel_tangent, ops.geodesic_accel_tangent, 2,
                            (x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()))
+
+    def shoot(self, x, v, num_steps):
+        """(curve, vel [C, S+1, Q], bad [C] int32): geodesic._rk4 on accel from the states x, v [C, Q], with its bits, by the
+        integrator on the device: ONE call of ops.geodesic_shoot per block of curves (accel's points per block) runs every
+        stage of every step.  The prior-only metric takes the host loop: straight lines."""
+        if not self.parts:
+            return _rk4(self.accel, x, v, num_steps)
+        return self._shoot(ops.geodesic_shoot, 1, (x.contiguous(), v.contiguous()), num_steps)
+
+    def shoot_tangent(self, x, v, dx, dv, num_steps):
+        """(curve, vel, dcurve, dvel [C, S+1, Q], bad [C] int32, speed0 [C]): geodesic._rk4_tangent on accel_tangent, with its
+        bits, by ops.geodesic_shoot_tangent, as shoot (accel_tangent's points per block)."""
+        if not self.parts:
+            return _rk4_tangent(self.accel_tangent, x, v, dx, dv, num_steps)
+        return self._shoot(ops.geodesic_shoot_tangent, 2, (x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()),
+                           num_steps)
+
+    def _shoot(self, run, width, state, num_steps):
+        """run(the parts' operands, w, *state, num_steps) per block of the curves of state, blocked as _solve blocks a stage."""
+        parts = [(marg.z, marg.gamma, marg.alpha, p) for marg, p in self.parts]
+        n, step = state[0].shape[0], max(1, self.block // width)
+        blocks = [run(parts, self.w, *(state if step >= n else [t[i:i + step] for t in state]), num_steps)
+                  for i in range(0, n, step)]
+        return blocks[0] if len(blocks) == 1 else tuple(torch.cat(bs) for bs in zip(*blocks))
 
     def _solve(self, slabs_of, solve, width, state):
         """solve(the parts' concatenated slabs_of(state), w, v) per block of the points of state = (x, v[, dx, dv]), `width` times

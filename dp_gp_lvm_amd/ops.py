@@ -3,6 +3,8 @@ Torch-tensor front-end of the C ABI (include/dpgp.h).  PyTorch is plumbing here:
 and (in models/) torch.distributed.  Every function takes CUDA (ROCm) tensors, enqueues HIP kernels on the current
 stream and returns device tensors; nothing here computes on the host and there is no fallback.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -487,14 +489,14 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     return d_mu, d_s
 
 
-def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None):
+def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None, prior=None):
     """The checks of the five point operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
     (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M], r [K,M,J] or c [K,G,M,M], `what` its wording);
     dirs: the directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), or (v, dx, dv) of
     ard_rbf_point_christoffel_tangent, checked in their place after x; max_q: an operator's own limit on Q (ValueError, after the
-    shapes)."""
+    shapes); prior: the constant diagonal metric [Q] of geodesic_shoot, checked after `a`."""
     dirs = () if dirs is None else tuple(zip(('v', 'dx', 'dv'), dirs))
-    args = (('z', z), ('x', x)) + dirs + (('gamma', gamma), ('alpha', alpha), (name, a))
+    args = (('z', z), ('x', x)) + dirs + (('gamma', gamma), ('alpha', alpha), (name, a)) + (() if prior is None else (('prior', prior),))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % nm)
@@ -516,6 +518,8 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None)
         bad = a.dim() != 3 or a.shape[0] != k or a.shape[1] != m or a.shape[2] < 1 or (name == 'p' and a.shape[2] != m)
     if bad:
         raise ValueError('%s must be %s, got %s' % (name, what, tuple(a.shape)))
+    if prior is not None and tuple(prior.shape) != (q,):
+        raise ValueError('prior must be [Q], got %s' % (tuple(prior.shape),))
     if max_q is not None and q > max_q:
         raise ValueError('z must have Q <= %d, got Q = %d' % (max_q, q))
     for nm, v in args:
@@ -671,6 +675,76 @@ def geodesic_accel(g, gam, prior, v):
                                                   a.data_ptr(), speed.data_ptr(), info.data_ptr(), _stream()),
                'dpgp_geodesic_accel_f64')
     return a, speed, info
+
+
+def _shoot(parts, prior, states, num_steps, tangent):
+    """The checks and the call of geodesic_shoot / geodesic_shoot_tangent.  parts: a non-empty list (TypeError; at most 64,
+    ValueError) of (z [K_i,M_i,Q], gamma [K_i,Q], alpha [K_i], p [K_i,M_i,M_i]), each checked as
+    ard_rbf_point_christoffel[_tangent] checks it next to the states (x, v[, dx, dv]) [C,Q] and prior [Q]; num_steps >= 1
+    (ValueError)."""
+    if not isinstance(parts, (list, tuple)) or not parts or any(not isinstance(pt, (list, tuple)) or len(pt) != 4 for pt in parts):
+        raise TypeError('parts must be a non-empty list of (z, gamma, alpha, p)')
+    if len(parts) > 64:
+        raise ValueError('parts must have at most 64 entries, got %d' % len(parts))
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError('num_steps must be >= 1, got %d' % num_steps)
+    if prior is None:
+        raise TypeError('prior must be a float64 torch.Tensor')
+    x, dirs = states[0], tuple(states[1:])
+    kept, ks, ms, off_gpu = [], [], [], None
+    for z, gamma, alpha, p in parts:
+        try:
+            z, xc, gamma, alpha, p, k, c, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]', dirs=dirs,
+                                                                    max_q=31 if tangent else 63, prior=prior)
+        except RuntimeError as err:          # (the types and shapes of the later parts come before any part's device)
+            off_gpu = off_gpu or err
+            continue
+        kept.append((z, gamma, alpha, p))
+        ks.append(k)
+        ms.append(m)
+    if off_gpu is not None:
+        raise off_gpu
+    if any(pt[0].device != xc.device for pt in kept):
+        raise RuntimeError('every part must live on the GPU of x: dp_gp_lvm_amd runs its operators in HIP only')
+    prior = prior.contiguous()
+    states = [xc] + [d.contiguous() for d in dirs]
+    rows = [torch.empty((c, num_steps + 1, q), dtype=torch.float64, device=xc.device) for _ in states]
+    bad = torch.empty((c,), dtype=torch.int32, device=xc.device)
+    speed0 = [torch.empty((c,), dtype=torch.float64, device=xc.device)] if tangent else []
+    n = len(kept)
+    ints = ctypes.c_int * n
+    ptrs = ctypes.c_void_p * n
+    ka, ma = ints(*ks), ints(*ms)
+    lists = [ptrs(*(pt[j].data_ptr() for pt in kept)) for j in range(4)]
+    l = _lib.lib()
+    wsb = l.dpgp_geodesic_shoot_workspace_bytes(n, ka, ma, q, c, int(tangent))
+    ws = _ws(wsb, xc.device)
+    fn = 'dpgp_geodesic_shoot_tangent_f64' if tangent else 'dpgp_geodesic_shoot_f64'
+    _lib.check(getattr(l, fn)(n, ka, ma, q, c, num_steps, *lists, prior.data_ptr(), *(t.data_ptr() for t in states),
+                              *(t.data_ptr() for t in rows), bad.data_ptr(), *(t.data_ptr() for t in speed0), ws.data_ptr(), wsb,
+                              _stream()), fn)
+    return tuple(rows) + (bad,) + tuple(speed0)
+
+
+def geodesic_shoot(parts, prior, x, v, num_steps):
+    """The exponential map on the device (dpgp_geodesic_shoot_f64): the classical RK4 solution of (x', v') = (v, -G^-1 Gamma) on
+    t in [0, 1] at step 1 / num_steps for the C curves from x [C,Q] with the velocities v [C,Q], under the metric
+    G = sum over parts and their kernels of g + diag(prior): parts is a list of (z [K_i,M_i,Q], gamma [K_i,Q], alpha [K_i],
+    p [K_i,M_i,M_i]), the operands of ard_rbf_point_christoffel, prior [Q].  Returns (curve, vel [C,S+1,Q], bad [C] int32): the
+    BITS of models/geodesic.exp_map's loop on ard_rbf_point_christoffel (the parts' slabs concatenated) and geodesic_accel;
+    bad counts the stages whose metric failed to factor (NaN in that curve from there on, the others unaffected).  One C call:
+    4 S (parts + 1) launches, nothing allocated or added by torch between stages, nothing read on the host.  Q <= 63.  float64
+    tensors (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
+    return _shoot(parts, prior, (x, v), num_steps, False)
+
+
+def geodesic_shoot_tangent(parts, prior, x, v, dx, dv, num_steps):
+    """geodesic_shoot with its tangent-linear solution from (dx, dv) [C,Q] (dpgp_geodesic_shoot_tangent_f64): returns
+    (curve, vel, dcurve, dvel [C,S+1,Q], bad [C] int32, speed0 [C]), the BITS of models/geodesic._rk4_tangent on
+    ard_rbf_point_christoffel_tangent and geodesic_accel_tangent; speed0 = v^T G(x) v at the start.  Q <= 31; everything else as
+    geodesic_shoot."""
+    return _shoot(parts, prior, (x, v, dx, dv), num_steps, True)
 
 
 def ard_rbf_point_cov(z, x, gamma, alpha, c):

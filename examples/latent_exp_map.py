@@ -31,11 +31,13 @@ def main():
     ap.add_argument('--steps', type=int, default=64)
     ap.add_argument('--radius', type=float, default=3.0, help='the Riemannian length |v|_G of every ray')
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--integrator', choices=('host', 'device'), default='host', help='where the Runge-Kutta loop runs')
     args = ap.parse_args()
     np.random.seed(args.seed)
     y, _, block = synthetic.grouped_outputs(120, 18, seed=args.seed)
     q = 4
     model = dp_gp_lvm_t(y, num_latent_dims=q, num_inducing_points=20, truncation_level=4)
+    model.integrator = args.integrator
     model.optimise(args.iterations, learning_rate=0.05)
     x_mean = model.q_x[0].detach()
     centre = torch.argmin(((x_mean - x_mean.mean(dim=0)) ** 2).sum(dim=1))            # the training latent nearest the middle

@@ -33,11 +33,13 @@ def main():
     ap.add_argument('--descent', type=int, default=8)
     ap.add_argument('--eta', type=float, default=1.0)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--integrator', choices=('host', 'device'), default='host', help='where the Runge-Kutta loops run')
     args = ap.parse_args()
     np.random.seed(args.seed)
     y, _, block = synthetic.grouped_outputs(120, 18, seed=args.seed)
     q = 4
     model = dp_gp_lvm_t(y, num_latent_dims=q, num_inducing_points=20, truncation_level=4)
+    model.integrator = args.integrator
     model.optimise(args.iterations, learning_rate=0.05)
     x_mean = model.q_x[0].detach()
     group = model.assignments.detach().cpu().numpy().argmax(axis=1)

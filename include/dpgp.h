@@ -386,6 +386,43 @@ int dpgp_geodesic_accel_tangent_f64(int K, int N, int Q, const double *g, const 
                                     const double *dgam, const double *prior, const double *v, double *a, double *da,
                                     double *speed, int *info, void *stream);
 
+/* ---- The integrators of the geodesic equation on the device (csrc/geodesic_accel.hip): the classical Runge-Kutta solution of
+ *      (x', v') = (v, -G(x)^-1 Gamma(x, v)) on t in [0, 1] at step h = 1 / S for C curves from x[C][Q] with velocities v[C][Q], and
+ *      its tangent-linear solution (a discrete Jacobi field) from (dx, dv)[C][Q], all steps from ONE call.  The metric is given
+ *      as `parts` parts, part i being the kernels z[i][K_i][M_i][Q], gamma[i][K_i][Q], alpha[i][K_i] and p[i][K_i][M_i][M_i] of the
+ *      christoffel operators above (K, M: host arrays of `parts` ints; z, gamma, alpha, p: host arrays of `parts` device
+ *      pointers), plus the constant diagonal prior[Q]:  G = sum_i sum_k g_ik + diag(prior), kernels in part order.
+ *      Per stage the call enqueues dpgp_ard_rbf_point_christoffel[_tangent]_f64 once per part, each into its slice of one slab
+ *      array [sum_i K_i][C][..] in the workspace, and then one stage kernel, a workgroup of one wave per curve, which does
+ *      dpgp_geodesic_accel[_tangent]_f64's work on the slabs (the same code: slab sums in ascending k, Cholesky in LDS, the
+ *      solves) and applies the stage's share of the step to a per-curve state in the workspace:
+ *        next arguments  base + (h/2) k  (stage 3: base + h k),    running sums ((k1 + 2 k2) + 2 k3) + k4,
+ *        stage 4:        row s+1 = base + (h/6) sums               (each product rounded before its add)
+ *      with h, h/2 and h/6 formed in double on the host.  4 S (parts + 1) launches in order on `stream`; nothing is allocated
+ *      and nothing is read on the host; no atomics, no cooperative launch; the same bits on every run, and a curve's bits depend
+ *      neither on C nor on its place.  The results carry the bits of the host loop of models/geodesic.py on the two operators.
+ *        curve, vel[, dcurve, dvel] [C][S+1][Q]   the states after every step; row 0 holds the bits of x, v[, dx, dv]
+ *        bad[C]                                   the number of stages whose G failed to factor; such a stage leaves NaN in its
+ *                                                 curve from there on, the other curves are unaffected
+ *        speed0[C]  (tangent)                     v^T G(x) v at the start
+ *      1 <= parts <= 64;  1 <= K_i, M_i, C, S;  1 <= Q <= 63, tangent 1 <= Q <= 31.
+ *   Bad arguments, checked in this order before anything is launched:  parts -1, K (null, or an entry < 1) -2, M -3, Q -4, C -5,
+ *      S -6, z (null, or a null entry) -7, gamma -8, alpha -9, p -10, prior -11, x -12, v -13, then
+ *        shoot:          curve -14, vel -15, bad -16, ws -17, ws_bytes too small -18
+ *        shoot_tangent:  dx -14, dv -15, curve -16, vel -17, dcurve -18, dvel -19, bad -20, speed0 -21, ws -22, ws_bytes too small -23
+ *   ws: dpgp_geodesic_shoot_workspace_bytes (a host function; tangent != 0 for the tangent call) bytes: the slabs,
+ *      sum_i K_i C (Q Q + Q) doubles (tangent: twice that), and 6 (tangent: 12) C Q doubles of state; 0 for a shape out of range. */
+size_t dpgp_geodesic_shoot_workspace_bytes(int parts, const int *K, const int *M, int Q, int C, int tangent);
+int dpgp_geodesic_shoot_f64(int parts, const int *K, const int *M, int Q, int C, int S, const double *const *z,
+                            const double *const *gamma, const double *const *alpha, const double *const *p, const double *prior,
+                            const double *x, const double *v, double *curve, double *vel, int *bad, void *ws, size_t ws_bytes,
+                            void *stream);
+int dpgp_geodesic_shoot_tangent_f64(int parts, const int *K, const int *M, int Q, int C, int S, const double *const *z,
+                                    const double *const *gamma, const double *const *alpha, const double *const *p,
+                                    const double *prior, const double *x, const double *v, const double *dx, const double *dv,
+                                    double *curve, double *vel, double *dcurve, double *dvel, int *bad, double *speed0, void *ws,
+                                    size_t ws_bytes, void *stream);
+
 /* ---- Joint posterior covariance at deterministic latent points (csrc/ard_rbf_point_cov.hip): the off-diagonal that the per-point
  *      operators above leave out.  Kernels z[K][M][Q], gamma[K][Q], alpha[K] and points x[N][Q] as for the metric operator;
  *      c[K][G][M][M]: G matrices per kernel (one per training row pattern), any matrices.  With k_km as above,
