@@ -103,6 +103,9 @@ SIGNATURES = {
     'dpgp_ard_rbf_point_christoffel_tangent_workspace_bytes': (_sz, [_i] * 4),
     'dpgp_ard_rbf_point_christoffel_tangent_f64': (_i, [_i] * 4 + [_vp] * 12 + [_vp, _sz, _vp]),
     'dpgp_geodesic_accel_tangent_f64': (_i, [_i] * 3 + [_vp] * 10 + [_vp]),
+    'dpgp_ard_rbf_point_transport_workspace_bytes': (_sz, [_i] * 5),
+    'dpgp_ard_rbf_point_transport_f64': (_i, [_i] * 5 + [_vp] * 10 + [_vp, _sz, _vp]),
+    'dpgp_geodesic_transport_f64': (_i, [_i] * 4 + [_vp] * 9 + [_vp]),
     'dpgp_geodesic_shoot_workspace_bytes': (_sz, [_i, _vp, _vp, _i, _i, _i]),
     'dpgp_geodesic_shoot_f64': (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 10 + [_vp, _sz, _vp]),
     'dpgp_geodesic_shoot_tangent_f64': (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 15 + [_vp, _sz, _vp]),

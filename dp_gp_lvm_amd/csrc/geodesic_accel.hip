@@ -6,12 +6,16 @@
 // a = NaN; the other points never see it.  1 <= Q <= 64.
 // The tangent operator (gat_kernel) takes the tangent mode's (dg, dgam) as well and solves a second time with the same factor:
 //   da = -G^-1 (sum_k dgam[k][n] + (sum_k dg[k][n]) a);     a, speed and info carry ga_kernel's bits.
+// The transport operator (gt_kernel) takes the transport mode's tgam [K][N][F][Q] as well and solves for 1 + F right-hand sides in
+// ONE pair of substitutions on the same factor:
+//   dw_r = -G^-1 sum_k tgam[k][n][r]:     the rate of a vector w_r in parallel transport along the geodesic;  a, speed, info: ga_kernel's bits.
 // The integrators on the device (gs_kernel, dpgp_geodesic_shoot[_tangent]_f64): the same solve (ga_point, shared by all four
 // kernels) as one launch per Runge-Kutta stage, which also applies the stage's share of the classical RK4 step to a per-curve
 // state in the workspace; all C curves over all S steps from one C call, with the bits of the host loop of models/geodesic.py.
 #include "point_tile.h"
 
 #define GA_MAX_Q 64
+#define GT_MAX_F 63                 // the transport operator's right-hand sides beside a's
 
 namespace {
 
@@ -35,18 +39,22 @@ __device__ __forceinline__ double ga_slab_sum(const double *__restrict__ p, int 
 // of the failing pivot (uniform over the workgroup): nothing is solved then.  On success thread t < Q returns row t of a in res
 // (and of da in dres).  speed (this point's entry, or nullptr: not formed) receives v^T G v; sv, LDS, keeps v_n for the caller.
 __device__ __forceinline__ double gat_solve(const double *sA, double *sb, int Q, int LD, int t, bool row_live);
+__device__ __forceinline__ void gt_solve(const double *sA, double *sb, double *sy, int Q, int LD, int NR, int t, bool row_live);
 
-template <bool TAN>
+// TRN (gt_kernel): dgam is tgam [K][N][F][Q]; the 1 + F right-hand sides -sum_k gam, -sum_k tgam[.][r] are solved together and
+// the solutions are left in LDS, [1 + F][Q] from smem + Q (Q + 1) doubles on: thread t < Q reads row t of each, which it wrote.
+template <bool TAN, bool TRN = false>
 __device__ __forceinline__ int ga_point(unsigned char *smem, int K, int N, int Q, int n, const double *__restrict__ g,
                                         const double *__restrict__ gam, const double *__restrict__ dg,
                                         const double *__restrict__ dgam, const double *__restrict__ prior,
                                         const double *__restrict__ vel, double *__restrict__ speed, double &res, double &dres,
-                                        const double *&v_lds) {
+                                        const double *&v_lds, int F = 0) {
     const int LD = Q + 1;
     double *sA = reinterpret_cast<double *>(smem);          // [Q][Q + 1]  G, then L in its lower triangle
-    double *sb = sA + (size_t)Q * LD;                        // [Q]         the right-hand side, then y
-    double *sv = sb + Q;                                     // [Q]         v_n
+    double *sb = sA + (size_t)Q * LD;                        // [Q]         the right-hand side, then y    (TRN: [1 + F][Q])
+    double *sv = sb + (TRN ? (size_t)(1 + F) * Q : (size_t)Q);   // [Q]     v_n
     double *sr = sv + Q;                                     // [Q]         the rows' shares of v^T G v
+    double *sy = sr + Q;                                     // [1 + F][Q]  the forward substitutions' results          (TRN only)
     double *sD = sr + Q;                                     // [Q][Q + 1]  sum_k dg                       (TAN only, as the next two)
     double *sc = sD + (size_t)Q * LD;                        // [Q]         sum_k dgam
     double *sa = sc + Q;                                     // [Q]         a_n
@@ -63,6 +71,8 @@ __device__ __forceinline__ int ga_point(unsigned char *smem, int K, int N, int Q
         sb[t] = -ga_slab_sum(gam + (size_t)n * Q + t, K, (size_t)N * Q);
         sv[t] = vel[(size_t)n * Q + t];
         if (TAN) sc[t] = ga_slab_sum(dgam + (size_t)n * Q + t, K, (size_t)N * Q);
+        if constexpr (TRN)
+            for (int r = 0; r < F; ++r) sb[(1 + r) * Q + t] = -ga_slab_sum(dgam + ((size_t)n * F + r) * Q + t, K, (size_t)N * F * Q);
     }
     __syncthreads();
     if (speed) {                                              // (uniform)
@@ -95,6 +105,10 @@ __device__ __forceinline__ int ga_point(unsigned char *smem, int K, int N, int Q
             for (int c = j + 1; c <= t; ++c) sA[t * LD + c] = fma(-lij, sA[c * LD + j], sA[t * LD + c]);
     }
     if (fail) return fail;
+    if constexpr (TRN) {
+        gt_solve(sA, sb, sy, Q, LD, 1 + F, t, row_live);
+        return 0;
+    }
     res = gat_solve(sA, sb, Q, LD, t, row_live);
     if (TAN) {
         if (row_live) sa[t] = res;
@@ -130,6 +144,30 @@ __device__ __forceinline__ double gat_solve(const double *sA, double *sb, int Q,
     return res;
 }
 
+// gat_solve for NR right-hand sides sb [NR][Q] at once, each with gat_solve's statements on its own column (the same bits as NR
+// calls), the barriers paid once: thread t owns row t of every right-hand side.  sy [NR][Q]: y, which gat_solve keeps in a
+// register.  The solutions come back in sb; thread t wrote row t of each.
+__device__ __forceinline__ void gt_solve(const double *sA, double *sb, double *sy, int Q, int LD, int NR, int t, bool row_live) {
+    for (int j = 0; j < Q; ++j) {
+        __syncthreads();
+        const double ljj = sA[j * LD + j], ltj = t > j && row_live ? sA[t * LD + j] : 0.0;
+        for (int r = 0; r < NR; ++r) {
+            const double yj = sb[r * Q + j] / ljj;
+            if (t == j) sy[r * Q + j] = yj;
+            if (t > j && row_live) sb[r * Q + t] = fma(-ltj, yj, sb[r * Q + t]);
+        }
+    }
+    for (int j = Q - 1; j >= 0; --j) {
+        __syncthreads();
+        const double ljj = sA[j * LD + j], ljt = t < j ? sA[j * LD + t] : 0.0;
+        for (int r = 0; r < NR; ++r) {
+            const double rj = sy[r * Q + j] / ljj;
+            if (t == j) sb[r * Q + j] = rj;
+            if (t < j) sy[r * Q + t] = fma(-ljt, rj, sy[r * Q + t]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void ga_kernel(int K, int N, int Q, const double *__restrict__ g, const double *__restrict__ gam,
                                                 const double *__restrict__ prior, const double *__restrict__ vel,
                                                 double *__restrict__ acc, double *__restrict__ speed, int *__restrict__ info) {
@@ -160,6 +198,27 @@ __global__ __launch_bounds__(64) void gat_kernel(int K, int N, int Q, const doub
     if (row_live) {
         acc[(size_t)n * Q + t] = fail ? __builtin_nan("") : res;
         dacc[(size_t)n * Q + t] = fail ? __builtin_nan("") : dres;
+    }
+    if (t == 0) info[n] = fail;
+}
+
+// ga_kernel's work, statement for statement (a, speed and info come out with its bits), with the F right-hand sides of the
+// transport equation solved beside a's on the same factor (the prior is constant: it has no Christoffel symbols and enters G
+// only).  A failing pivot ends the point: a = dw = NaN.
+__global__ __launch_bounds__(64) void gt_kernel(int K, int N, int Q, int F, const double *__restrict__ g, const double *__restrict__ gam,
+                                                const double *__restrict__ tgam, const double *__restrict__ prior,
+                                                const double *__restrict__ vel, double *__restrict__ acc, double *__restrict__ dw,
+                                                double *__restrict__ speed, int *__restrict__ info) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int t = threadIdx.x, n = blockIdx.x;
+    const bool row_live = t < Q;
+    double res = 0.0, dres = 0.0;
+    const double *sv;
+    const int fail = ga_point<false, true>(smem_raw, K, N, Q, n, g, gam, nullptr, tgam, prior, vel, speed + n, res, dres, sv, F);
+    const double *sol = reinterpret_cast<const double *>(smem_raw) + (size_t)Q * (Q + 1);
+    if (row_live) {
+        acc[(size_t)n * Q + t] = fail ? __builtin_nan("") : sol[t];
+        for (int r = 0; r < F; ++r) dw[((size_t)n * F + r) * Q + t] = fail ? __builtin_nan("") : sol[(1 + r) * Q + t];
     }
     if (t == 0) info[n] = fail;
 }
@@ -256,6 +315,31 @@ extern "C" int dpgp_geodesic_accel_tangent_f64(int K, int N, int Q, const double
     if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(gat_kernel), lds)) return DPGP_ERR_LAUNCH;
     DPGP_PRELAUNCH();
     hipLaunchKernelGGL(gat_kernel, dim3((unsigned)N), dim3(64), lds, (hipStream_t)stream, K, N, Q, g, gam, dg, dgam, prior, v, a, da,
+                       speed, info);
+    DPGP_LAUNCH_CHECK();
+    return DPGP_OK;
+}
+
+extern "C" int dpgp_geodesic_transport_f64(int K, int N, int Q, int F, const double *g, const double *gam, const double *tgam,
+                                           const double *prior, const double *v, double *a, double *dw, double *speed, int *info,
+                                           void *stream) {
+    if (K < 1 || K > DPGP_POINT_MAX_N) return -1;
+    if (N < 1 || N > DPGP_POINT_MAX_N) return -2;
+    if (Q < 1 || Q > GA_MAX_Q) return -3;
+    if (F < 1 || F > GT_MAX_F) return -4;
+    if (!g) return -5;
+    if (!gam) return -6;
+    if (!tgam) return -7;
+    if (!prior) return -8;
+    if (!v) return -9;
+    if (!a) return -10;
+    if (!dw) return -11;
+    if (!speed) return -12;
+    if (!info) return -13;
+    const size_t lds = sizeof(double) * ((size_t)Q * (Q + 1) + 2 * (size_t)(1 + F) * Q + 2 * Q);       // 97.5 KiB at Q = 64, F = 63
+    if (dpgp_set_dyn_lds(reinterpret_cast<const void *>(gt_kernel), lds)) return DPGP_ERR_LAUNCH;
+    DPGP_PRELAUNCH();
+    hipLaunchKernelGGL(gt_kernel, dim3((unsigned)N), dim3(64), lds, (hipStream_t)stream, K, N, Q, F, g, gam, tgam, prior, v, a, dw,
                        speed, info);
     DPGP_LAUNCH_CHECK();
     return DPGP_OK;

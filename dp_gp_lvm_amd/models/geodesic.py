@@ -26,7 +26,13 @@ The Runge-Kutta loops of exp_map, exp_map_tangent and log_map run here, in Pytho
 `shoot`, a callable that returns the loop's results from elsewhere: marginals.Metric.shoot / shoot_tangent, ONE call of
 ops.geodesic_shoot[_tangent] per shot, with the loop's bits (a model's integrator = 'device').
 
-The three callables are the methods of ONE marginals.Metric, the metric that a public call runs under; the models' public methods
+Parallel transport: along a geodesic a vector w obeys G w' = -Gamma(x; x', w), the symbols contracted with the velocity and w.
+parallel_transport integrates (x', v', w_1' .. w_F') for a frame of F vectors by the same Runge-Kutta scheme on `transport`, a
+callable (x, v [N,Q], w [N,F,Q]) -> (a [N,Q], dw [N,F,Q], speed [N], info [N]) (marginals.Metric.transport on
+ops.ard_rbf_point_transport and ops.geodesic_transport); transport_to is log_map followed by it.  Its loop always runs here: there
+is no integrator on the device for it yet.
+
+The four callables are the methods of ONE marginals.Metric, the metric that a public call runs under; the models' public methods
 on them are written once, in models/latent_geometry.py.
 """
 import numpy as np
@@ -367,3 +373,100 @@ def log_map(accel_tangent, x_from, x_to, q, device, num_steps=64, max_iterations
     if single:
         return v[0], dist[0], curve[0], norm[0]
     return v, dist, curve.contiguous(), norm
+
+
+# ---- parallel transport along geodesics ---------------------------------------------------------------------------------------------
+def frames_arg(w, states, single, q, device):
+    """w [C x F x Q], or one vector per point in the shape of the states ([C x Q], [Q] where they came as [Q]), as a contiguous
+    fp64 tensor [C x F x Q] on the device, and whether it came as one vector."""
+    w = w.detach() if torch.is_tensor(w) else torch.as_tensor(np.asarray(w, dtype=np.float64))
+    w = w.to(device=device, dtype=TORCH_DTYPE)
+    c = states.shape[0]
+    one = w.dim() == (1 if single else 2)
+    assert one or (w.dim() == 3 and not single), 'w must be [N* x F x Q], or one vector per point in the shape of x'
+    w = (w.reshape(c, 1, q) if tuple(w.shape) == ((q,) if single else (c, q)) else None) if one else w
+    assert w is not None and w.shape[0] == c and w.shape[1] >= 1 and w.shape[2] == q, \
+        'w must be [N* x F x Q] with F >= 1, or one vector per point in the shape of x'
+    return w.contiguous(), one
+
+
+def parallel_transport_rate(transport, x, v, w, q, device):
+    """(a, dw): geodesic_acceleration's a [N* x Q] (or [Q]) with its bits, and dw in the shape of w, the rates
+    w_r' = -G(x)^-1 Gamma(x; v, w_r) of the vectors w ([N* x F x Q], or one vector per point [N* x Q] / [Q]) in parallel transport
+    along the geodesics through x with the velocities v: the right-hand side of the transport equation.  transport: a callable
+    (x, v [N,Q], w [N,F,Q]) -> (a [N,Q], dw [N,F,Q], speed [N], info [N]) that a model builds ONCE per call
+    (marginals.Metric.transport)."""
+    (xs, vs), single = states_arg(q, device, x=x, v=v)
+    ws, one = frames_arg(w, xs, single, q, device)
+    with torch.no_grad():
+        a, dw = transport(xs, vs, ws)[:2]
+    dw = dw[:, 0] if one else dw
+    return (a[0], dw[0]) if single else (a, dw)
+
+
+def _rk4_transport(transport, xs, vs, ws, num_steps):
+    """(curve, vel [C x S+1 x Q], frames [C x S+1 x F x Q], bad [C] int32): the classical RK4 on the state (x, v, w_1 .. w_F) from
+    xs, vs [C x Q] and ws [C x F x Q], with k_w = dw at each stage.  The x and v statements are _rk4's, and transport's a has
+    accel's bits: curve and vel are exp_map's, bit for bit; frames[:, 0] holds the bits of ws.  bad counts the stages whose
+    metric failed to factor.  Nothing is read on the host."""
+    c, q, h = xs.shape[0], xs.shape[1], 1.0 / num_steps
+    curve = torch.empty((c, num_steps + 1, q), dtype=xs.dtype, device=xs.device)
+    vel = torch.empty_like(curve)
+    frames = torch.empty((c, num_steps + 1) + tuple(ws.shape[1:]), dtype=xs.dtype, device=xs.device)
+    bad = torch.zeros(c, dtype=torch.int32, device=xs.device)
+
+    def f(xx, vv, ww):
+        nonlocal bad
+        a, dw, _, info = transport(xx, vv, ww)
+        bad = bad + (info != 0).to(torch.int32)
+        return a, dw
+
+    curve[:, 0], vel[:, 0], frames[:, 0] = xs, vs, ws
+    for s in range(num_steps):
+        k1x = vs
+        k1v, k1w = f(xs, vs, ws)
+        k2x = vs + (0.5 * h) * k1v
+        k2v, k2w = f(xs + (0.5 * h) * k1x, k2x, ws + (0.5 * h) * k1w)
+        k3x = vs + (0.5 * h) * k2v
+        k3v, k3w = f(xs + (0.5 * h) * k2x, k3x, ws + (0.5 * h) * k2w)
+        k4x = vs + h * k3v
+        k4v, k4w = f(xs + h * k3x, k4x, ws + h * k3w)
+        xs = xs + (h / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x)
+        vs = vs + (h / 6.0) * (k1v + 2.0 * k2v + 2.0 * k3v + k4v)
+        ws = ws + (h / 6.0) * (k1w + 2.0 * k2w + 2.0 * k3w + k4w)
+        curve[:, s + 1], vel[:, s + 1], frames[:, s + 1] = xs, vs, ws
+    return curve, vel, frames, bad
+
+
+def parallel_transport(transport, x, v, w, q, device, num_steps=64, return_curve=False):
+    """The vectors w ([C x F x Q], or one per curve [C x Q] / [Q]) at the points x, moved by parallel transport along the
+    geodesics exp_x(t v), t in [0, 1], to their ends: the frame at t = 1 in the shape of w, from the classical RK4 solution of
+    (x', v', w_r') = (v, a, dw_r) at step 1 / S, S = num_steps (_rk4_transport; the loop runs on the host).  With return_curve
+    (curve, velocity [C x S+1 x Q], frames [C x S+1 x F x Q]) (without the axes that x or w came without): curve and velocity are
+    exp_map's, bit for bit; frames' row 0 holds the bits of w.  Transport keeps every <w_i, w_j>_G up to the integrator's error,
+    and moves w = v as the velocity itself, bit for bit.  Four calls of transport per step; the stages' info is accumulated on
+    the device and read ONCE at the end: FloatingPointError if the metric failed to factor at any stage of any curve."""
+    (xs, vs), single = states_arg(q, device, x=x, v=v)
+    ws, one = frames_arg(w, xs, single, q, device)
+    num_steps = int(num_steps)
+    assert num_steps >= 1, 'num_steps >= 1'
+    with torch.no_grad():
+        curve, vel, frames, bad = _rk4_transport(transport, xs, vs, ws, num_steps)
+        failed = int(torch.count_nonzero(bad))
+        if failed:
+            raise FloatingPointError('latent_parallel_transport: the metric failed to factor (not positive definite in fp64) '
+                                     'along %d of %d curves' % (failed, xs.shape[0]))
+    if one:
+        frames = frames[:, :, 0]
+    if single:
+        curve, vel, frames = curve[0], vel[0], frames[0]
+    return (curve, vel, frames) if return_curve else frames[..., -1, :, :] if not one else frames[..., -1, :]
+
+
+def transport_to(accel_tangent, transport, x_from, x_to, w, q, device, num_steps=64, max_iterations=20, tol=1e-10, shoot=None):
+    """(w at x_to in the shape of w, v, distance, residual): the vectors w at x_from moved to x_to along the geodesic that joins
+    them: log_map(x_from, x_to) finds its initial velocity v (with distance and residual as there; a pair that does not converge
+    is reported through residual, and its vectors are moved along the geodesic that v does give), parallel_transport moves w
+    along it at the same num_steps.  shoot: log_map's."""
+    v, dist, _, res = log_map(accel_tangent, x_from, x_to, q, device, num_steps, max_iterations, tol, shoot=shoot)
+    return parallel_transport(transport, x_from, v, w, q, device, num_steps), v, dist, res

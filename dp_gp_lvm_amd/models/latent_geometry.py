@@ -1,9 +1,10 @@
 """
 The latent-geometry surface of the four latent-variable models, written once: magnification, curve energy and length, geodesics
-between two points, the geodesic acceleration and exponential map, their tangents and the logarithm map.  Every model's metric is
+between two points, the geodesic acceleration and exponential map, their tangents, the logarithm map and parallel transport
+along geodesics.  Every model's metric is
 one marginals.Metric (a sum over parts b_k(x)^T P_k b_k(x) plus constant diagonal terms), so the methods differ between the models
 only in how that value is built: a model supplies ONE hook from its closure and its own latent_metric, and models/geodesic.py does
-the work on the Metric's three callables.
+the work on the Metric's four callables.
 
     LatentGeometry        bayesian_gp_lvm, dp_gp_lvm, dp_gp_lvm_t (columns=): the hook _metric_of(columns, name) -> Metric
     ViewsLatentGeometry   manifold_relevance_determination (views=, total=): the hook _metrics_of(views, total) -> [Metric, ...]
@@ -30,7 +31,8 @@ class _Integrator:
     """The attribute `integrator` of a model: where the Runge-Kutta loops of latent_exp_map, latent_exp_map_tangent and
     latent_log_map run.  'host' (the default: the Python loops of models/geodesic.py) or 'device' (the same steps, to the same
     bits, from one C call per shot); assigning anything else raises ValueError.  An attribute and not a keyword
-    of the three methods: their signatures are pinned."""
+    of the three methods: their signatures are pinned.  The loop of latent_parallel_transport (and of the transport half of
+    latent_transport_to) runs on the host whatever the value: there is no transport shot on the device yet."""
     _integrator = 'host'
 
     @property
@@ -134,6 +136,39 @@ class LatentGeometry(_Integrator):
         return _geodesic.log_map(metric.accel_tangent, x_from, x_to, self._latent_dims, self._device, num_steps, max_iterations,
                                  tol, init, shoot=_shoot_of(metric, self.integrator, True))
 
+    def parallel_transport_rate(self, x, v, w, columns=None):
+        """(a, dw): geodesic_acceleration(x, v, columns), with its bits, and the rates w_r' = -G(x)^-1 Gamma(x; v, w_r) of the
+        vectors w in parallel transport along the geodesics through x with the velocities v under latent_metric(., columns):
+        the right-hand side of the transport equation, Gamma the Christoffel symbols of the first kind contracted with v and
+        w_r, in closed form.  w: a frame [N* x F x Q], or one vector per point [N* x Q] ([Q] with x, v [Q]); dw comes in the
+        shape of w.  One call of ops.ard_rbf_point_transport and one of ops.geodesic_transport, whatever F; the training side
+        is built once per call.  Q + 1 + F <= 64.  fp64, torch.no_grad."""
+        metric = self._metric_of(columns, 'parallel_transport_rate')
+        return _geodesic.parallel_transport_rate(metric.transport, x, v, w, self._latent_dims, self._device)
+
+    def latent_parallel_transport(self, x, v, w, num_steps=64, columns=None, return_curve=False):
+        """The vectors w at the latent points x after parallel transport along the geodesics exp_x(t v), t in [0, 1], under
+        latent_metric(., columns): the frame at t = 1 in the shape of w ([C x F x Q], or one vector per curve [C x Q] / [Q]), the
+        classical RK4 solution of (x', v', w_r') = (v, -G^-1 Gamma(v, v), -G^-1 Gamma(v, w_r)) at step 1 / num_steps
+        (models/geodesic.parallel_transport).  With return_curve (curve, velocity, frames), every step's state: curve and
+        velocity are latent_exp_map(x, v, num_steps, columns, return_velocity=True), bit for bit; frames' row 0 holds the bits
+        of w.  Transport keeps the inner products <w_i, w_j>_G up to the integrator's error (fourth order) and moves w = v as
+        the velocity itself.  A stage is one call of ops.ard_rbf_point_transport and one of ops.geodesic_transport for the
+        whole frame; one host read at the end: FloatingPointError if the metric failed to factor at any stage.  The loop runs
+        on the host whatever self.integrator says.  Q + 1 + F <= 64.  fp64, torch.no_grad."""
+        metric = self._metric_of(columns, 'latent_parallel_transport')
+        return _geodesic.parallel_transport(metric.transport, x, v, w, self._latent_dims, self._device, num_steps, return_curve)
+
+    def latent_transport_to(self, x_from, x_to, w, num_steps=64, max_iterations=20, tol=1e-10, columns=None):
+        """(w at x_to, v, distance, residual): the vectors w at x_from ([C x F x Q], [C x Q] or [Q]) moved to x_to along the
+        geodesic that joins them under latent_metric(., columns): latent_log_map(x_from, x_to, num_steps, max_iterations, tol,
+        columns) gives v, distance and residual, latent_parallel_transport moves w along exp_{x_from}(t v) at the same
+        num_steps.  A pair that does not converge is reported through residual, as in the logarithm map.  self.integrator
+        governs the logarithm map's shots; the transport loop runs on the host.  Q <= 31.  fp64, torch.no_grad."""
+        metric = self._metric_of(columns, 'latent_transport_to')
+        return _geodesic.transport_to(metric.accel_tangent, metric.transport, x_from, x_to, w, self._latent_dims, self._device,
+                                      num_steps, max_iterations, tol, shoot=_shoot_of(metric, self.integrator, True))
+
 
 class ViewsLatentGeometry(_Integrator):
     """The methods of manifold_relevance_determination: one result per view of `views` (default: all V, in order), each under the
@@ -209,4 +244,26 @@ class ViewsLatentGeometry(_Integrator):
         The training side of all views is built once per call.  self.integrator: as latent_exp_map."""
         return self._per_metric(views, total, lambda m: _geodesic.log_map(
             m.accel_tangent, x_from, x_to, self._latent_dims, self._device, num_steps, max_iterations, tol, init,
+            shoot=_shoot_of(m, self.integrator, True)))
+
+    def parallel_transport_rate(self, x, v, w, views=None, total=False):
+        """One pair (a, dw) per view of `views` (default: all V, in order), as bayesian_gp_lvm.parallel_transport_rate under the
+        view's latent_metric; total=True: one pair, under the summed metric (one ops.ard_rbf_point_transport call per view and
+        one ops.geodesic_transport).  The training side of all views is built once per call."""
+        return self._per_metric(views, total, lambda m: _geodesic.parallel_transport_rate(
+            m.transport, x, v, w, self._latent_dims, self._device))
+
+    def latent_parallel_transport(self, x, v, w, num_steps=64, views=None, total=False, return_curve=False):
+        """One transported frame (with return_curve one triple (curve, velocity, frames)) per view of `views`, as
+        bayesian_gp_lvm.latent_parallel_transport under the view's latent_metric; total=True: one result, under the summed
+        metric.  The loop runs on the host whatever self.integrator says."""
+        return self._per_metric(views, total, lambda m: _geodesic.parallel_transport(
+            m.transport, x, v, w, self._latent_dims, self._device, num_steps, return_curve))
+
+    def latent_transport_to(self, x_from, x_to, w, num_steps=64, max_iterations=20, tol=1e-10, views=None, total=False):
+        """One result (w at x_to, v, distance, residual) per view of `views`, as bayesian_gp_lvm.latent_transport_to under the
+        view's latent_metric; total=True: one result, under the summed metric.  self.integrator governs the logarithm map's
+        shots; the transport loop runs on the host."""
+        return self._per_metric(views, total, lambda m: _geodesic.transport_to(
+            m.accel_tangent, m.transport, x_from, x_to, w, self._latent_dims, self._device, num_steps, max_iterations, tol,
             shoot=_shoot_of(m, self.integrator, True)))

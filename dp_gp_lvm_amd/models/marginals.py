@@ -180,7 +180,7 @@ class Metric:
     diagonal metrics.  parts: a list of (marg: _Marginals, P [K, M, M], prior [K, Q, Q]), _metric_operands' pair behind its
     _Marginals (one part per model; MRD's summed metric has one per view); extra: further constant diagonal metrics [*, Q, Q] or
     None (only the diagonals of prior and extra are read).  No part and an extra is the prior-only metric (dp_gp_lvm with no
-    chosen column observed in training).  Several parts with an extra occur nowhere and are refused.  Its three methods are the
+    chosen column observed in training).  Several parts with an extra occur nowhere and are refused.  Its four methods are the
     callables of models/geodesic.py; every one runs in blocks of points of at most 2^25 result entries, and a point's bits do not
     depend on its block.  shoot and shoot_tangent are the integrators on the device over accel and accel_tangent: whole
     Runge-Kutta solutions with the bits of geodesic.py's loops, blocked over the curves in the same way.
@@ -239,6 +239,20 @@ class Metric:
         return self._solve(ops.ard_rbf_point_christoffel_tangent, ops.geodesic_accel_tangent, 2,
                            (x.contiguous(), v.contiguous(), dx.contiguous(), dv.contiguous()))
 
+    def transport(self, x, v, w):
+        """(a [N, Q], dw [N, F, Q], speed [N], info [N] int32): accel's triple with its bits, and the rates
+        dw_r = -G(x)^-1 Gamma(x; v, w_r) of the vectors w [N, F, Q] in parallel transport along the geodesics through x with the
+        velocities v.  One call of ops.ard_rbf_point_transport per part gives the slabs (g_k, Gamma_k, Gamma_k(v, w_r)), one
+        call of ops.geodesic_transport sums them and solves for all 1 + F right-hand sides with one factor.  K (Q^2 + Q + F Q)
+        entries per point go into the 2^25-entry blocks.  Q + 1 + F <= 64.  The prior-only metric has no symbols: dw = 0."""
+        if not self.parts:
+            a, speed, info = self.accel(x, v)
+            return a, torch.zeros_like(w), speed, info
+        q, f = self.q, w.shape[1]
+        step = self.block * (q * q + q) // (q * q + q + f * q)          # accel's points per block, scaled to this call's entries
+        return self._solve(ops.ard_rbf_point_transport, ops.geodesic_transport, 1, (x.contiguous(), v.contiguous(), w.contiguous()),
+                           step=step)
+
     def shoot(self, x, v, num_steps):
         """(curve, vel [C, S+1, Q], bad [C] int32): geodesic._rk4 on accel from the states x, v [C, Q], with its bits, by the
         integrator on the device: ONE call of ops.geodesic_shoot per block of curves (accel's points per block) runs every
@@ -263,12 +277,12 @@ class Metric:
                   for i in range(0, n, step)]
         return blocks[0] if len(blocks) == 1 else tuple(torch.cat(bs) for bs in zip(*blocks))
 
-    def _solve(self, slabs_of, solve, width, state):
-        """solve(the parts' concatenated slabs_of(state), w, v) per block of the points of state = (x, v[, dx, dv]), `width` times
-        accel's entries per point.  A stage of an integrator comes here: one block (the usual case) is neither sliced nor
-        concatenated."""
+    def _solve(self, slabs_of, solve, width, state, step=None):
+        """solve(the parts' concatenated slabs_of(state), w, v) per block of the points of state = (x, v[, dx, dv | w]), `width`
+        times accel's entries per point (or `step` points per block, where the caller counts them itself).  A stage of an
+        integrator comes here: one block (the usual case) is neither sliced nor concatenated."""
         parts, w, n = self.parts, self.w, state[0].shape[0]
-        step = max(1, self.block // width)
+        step = max(1, self.block // width if step is None else step)
         blocks = []
         for i in range(0, n, step):
             sb = state if step >= n else [t[i:i + step] for t in state]

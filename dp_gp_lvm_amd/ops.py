@@ -489,14 +489,16 @@ def psi_latent_adjoint(z, mu, s, gamma, alpha, y, g_v, g_psi2, weights=None):
     return d_mu, d_s
 
 
-def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None, prior=None):
-    """The checks of the five point operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
+def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None, prior=None, frame=None):
+    """The checks of the six point operators below: float64 tensors (TypeError), of the stated shapes (ValueError), on one GPU
     (RuntimeError), in this order; `a` is the last operand (`name`: p [K,M,M], r [K,M,J] or c [K,G,M,M], `what` its wording);
     dirs: the directions v [N,Q] of ard_rbf_point_energy / ard_rbf_point_christoffel (a one-element tuple), or (v, dx, dv) of
     ard_rbf_point_christoffel_tangent, checked in their place after x; max_q: an operator's own limit on Q (ValueError, after the
-    shapes); prior: the constant diagonal metric [Q] of geodesic_shoot, checked after `a`."""
+    shapes); prior: the constant diagonal metric [Q] of geodesic_shoot, checked after `a`; frame: the vectors w [N,F,Q] of
+    ard_rbf_point_transport, checked after the directions, and Q + 1 + F <= 64 where max_q is."""
     dirs = () if dirs is None else tuple(zip(('v', 'dx', 'dv'), dirs))
-    args = (('z', z), ('x', x)) + dirs + (('gamma', gamma), ('alpha', alpha), (name, a)) + (() if prior is None else (('prior', prior),))
+    wdir = () if frame is None else (('w', frame),)
+    args = (('z', z), ('x', x)) + dirs + wdir + (('gamma', gamma), ('alpha', alpha), (name, a)) + (() if prior is None else (('prior', prior),))
     for nm, v in args:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % nm)
@@ -508,6 +510,8 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None,
     for nm, v in dirs:
         if tuple(v.shape) != tuple(x.shape):
             raise ValueError('%s must be [N x Q] as x, got %s' % (nm, tuple(v.shape)))
+    if frame is not None and (frame.dim() != 3 or frame.shape[0] != x.shape[0] or frame.shape[1] < 1 or frame.shape[2] != q):
+        raise ValueError('w must be [N x F x Q] with N, Q as x and F >= 1, got %s' % (tuple(frame.shape),))
     if tuple(gamma.shape) != (k, q):
         raise ValueError('gamma must be [K x Q], got %s' % (tuple(gamma.shape),))
     if alpha.numel() != k:
@@ -522,6 +526,8 @@ def _point_metric_args(z, x, gamma, alpha, a, name, what, dirs=None, max_q=None,
         raise ValueError('prior must be [Q], got %s' % (tuple(prior.shape),))
     if max_q is not None and q > max_q:
         raise ValueError('z must have Q <= %d, got Q = %d' % (max_q, q))
+    if frame is not None and q + 1 + frame.shape[1] > 64:
+        raise ValueError('z and w must have Q + 1 + F <= 64, got Q = %d, F = %d' % (q, frame.shape[1]))
     for nm, v in args:
         if not v.is_cuda or v.device != z.device:
             raise RuntimeError('%s must live on the GPU of z: dp_gp_lvm_amd runs its operators in HIP only' % nm)
@@ -619,9 +625,32 @@ def ard_rbf_point_christoffel_tangent(z, x, v, dx, dv, gamma, alpha, p):
     return g, gam, dg, dgam
 
 
+def ard_rbf_point_transport(z, x, v, w, gamma, alpha, p):
+    """ard_rbf_point_christoffel's pair and the Christoffel symbols that move a frame of F vectors w [N,F,Q] along the velocities
+    v [N,Q] (dpgp_ard_rbf_point_transport_f64): with u_q = gamma_kq (x_nq - z_kmq), k, b as there, a_v = sum_q u_q v_q and
+        a_w = sum_q u_q w_q,     d(v, w) = v^T (d^2 k / dx dx) w = k (a_v a_w - sum_q gamma_kq v_q w_q)
+    returns (g, gam, tgam),
+        g [K,N,Q,Q], gam [K,N,Q]     the bits of ard_rbf_point_christoffel(z, x, v, gamma, alpha, p)
+        tgam [K,N,F,Q] = sum_{m,m'} b_kmq(x_n) p[k,m,m'] d_knm'(v, w_r)
+    p [K,M,M] is used as given (not symmetrised); for a SYMMETRIC p, tgam is the Christoffel symbol of the first kind of g
+    contracted with v and w_r, so that parallel transport along a geodesic of G = G0 + sum_k g_k with velocity v obeys
+    G w_r' = -sum_k tgam_k[r].  One launch, all three results from one product over the feature block [b | d(v,v) | d(v,w_1) ..
+    d(v,w_F)]; nothing of size N M in memory; fixed summation order, the same bits on every run.  A vector's tgam depends
+    neither on F, nor on its place in the frame, nor on the other vectors; for w_r = v it has the bits of gam; exact zeros for
+    w_r = 0.  Q + 1 + F <= 64 (ValueError).  float64 tensors (TypeError) of these shapes (ValueError) on one GPU (RuntimeError)."""
+    z, x, gamma, alpha, p, k, n, m, q = _point_metric_args(z, x, gamma, alpha, p, 'p', '[K x M x M]', dirs=(v,), frame=w)
+    v, w = v.contiguous(), w.contiguous()
+    f = w.shape[1]
+    g = torch.empty((k, n, q, q), dtype=torch.float64, device=z.device)
+    gam = torch.empty((k, n, q), dtype=torch.float64, device=z.device)
+    tgam = torch.empty((k, n, f, q), dtype=torch.float64, device=z.device)
+    _point_call('transport', (k, n, m, q, f), (z, x, v, w, gamma, alpha, p), (g, gam, tgam))
+    return g, gam, tgam
+
+
 def _accel_args(args):
-    """The checks of geodesic_accel / geodesic_accel_tangent on (('g', g), ('gam', gam)[, ('dg', dg), ('dgam', dgam)],
-    ('prior', prior), ('v', v)): contiguous tensors in that order and (K, N, Q)."""
+    """The checks of geodesic_accel / geodesic_accel_tangent / geodesic_transport on (('g', g), ('gam', gam)[, ('dg', dg),
+    ('dgam', dgam) or ('tgam', tgam)], ('prior', prior), ('v', v)): contiguous tensors in that order and (K, N, Q)."""
     for nm, t in args:
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
             raise TypeError('%s must be a float64 torch.Tensor' % nm)
@@ -632,7 +661,10 @@ def _accel_args(args):
     want = dict(gam=((k, n, q), '[K x N x Q] as g'), dg=((k, n, q, q), '[K x N x Q x Q] as g'), dgam=((k, n, q), '[K x N x Q] as g'),
                 prior=((q,), '[Q]'), v=((n, q), '[N x Q]'))
     for nm, t in args[1:]:
-        if tuple(t.shape) != want[nm][0]:
+        if nm == 'tgam':
+            if t.dim() != 4 or tuple(t.shape[:2]) != (k, n) or not 1 <= t.shape[2] <= 63 or t.shape[3] != q:
+                raise ValueError('tgam must be [K x N x F x Q] with K, N, Q as g and 1 <= F <= 63, got %s' % (tuple(t.shape),))
+        elif tuple(t.shape) != want[nm][0]:
             raise ValueError('%s must be %s, got %s' % (nm, want[nm][1], tuple(t.shape)))
     for nm, t in args:
         if not t.is_cuda or t.device != g.device:
@@ -657,6 +689,26 @@ def geodesic_accel_tangent(g, gam, dg, dgam, prior, v):
                                                           speed.data_ptr(), info.data_ptr(), _stream()),
                'dpgp_geodesic_accel_tangent_f64')
     return a, da, speed, info
+
+
+def geodesic_transport(g, gam, tgam, prior, v):
+    """geodesic_accel and the rates of a frame in parallel transport from ard_rbf_point_transport's three results
+    (dpgp_geodesic_transport_f64): returns (a, dw, speed, info); a, speed and info carry the bits of
+    geodesic_accel(g, gam, prior, v), and with the same factor
+        dw [N,F,Q] = -G_n^-1 sum_k tgam[k,n,r]                                (k ascending; the constant prior enters G only)
+    all 1 + F right-hand sides in one pair of substitutions.  Where tgam[:, n, r] has the bits of gam[:, n], dw[n, r] has the
+    bits of a[n].  info[n] != 0: a[n, :] and dw[n, :, :] are NaN and the other points are unaffected.  tgam [K,N,F,Q] with
+    F <= 63; everything else as geodesic_accel."""
+    (g, gam, tgam, prior, v), k, n, q = _accel_args((('g', g), ('gam', gam), ('tgam', tgam), ('prior', prior), ('v', v)))
+    f = tgam.shape[2]
+    a = torch.empty((n, q), dtype=torch.float64, device=g.device)
+    dw = torch.empty((n, f, q), dtype=torch.float64, device=g.device)
+    speed = torch.empty((n,), dtype=torch.float64, device=g.device)
+    info = torch.empty((n,), dtype=torch.int32, device=g.device)
+    _lib.check(_lib.lib().dpgp_geodesic_transport_f64(k, n, q, f, g.data_ptr(), gam.data_ptr(), tgam.data_ptr(), prior.data_ptr(),
+                                                      v.data_ptr(), a.data_ptr(), dw.data_ptr(), speed.data_ptr(), info.data_ptr(),
+                                                      _stream()), 'dpgp_geodesic_transport_f64')
+    return a, dw, speed, info
 
 
 def geodesic_accel(g, gam, prior, v):

@@ -386,6 +386,38 @@ int dpgp_geodesic_accel_tangent_f64(int K, int N, int Q, const double *g, const 
                                     const double *dgam, const double *prior, const double *v, double *a, double *da,
                                     double *speed, int *info, void *stream);
 
+/* ---- Parallel transport along a geodesic (csrc/ard_rbf_point_metric.hip, csrc/geodesic_accel.hip): what one stage of an
+ *      integrator of the transport equation w' = -G^-1 Gamma(x; v, w) needs, for a frame of F vectors w[N][F][Q] at once.
+ *      With u_q, k, b_q, a = a_v, d = d(v,v) as above and, per vector w_r of the frame,
+ *        a_w = sum_q u_q w_q,     d(v,w) = v^T (d^2 k / dx dx) w = k (a_v a_w - sum_q gamma_kq v_q w_q)
+ *      the first operator gives g and gam, WITH THE BITS of dpgp_ard_rbf_point_christoffel_f64, and
+ *        tgam[K][N][F][Q] = B^T p d(v,w_r)                                                               (p used as given)
+ *      which for a symmetric p is the Christoffel symbol of the first kind of g contracted with v and w_r.
+ *      One launch: the same kernel with the feature block [B | d(v,v) | d(v,w_1) .. d(v,w_F)], W = Q + 1 + F columns,
+ *      ceil(W / 16) column tiles; tgam[..][r][:] is rows 0 .. Q-1 of column Q + 1 + r of the one product.  Result tiles below
+ *      row Q are not formed.  d(v,w) is made with the statements of d(v,v): for w_r = v, tgam[..][r][:] has the bits of gam; a
+ *      vector's tgam depends neither on F, nor on r, nor on the other vectors.  The rules of the operators above hold: nothing of
+ *      size N M in memory, no atomics, sums ordered by (M, Q) alone, a point's bits independent of N, its place and K, exact
+ *      zeros far from every z and for w = 0.  1 <= K, N, M, Q, F;  Q + 1 + F <= 64.
+ *   Bad arguments, checked in this order before anything is launched:  K -1, N -2, M -3, Q -4, F -5, z -6, x -7, v -8, w -9,
+ *      gamma -10, alpha -11, p -12, g -13, gam -14, tgam -15, ws -16, ws_bytes too small -17.
+ *   ws: as above, a token 256 bytes for a shape in range, 0 for one out of range.
+ *      The finishing operator takes the three results, prior[Q] and v[N][Q] and gives a, speed and info WITH THE BITS of
+ *      dpgp_geodesic_accel_f64 on (g, gam), and with the same factor of G (the constant prior has no Christoffel symbols)
+ *        dw[N][F][Q] = -G^-1 sum_k tgam[k][n][r]                                  (k ascending)
+ *      all 1 + F right-hand sides in one pair of substitutions, each with the statements of a's: where tgam[..][r][:] has the
+ *      bits of gam, dw[n][r][:] has the bits of a[n][:].  A pivot that is not positive ends that point alone: info = its 1-based
+ *      index, a[n][:] = dw[n][:][:] = NaN.  1 <= K, N;  1 <= Q <= DPGP_QX_PSI_MAX_Q;  1 <= F <= 63.
+ *   Bad arguments, in this order:  K -1, N -2, Q -3, F -4, g -5, gam -6, tgam -7, prior -8, v -9, a -10, dw -11, speed -12,
+ *      info -13. */
+size_t dpgp_ard_rbf_point_transport_workspace_bytes(int K, int N, int M, int Q, int F);
+int dpgp_ard_rbf_point_transport_f64(int K, int N, int M, int Q, int F, const double *z, const double *x, const double *v,
+                                     const double *w, const double *gamma, const double *alpha, const double *p, double *g,
+                                     double *gam, double *tgam, void *ws, size_t ws_bytes, void *stream);
+int dpgp_geodesic_transport_f64(int K, int N, int Q, int F, const double *g, const double *gam, const double *tgam,
+                                const double *prior, const double *v, double *a, double *dw, double *speed, int *info,
+                                void *stream);
+
 /* ---- The integrators of the geodesic equation on the device (csrc/geodesic_accel.hip): the classical Runge-Kutta solution of
  *      (x', v') = (v, -G(x)^-1 Gamma(x, v)) on t in [0, 1] at step h = 1 / S for C curves from x[C][Q] with velocities v[C][Q], and
  *      its tangent-linear solution (a discrete Jacobi field) from (dx, dv)[C][Q], all steps from ONE call.  The metric is given
